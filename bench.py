@@ -1,8 +1,14 @@
 #!/usr/bin/env python
-"""Headline benchmark: observations/sec per LM iteration (+ final RMS reprojection error, px).
+"""Headline benchmark: observations/sec per LM iteration (``--full``: + final RMS reprojection error, px, and the figures below).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4] [--scaling strong|weak] [--no-cpu] [--also cfg2,cfg3,cfg5]
-                    [--devices 0,1,..] [--xchg auto|rccl|direct]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4] [--scaling strong|weak] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-first-call] [--also cfg2,cfg3,cfg5]] [--devices 0,1,..] [--xchg auto|rccl|direct]
+
+A plain run does what the headline needs and no more: it generates the scene, builds the handle, warms up, times K steps and prints
+one JSON line (``value``, ``ms_per_step`` = the milliseconds of one timed step).  ``--dump-outputs DIR`` writes what the last timed
+step returned (the solution x and its scalars, float64 .npy) so that two builds can be compared on the same seeded inputs.  Everything
+else is measured only with ``--full``: the instrumented repeat (``roofline``, ``comm_ms_per_step``), the full solve (``final_rms_px``,
+``solve``), the first-call and warm set-up figures, ``cpu_baseline`` / ``parity`` and the ``also`` workloads.
 
 ``--gpus N`` works two ways.  Under a launcher that sets RANK / WORLD_SIZE (``python -m torch.distributed.run --nproc-per-node N ...``)
 this process is one rank of N.  Started plainly, the N ranks run INSIDE this process — one host thread per device, the engines joined
@@ -24,8 +30,8 @@ Workload (``config.workload``): BASELINE.json's multi-GPU configuration cfg4 —
 words it ("2M obs sharded across 8 x MI355X"): the same 2M observations, their points partitioned over the N ranks
 (caliscope_amd/sharding.py), the camera blocks and the reduced camera system all-reduced over RCCL each iteration;
 ``--scaling weak`` gives every rank its own 200k-point shard of the same 64 cameras instead.  The other configs (cfg2,
-cfg3, and cfg5 = 128 cameras / 1M points / 10M observations with joint intrinsics, on one GPU) are run
-untimed-by-the-driver after the headline and reported under ``also`` (cfg5 with its full roofline block).
+cfg3, and cfg5 = 128 cameras / 1M points / 10M observations with joint intrinsics, on one GPU) are run with ``--full``,
+untimed-by-the-driver after the headline, and reported under ``also`` (cfg5 with its full roofline block).
 
 ``cpu_baseline`` is the reference's scipy call on the headline's OWN arrays (full cfg4: 4 evaluations, ~25 s on one host core);
 ``parity`` compares its solution with the headline's solve on the device (RMS px, cost, gauge-aligned poses / points) and times the
@@ -127,10 +133,13 @@ class _Solo:
 
 
 def measure(name, steps, warmup, device_id=0, timers=True, seed=42, solve_kw=None, control=None, scaling="strong", group=None, prebuilt=None,
-            on_engine=None, count="trials", with_first_call=True, **overrides):
+            on_engine=None, count="trials", with_first_call=True, full=True, keep_x=False, **overrides):
     """Strong scaling: every rank generates the same scene and keeps the shard of points ``shard_problem`` gives it.
     Weak scaling: rank r draws its own points/observations of the same cameras.  Either way the engine all-reduces the
-    camera blocks, the reduced camera system and the scalar sums over RCCL."""
+    camera blocks, the reduced camera system and the scalar sums over RCCL.
+
+    ``full=False`` stops after the timed steps (the plain bench run): no instrumented repeat, no full solve for the accuracy figures, no
+    first-call or warm set-up measurements.  ``keep_x``: the record carries ``x_last``, the x the last timed solve ended at."""
     from caliscope_amd.hip_engine import HipEngine
     from caliscope_amd.sharding import shard_problem
 
@@ -179,6 +188,19 @@ def measure(name, steps, warmup, device_id=0, timers=True, seed=42, solve_kw=Non
     solves, last = run_iterations(eng, steps, solve_kw, count)  # every engine call ends with a stream synchronize
     control.barrier()
     elapsed = control.allreduce_max(time.perf_counter() - t0)
+    # (fetch_x=True would have downloaded this same vector at the end of the last solve: cba_solve reads CBA_VEC_X)
+    x_last = eng.current_x() if keep_x else None
+    rec = {
+        "name": name, "n_obs": prob.n_obs, "n_obs_total": n_total if n_total is not None else prob.n_obs * control.world,
+        "n_points": par.n_points, "n_cams": len(par.blocks), "ncp": par.n_camera_params,
+        "nct": 9 if any(b.n_params == 9 for b in par.blocks) else 6, "loss": prob.loss, "elapsed": elapsed, "steps": steps,
+        "solves": solves, "timers": {}, "info": info, "t_generate_s": t_gen, "scene": sc, "par": par, "x0": x0, "setup_s": t_setup,
+        "plan_wait_s": t_plan, "rank": control.rank, "mix": last.mix, "last": last, "x_last": x_last,
+        "two_stage": two_stage, "first_call": None, "count": count, "deterministic": deterministic,
+    }
+    if not full:
+        eng.close()
+        return rec
     # instrumented repeat of the same `steps` iterations: HIP events around every kernel family on the engine's
     # stream.  Kept out of the region above because recording ~40 event pairs per iteration costs 6 % (cfg4) to
     # 50 % (cfg2) of the wall time, which would understate `value`.
@@ -236,15 +258,11 @@ def measure(name, steps, warmup, device_id=0, timers=True, seed=42, solve_kw=Non
             again.append(time.perf_counter() - t_w)
             e2.close()
         t_setup_warm = float(np.median(again))
-    return {
-        "name": name, "n_obs": prob.n_obs, "n_obs_total": n_total if n_total is not None else prob.n_obs * control.world,
-        "n_points": par.n_points, "n_cams": len(par.blocks), "ncp": par.n_camera_params, "full_njev": full.njev,
-        "nct": 9 if any(b.n_params == 9 for b in par.blocks) else 6, "loss": prob.loss, "elapsed": elapsed, "steps": steps,
-        "solves": solves, "timers": tm, "final_rms_px": rms, "initial_rms_px": rms0, "full_nfev": full.nfev,
-        "full_status": full.status, "full_cost": full.cost, "info": info, "t_generate_s": t_gen,
-        "scene": sc, "par": par, "x0": x0, "x_full": full.x, "setup_s": t_setup, "setup_warm_s": t_setup_warm, "plan_wait_s": t_plan, "rank": control.rank, "mix": last.mix,
-        "two_stage": two_stage, "first_call": first_call, "count": count, "deterministic": deterministic,
-    }
+    rec.update({
+        "timers": tm, "final_rms_px": rms, "initial_rms_px": rms0, "full_nfev": full.nfev, "full_njev": full.njev, "full_status": full.status,
+        "full_cost": full.cost, "x_full": full.x, "setup_warm_s": t_setup_warm, "first_call": first_call,
+    })
+    return rec
 
 
 # kernels of each timer family in the rocprofv3 summaries (the Schur pass is k_tprep + k_schur_reg3)
@@ -709,7 +727,7 @@ def run_ranks_in_process(args, devices, xchg):
 
         try:
             records[rank] = measure(args.workload, args.steps, args.warmup, device_id=devices[rank], control=ctl, scaling=args.scaling,
-                                    group=group, prebuilt=prebuilt, on_engine=keep)
+                                    group=group, prebuilt=prebuilt, on_engine=keep, full=args.full)
         except BaseException as exc:  # noqa: BLE001 - reported by the main thread
             errors[rank] = exc
             ctl.abort()
@@ -741,6 +759,23 @@ def run_ranks_in_process(args, devices, xchg):
     return records
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, m):
+    """What the headline's last timed call (HipEngine.solve -> cba_solve) hands its caller, its TrfResult, as ``directory/<name>.npy`` in float64:
+    the solution x and the scalars that come with it.  The scene is generated from a fixed seed, so two builds run with the same arguments
+    can be compared array for array."""
+    last = m["last"]
+    arrays = {"x": m["x_last"], "cost": [last.cost], "optimality": [last.optimality], "nfev": [last.nfev], "njev": [last.njev], "status": [last.status]}
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES  # (cfg5's x, the largest, is 24 MB)
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+
+
 def _source_digest():
     from caliscope_amd.build import source_digest
 
@@ -764,6 +799,42 @@ def main(argv=None):
     return line
 
 
+def _full_extras(args, m, out, rank, world, local_rank):
+    """--full: the figures beyond the headline, added to its line `out`: communication time, warm set-up, the full solve's accuracy, the roofline,
+    the scipy baseline with its parity legs, and the `--also` workloads."""
+    comm = m["timers"].get("exchange") if m["timers"] else None
+    out.update({
+        # device time of the all-reduces per step (HIP events around every exchange on rank 0's stream, instrumented repeat); None on one GPU
+        "comm_ms_per_step": round(comm[0] / max(m["steps"], 1), 4) if comm and comm[1] else None,
+        "setup_ms_warm": None if m["setup_warm_s"] != m["setup_warm_s"] else round(m["setup_warm_s"] * 1e3, 1),  # cba_create again in the warm process (median of 3)
+        "final_rms_px": round(m["final_rms_px"], 6),
+        "initial_rms_px": round(m["initial_rms_px"], 4),
+        "solve": {"nfev": m["full_nfev"], "njev": m["full_njev"], "accepted_steps": m["full_njev"] - 1,
+                  "rejected_trials": m["full_nfev"] - m["full_njev"], "status": m["full_status"], "cost": m["full_cost"]},
+        "roofline": roofline_from(m),
+    })
+    if not args.no_cpu and rank == 0 and world == 1:
+        try:
+            out["cpu_baseline"], out["parity"] = cpu_baseline(m, device_id=local_rank)
+        except Exception as exc:  # the baseline must never break the bench line
+            out["cpu_baseline"] = {"value": None, "unit": "obs/s", "cores": 1, "kind": "port", "sample": f"failed: {exc!r}"}
+    also = {}
+    if rank == 0 and world == 1 and args.also:
+        for name in [s for s in args.also.split(",") if s and s != args.workload]:
+            try:
+                a = measure(name, args.steps, args.warmup, device_id=local_rank, solve_kw={}, count="accepted",  # K ACCEPTED steps each
+                            with_first_call=not args.no_first_call)
+                also[name] = _also_block(a, name)
+                if name == "cfg5" and not args.no_cpu:
+                    also[name]["parity"] = cfg5_sample_parity(device_id=local_rank, n_points=args.cfg5_sample_points)
+                if name == "cfg3" and not args.no_cpu:
+                    also[name]["parity"] = cfg3_tight_parity(device_id=local_rank)
+            except Exception as exc:
+                also.setdefault(name, {})["error"] = repr(exc)
+    if also:
+        out["also"] = also
+
+
 def _run(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -779,7 +850,16 @@ def _run(argv):
     ap.add_argument("--cfg5-sample-points", type=int, default=10_000, help="points of the cfg5-recipe parity sample (10 observations each)")
     ap.add_argument("--xchg", choices=("auto", "rccl", "direct"), default="auto",
                     help="in-process ranks: RCCL communicator (default for distinct devices) or the library's peer-to-peer device group")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the instrumented repeat (roofline, per-kernel times), the full solve (RMS, solve), the first-call and "
+                         "warm set-up figures, the scipy baseline and parity legs, and the --also workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (x, cost, optimality, nfev, njev, status) as DIR/<name>.npy, float64; one GPU")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs is not None and args.gpus != 1:
+        raise SystemExit("--dump-outputs needs --gpus 1 (a rank holds only its shard of the points)")
 
     launched = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     rank = int(os.environ.get("RANK", "0")) if launched else 0
@@ -825,14 +905,15 @@ def _run(argv):
         exchange_backend = xchg
     else:
         m = measure(args.workload, args.steps, args.warmup, device_id=local_rank, control=control, scaling=args.scaling,
-                    with_first_call=not args.no_first_call)
+                    with_first_call=not args.no_first_call, full=args.full, keep_x=args.dump_outputs is not None)
         exchange_backend = "rccl" if world > 1 else None
         if world > 1:
             route = f"{world} processes (launcher), one per GPU, exchange: RCCL communicator"
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, m)
     total_obs = m["n_obs_total"]
     value = total_obs * m["steps"] / m["elapsed"]
     obs_per_rank = [r["n_obs"] for r in per_rank] if per_rank else [m["n_obs"]]
-    comm = m["timers"].get("exchange") if m["timers"] else None
     out = {
         "metric": "observations/sec per LM iteration",
         "value": round(value, 1),
@@ -856,41 +937,15 @@ def _run(argv):
             "sums": "fixed order (CBA_DETERMINISTIC=1: bit-identical from run to run)" if m.get("deterministic") else "FP64 atomics (default)",
         },
         "rccl_ranks": world if exchange_backend == "rccl" else 0,
-        # device time of the all-reduces per step (HIP events around every exchange on rank 0's stream, instrumented repeat); None on one GPU
-        "comm_ms_per_step": round(comm[0] / max(m["steps"], 1), 4) if comm and comm[1] else None,
         "setup_ms": round(m["setup_s"] * 1e3, 1),  # cba_create for this workload (sort, first Schur plan, upload): once per problem structure, not in `value`
-        "setup_ms_warm": None if m["setup_warm_s"] != m["setup_warm_s"] else round(m["setup_warm_s"] * 1e3, 1),  # ... built again in the warm process (median of 3)
         "plan_wait_ms": round(m["plan_wait_s"] * 1e3, 1),  # ... and how much longer the balanced plan took (a solve would have started meanwhile)
-        "final_rms_px": round(m["final_rms_px"], 6),
-        "initial_rms_px": round(m["initial_rms_px"], 4),
         # accepted iterations re-linearise (njev - 1 of them after x0); the other trial points were rejected
         "timed_region": step_mix(m),
-        "solve": {"nfev": m["full_nfev"], "njev": m["full_njev"], "accepted_steps": m["full_njev"] - 1,
-                  "rejected_trials": m["full_nfev"] - m["full_njev"], "status": m["full_status"], "cost": m["full_cost"]},
-        "roofline": roofline_from(m),
         "engine": m["info"],
         "library_source_sha256": _source_digest(),  # the code this line was measured on (profiles/parity_r*.json carries the same field)
     }
-    if not args.no_cpu and rank == 0 and world == 1:
-        try:
-            out["cpu_baseline"], out["parity"] = cpu_baseline(m, device_id=local_rank)
-        except Exception as exc:  # the baseline must never break the bench line
-            out["cpu_baseline"] = {"value": None, "unit": "obs/s", "cores": 1, "kind": "port", "sample": f"failed: {exc!r}"}
-    also = {}
-    if rank == 0 and world == 1 and args.also:
-        for name in [s for s in args.also.split(",") if s and s != args.workload]:
-            try:
-                a = measure(name, args.steps, args.warmup, device_id=local_rank, solve_kw={}, count="accepted",  # K ACCEPTED steps each
-                            with_first_call=not args.no_first_call)
-                also[name] = _also_block(a, name)
-                if name == "cfg5" and not args.no_cpu:
-                    also[name]["parity"] = cfg5_sample_parity(device_id=local_rank, n_points=args.cfg5_sample_points)
-                if name == "cfg3" and not args.no_cpu:
-                    also[name]["parity"] = cfg3_tight_parity(device_id=local_rank)
-            except Exception as exc:
-                also.setdefault(name, {})["error"] = repr(exc)
-    if also:
-        out["also"] = also
+    if args.full:
+        _full_extras(args, m, out, rank, world, local_rank)
     line = None
     if rank == 0:
         line = json.dumps(out, default=lambda o: int(o) if isinstance(o, np.integer) else float(o))

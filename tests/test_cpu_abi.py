@@ -355,7 +355,7 @@ def test_bench_starts_its_own_ranks_without_a_launcher(cpu_lib):
         import bench
         lines = {}
         for name, argv in (("two", ["--gpus", "2", "--devices", "0,0", "--xchg", "direct"]), ("one", ["--gpus", "1"])):
-            lines[name] = json.loads(bench.main(argv + ["--workload", "tiny", "--steps", "4", "--warmup", "1", "--no-cpu", "--also", ""]))
+            lines[name] = json.loads(bench.main(argv + ["--workload", "tiny", "--steps", "4", "--warmup", "1", "--full", "--no-cpu", "--also", ""]))
         try:
             bench.main(["--gpus", "3", "--workload", "tiny", "--no-cpu", "--also", ""])
             refused = ""
@@ -391,7 +391,7 @@ def test_bench_under_the_launcher_one_process_per_rank(cpu_lib):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "CBA_CONTROL_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           str(ROOT / "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "4", "--warmup", "1", "--no-cpu", "--also", ""]
+           str(ROOT / "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "4", "--warmup", "1", "--full", "--no-cpu", "--also", ""]
     proc = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
@@ -401,6 +401,38 @@ def test_bench_under_the_launcher_one_process_per_rank(cpu_lib):
     assert "2 processes (launcher)" in d["config"]["parallelism"] and d["config"]["n_obs_total"] == 450
     assert abs(d["value"] - 450 / (d["ms_per_step"] * 1e-3)) < 1e-2 * d["value"]
     assert d["solve"]["status"] > 0 and abs(d["final_rms_px"] - 0.5) < 0.5  # converged on the sharded problem (the single-rank figure: the test above)
-    single = json.loads(subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "4", "--warmup", "1", "--no-cpu",
-                                        "--also", ""], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300, check=True).stdout.strip().splitlines()[-1])
+    single = json.loads(subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "4", "--warmup", "1", "--full",
+                                        "--no-cpu", "--also", ""], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300, check=True).stdout.strip().splitlines()[-1])
     assert abs(d["final_rms_px"] - single["final_rms_px"]) < 1e-6 and d["solve"]["nfev"] == single["solve"]["nfev"]
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_what_they_returned(cpu_lib, tmp_path):
+    """`bench.py --steps K --dump-outputs DIR` without --full: exactly K timed trial points, the contract keys and none of --full's figures; DIR holds
+    the last timed solve's x and scalars in float64, the same arrays from run to run, and the cost it reports is the oracle's cost at that x."""
+    out = _run(cpu_lib, f"""
+        import json
+        import numpy as np
+        import bench
+        from oracle.residuals import joint_residuals
+        names = ("x", "cost", "optimality", "nfev", "njev", "status")
+        lines, dumps = [], []
+        for run in ("a", "b"):
+            lines.append(json.loads(bench.main(["--workload", "tiny", "--steps", "3", "--warmup", "1", "--dump-outputs", r"{tmp_path}/" + run])))
+            dumps.append({{n: np.load(r"{tmp_path}/" + run + "/" + n + ".npy") for n in names}})
+        sc, par, x0, prob, _ = bench.build_problem("tiny")
+        d = dumps[0]
+        f = joint_residuals(d["x"], par, sc.camera_indices, sc.image_coords, sc.obj_indices)
+        f0 = joint_residuals(x0, par, sc.camera_indices, sc.image_coords, sc.obj_indices)
+        print(json.dumps(dict(line=lines[0], same=all(np.array_equal(dumps[0][n], dumps[1][n]) for n in names),
+                              dtypes=sorted({{str(a.dtype) for a in d.values()}}), shape=list(d["x"].shape), n_params=int(prob.n_params),
+                              cost=float(d["cost"][0]), cost_oracle=0.5 * float(f @ f), cost0=0.5 * float(f0 @ f0), status=float(d["status"][0]))))
+    """)
+    line = out["line"]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "timed_region"):
+        assert key in line, key
+    for key in ("roofline", "cpu_baseline", "parity", "also", "final_rms_px", "solve", "setup_ms_warm"):
+        assert key not in line, key
+    assert line["steps"] == 3 and line["timed_region"]["trial_points"] == 3 and line["metric"] == "observations/sec per LM iteration"
+    assert abs(line["value"] - 450 / (line["ms_per_step"] * 1e-3)) < 1e-2 * line["value"]
+    assert out["same"] is True and out["dtypes"] == ["float64"] and out["shape"] == [out["n_params"]]
+    assert abs(out["cost"] - out["cost_oracle"]) <= 1e-10 * out["cost_oracle"] and out["cost"] < out["cost0"] and out["status"] >= 0

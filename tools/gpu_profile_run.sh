@@ -11,21 +11,21 @@ export TMPDIR=/tmp PYTHONUNBUFFERED=1 CBA_GROUP_TIMEOUT_S=30
 O=$GRAFT_REPO_ROOT/gpurun_out/profile_run; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -x -q --timeout=400 > $O/tests.log 2>&1; echo "rc=$?" >> $O/tests.log; tail -4 $O/tests.log
 timeout 120 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-( time timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time; tail -3 $O/bench.time; tail -c 300 $O/bench.json; echo
+( time timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time; tail -3 $O/bench.time; tail -c 300 $O/bench.json; echo
 # (parity_at_size right behind the bench line: the two carry the library digest that tests/test_bench_contract.py compares; a run cut short loses the tail, not these)
 [ "$1" = quick ] || ( time timeout 1500 python tools/parity_at_size.py $O/parity.json > $O/parity.log 2>&1 ) 2> $O/parity.time
 tail -3 $O/parity.time 2>/dev/null
 cd /tmp
 B=$GRAFT_REPO_ROOT/bench.py
-timeout 200 rocprofv3 --kernel-trace --stats -d $O/trace_cfg4 -o t -- python $B --no-cpu --no-first-call --also "" --steps 20 --warmup 4 > $O/bench_cfg4.json 2> $O/trace_cfg4.err
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_cfg5 -o t -- python $B --no-cpu --no-first-call --workload cfg5 --also "" --steps 8 --warmup 2 > $O/bench_cfg5.json 2> $O/trace_cfg5.err
-timeout 200 rocprofv3 --kernel-trace --stats -d $O/trace_cfg23 -o t -- python $B --no-cpu --workload cfg2 --also cfg3 --steps 40 --warmup 8 > $O/bench_cfg23.json 2> $O/trace_cfg23.err
+timeout 200 rocprofv3 --kernel-trace --stats -d $O/trace_cfg4 -o t -- python $B --full --no-cpu --no-first-call --also "" --steps 20 --warmup 4 > $O/bench_cfg4.json 2> $O/trace_cfg4.err
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_cfg5 -o t -- python $B --full --no-cpu --no-first-call --workload cfg5 --also "" --steps 8 --warmup 2 > $O/bench_cfg5.json 2> $O/trace_cfg5.err
+timeout 200 rocprofv3 --kernel-trace --stats -d $O/trace_cfg23 -o t -- python $B --full --no-cpu --workload cfg2 --also cfg3 --steps 40 --warmup 8 > $O/bench_cfg23.json 2> $O/trace_cfg23.err
 for w in cfg4 cfg5; do
   st=12; [ $w = cfg5 ] && st=6
-  timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch_$w -o p --output-format csv -- python $B --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 2 > /dev/null 2>&1
-  timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write_$w -o p --output-format csv -- python $B --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 2 > /dev/null 2>&1
-  timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS -d $O/sqA_$w -o p --output-format csv -- python $B --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 2 > /dev/null 2>&1
-  timeout 300 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM -d $O/sqB_$w -o p --output-format csv -- python $B --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 2 > /dev/null 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch_$w -o p --output-format csv -- python $B --full --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 2 > /dev/null 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write_$w -o p --output-format csv -- python $B --full --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 2 > /dev/null 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS -d $O/sqA_$w -o p --output-format csv -- python $B --full --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 2 > /dev/null 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM -d $O/sqB_$w -o p --output-format csv -- python $B --full --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 2 > /dev/null 2>&1
 done
 cd $GRAFT_REPO_ROOT
 for w in cfg4 cfg5 cfg23; do DB=$(find $O/trace_$w -name "*.db" | head -1); [ -n "$DB" ] && python tools/rocpd_stats.py $DB $O/${w}_kernel_trace.md > /dev/null; done
@@ -40,7 +40,7 @@ find $O -name "*.db" -size +8M -delete; find $O -name "*kernel_trace.csv" -size 
 P=$GRAFT_REPO_ROOT/caliscope_amd/libcaliscope_ba_prof.so
 # device-side stamps of one fused iteration (round 6: what sits between the kernels without a profiler attached; per-tile / XCD / dispatch-order lifetimes of the pair kernel)
 for w in cfg2 cfg3 cfg4 cfg5; do
-  CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps 12 --warmup 4 > /dev/null 2> $O/stamps_$w.raw
+  CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps 12 --warmup 4 > /dev/null 2> $O/stamps_$w.raw
   awk '/device stamps of the last fused iteration/{n++} n==1' $O/stamps_$w.raw > $O/stamps_$w.txt
 done
 CALISCOPE_BA_LIB=$P CBA_SCHUR_CLOCK=1 timeout 120 python tools/newton_probe.py cfg4 1 2> $O/schur_clock_cfg4.log > /dev/null
@@ -53,8 +53,8 @@ timeout 200 python tools/end_to_end.py cfg4 > $O/end_to_end_cfg4.log 2>&1
 timeout 400 python tools/large_size_probe.py > $O/large_size_probe.log 2>&1
 for w in 2 8; do
   devs=$(python -c "print(','.join(['0']*$w))")
-  timeout 400 python bench.py --gpus $w --devices $devs --xchg direct --no-cpu --also "" --steps 20 --warmup 4 > $O/ranks${w}_cfg4.json 2> $O/ranks${w}_cfg4.err
-  timeout 700 python bench.py --gpus $w --devices $devs --xchg direct --no-cpu --workload cfg5 --also "" --steps 8 --warmup 2 > $O/ranks${w}_cfg5.json 2> $O/ranks${w}_cfg5.err
+  timeout 400 python bench.py --full --gpus $w --devices $devs --xchg direct --no-cpu --also "" --steps 20 --warmup 4 > $O/ranks${w}_cfg4.json 2> $O/ranks${w}_cfg4.err
+  timeout 700 python bench.py --full --gpus $w --devices $devs --xchg direct --no-cpu --workload cfg5 --also "" --steps 8 --warmup 2 > $O/ranks${w}_cfg5.json 2> $O/ranks${w}_cfg5.err
 done
 timeout 300 python tools/shard_projection.py cfg4 > $O/shard_projection_cfg4.log 2>&1
 timeout 600 python tools/shard_projection.py cfg5 > $O/shard_projection_cfg5.log 2>&1

@@ -22,7 +22,7 @@ cfg5_full_linear_algebra   FULL cfg5 (10M observations) through size-independent
                 observations at a time: residual rows, cost, gradient J^T f and Jacobi scale of the device against the oracle's, and the device's damped
                 step s put into the oracle's normal equations: ||(J^T J + lam D^2) s + g||_inf / ||g||_inf (the whole Schur route — records, pair
                 products, dense solve, back-substitution — checked without a second solver; --skip-cfg5-full leaves it out)
-(full cfg4 is compared in every bench.py run: ``parity`` in its JSON line)
+(full cfg4 is compared in every bench.py --full run: ``parity`` in its JSON line)
 """
 import json
 import os

@@ -10,12 +10,12 @@ for w in cfg4 cfg5 cfg2; do
   for v in "0 2" "1 2" "1 3"; do
     set -- $v
     echo "== $w CBA_BACKSUB_REC=$1 CBA_BACKSUB_WGS=$2"
-    CBA_BACKSUB_REC=$1 CBA_BACKSUB_WGS=$2 timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_${w}_$1_$2.err | python -c "$pick"
+    CBA_BACKSUB_REC=$1 CBA_BACKSUB_WGS=$2 timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_${w}_$1_$2.err | python -c "$pick"
   done
 done > $O/ab.txt 2>&1
 cat $O/ab.txt
 P=$GRAFT_REPO_ROOT/caliscope_amd/libcaliscope_ba_prof.so
 for w in cfg4 cfg2 cfg5; do
-  CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps 12 --warmup 4 > $O/stamps_$w.json 2> $O/stamps_$w.txt
+  CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps 12 --warmup 4 > $O/stamps_$w.json 2> $O/stamps_$w.txt
 done
 grep -A40 "device stamps" $O/stamps_cfg4.txt | head -60

@@ -8,9 +8,9 @@ pick='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); 
 for w in cfg4 cfg5 cfg3; do
 for v in 1 0 1 0; do
   st=20; [ $w = cfg5 ] && st=8
-  echo "== $w CBA_ROT_PRIO=$v"; CBA_ROT_PRIO=$v timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2>/dev/null | python -c "$pick"
+  echo "== $w CBA_ROT_PRIO=$v"; CBA_ROT_PRIO=$v timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2>/dev/null | python -c "$pick"
 done; done
 for v in 1 0; do
-  CBA_ROT_PRIO=$v CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --no-cpu --no-first-call --workload cfg4 --also "" --steps 12 --warmup 4 > /dev/null 2> $O/stamps_$v.txt
+  CBA_ROT_PRIO=$v CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --full --no-cpu --no-first-call --workload cfg4 --also "" --steps 12 --warmup 4 > /dev/null 2> $O/stamps_$v.txt
   echo "== stamps CBA_ROT_PRIO=$v"; grep -A26 "k_tprep | " $O/stamps_$v.txt | head -27 | grep -v chol_step
 done

@@ -9,13 +9,13 @@ for nb in 64 32 64 32; do
 for w in cfg4 cfg5 cfg3; do
   st=20; [ $w = cfg5 ] && st=8
   echo "== $w NB=$nb"
-  CBA_CHOL_NB=$nb timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_${w}_$nb.err | tee $O/bench_${w}_$nb.json | python -c "$pick"
+  CBA_CHOL_NB=$nb timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_${w}_$nb.err | tee $O/bench_${w}_$nb.json | python -c "$pick"
 done
 done > $O/ab.txt 2>&1
 cat $O/ab.txt
 P=$GRAFT_REPO_ROOT/caliscope_amd/libcaliscope_ba_prof.so
 for w in cfg4 cfg5; do
-CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps 12 --warmup 4 > $O/stamps_$w.json 2> $O/stamps_$w.txt
+CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps 12 --warmup 4 > $O/stamps_$w.json 2> $O/stamps_$w.txt
 grep -A40 "k_tprep | " $O/stamps_$w.txt | head -34
 done
 CALISCOPE_BA_LIB=$P CBA_CHOL_TRACE=1 timeout 200 python tools/chol_trace.py > $O/chol_trace.txt 2>&1; head -20 $O/chol_trace.txt

@@ -8,7 +8,7 @@ for w in cfg5 cfg4; do
 for rg in 32 8 16 64 128 32; do
   st=20; [ $w = cfg5 ] && st=8
   echo "== $w region $rg"
-  CBA_PLAN_REGION=$rg CBA_PLAN_TIMING=1 timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_${w}_$rg.err | tee $O/bench_${w}_$rg.json | python -c "$pick"
+  CBA_PLAN_REGION=$rg CBA_PLAN_TIMING=1 timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_${w}_$rg.err | tee $O/bench_${w}_$rg.json | python -c "$pick"
   grep "lane utilisation" $O/bench_${w}_$rg.err | tail -1
 done
 done > $O/ab.txt 2>&1

@@ -10,13 +10,13 @@ for f in 1 0; do
   for w in cfg4 cfg3 cfg5; do
   st=20; [ $w = cfg5 ] && st=8
   echo "== $w fused=$f"
-  CBA_REG_FINALIZE=$f timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_${w}_$f.err | tee $O/bench_${w}_$f.json | python -c "$pick"
+  CBA_REG_FINALIZE=$f timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_${w}_$f.err | tee $O/bench_${w}_$f.json | python -c "$pick"
   done
 done
 done > $O/ab.txt 2>&1
 cat $O/ab.txt
 P=$GRAFT_REPO_ROOT/caliscope_amd/libcaliscope_ba_prof.so
 for w in cfg4 cfg5; do
-CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps 12 --warmup 4 > $O/stamps_$w.json 2> $O/stamps_$w.txt
+CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps 12 --warmup 4 > $O/stamps_$w.json 2> $O/stamps_$w.txt
 grep -A8 "k_tprep | " $O/stamps_$w.txt | head -9
 done

@@ -13,7 +13,7 @@ for lib in new old; do
   [ $w = cfg5 ] && [ $rep != 1 ] && continue
   echo "== $w $lib"
   if [ $lib = old ]; then export CALISCOPE_BA_LIB=$OLD; else unset CALISCOPE_BA_LIB; fi
-  timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_${w}_$lib.err | tee $O/bench_${w}_$lib.json | python -c "$pick"
+  timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_${w}_$lib.err | tee $O/bench_${w}_$lib.json | python -c "$pick"
   done
 done
 done > $O/ab.txt 2>&1
@@ -21,6 +21,6 @@ unset CALISCOPE_BA_LIB
 cat $O/ab.txt
 P=$GRAFT_REPO_ROOT/caliscope_amd/libcaliscope_ba_prof.so
 for w in cfg4 cfg5; do
-CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps 12 --warmup 4 > $O/stamps_$w.json 2> $O/stamps_$w.txt
+CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps 12 --warmup 4 > $O/stamps_$w.json 2> $O/stamps_$w.txt
 egrep "k_step_cam|k_reduce_rows_pub|kernels," $O/stamps_$w.txt | head -3
 done

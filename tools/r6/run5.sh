@@ -8,11 +8,11 @@ pick='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); 
 for w in cfg4 cfg4 cfg2 cfg5; do
   st=20; [ $w = cfg5 ] && st=8; [ $w = cfg2 ] && st=40
   echo "== $w"
-  timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_$w.err | tee $O/bench_$w.json | python -c "$pick"
+  timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_$w.err | tee $O/bench_$w.json | python -c "$pick"
 done > $O/ab.txt 2>&1
 cat $O/ab.txt
 P=$GRAFT_REPO_ROOT/caliscope_amd/libcaliscope_ba_prof.so
-CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --no-cpu --no-first-call --workload cfg4 --also "" --steps 12 --warmup 4 > $O/stamps_cfg4.json 2> $O/stamps_cfg4.txt
+CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --full --no-cpu --no-first-call --workload cfg4 --also "" --steps 12 --warmup 4 > $O/stamps_cfg4.json 2> $O/stamps_cfg4.txt
 grep -B2 -A30 "k_tprep | " $O/stamps_cfg4.txt | tail -34 | grep -v "chol_step k=[2-9]"
 timeout 200 python tools/real_session_timing.py > $O/real_session.log 2>&1; cat $O/real_session.log
 CBA_SOLVE_TRACE=1 CBA_PLAN_TIMING=1 timeout 200 python tools/real_session_timing.py > $O/real_session_trace.log 2>&1; tail -120 $O/real_session_trace.log

@@ -8,12 +8,12 @@ pick='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); 
 for w in cfg4 cfg4 cfg5 cfg3 cfg2; do
   st=20; [ $w = cfg5 ] && st=8; [ $w = cfg2 ] && st=40
   echo "== $w"
-  timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_$w.err | tee $O/bench_$w.json | python -c "$pick"
+  timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps $st --warmup 4 2> $O/bench_$w.err | tee $O/bench_$w.json | python -c "$pick"
 done > $O/ab.txt 2>&1
 cat $O/ab.txt
 P=$GRAFT_REPO_ROOT/caliscope_amd/libcaliscope_ba_prof.so
 for w in cfg4 cfg5; do
-CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --no-cpu --no-first-call --workload $w --also "" --steps 12 --warmup 4 > $O/stamps_$w.json 2> $O/stamps_$w.txt
+CALISCOPE_BA_LIB=$P CBA_STAMPS=1 CBA_PLAN=full timeout 300 python bench.py --full --no-cpu --no-first-call --workload $w --also "" --steps 12 --warmup 4 > $O/stamps_$w.json 2> $O/stamps_$w.txt
 grep -A3 "k_tprep | " $O/stamps_$w.txt | tail -4
 done
 timeout 200 python tools/real_session_timing.py > $O/real_session.log 2>&1; cat $O/real_session.log
