@@ -1,7 +1,8 @@
 """The solver stages of the reference's extrinsic-calibration use case, on the MI355X engine.
 
-``calibrate_extrinsics`` (reference ``core/calibrate_extrinsics.py:44-261``) is a nine-stage pipeline; stages
-1-3 (blind intrinsics, pairwise PnP / essential-matrix bootstrap) need OpenCV and are upstream of the hot path.
+``calibrate_extrinsics`` (reference ``core/calibrate_extrinsics.py:44-261``) is a nine-stage pipeline; stage 3 (the pose
+bootstrap) runs here for board sessions with ``estimate_poses=True`` (PnP per view on the device,
+``caliscope_amd/pose_network.py``); the essential-matrix bootstrap for sessions without object geometry is not rebuilt.
 Stage 4 (static-marker guard, :146-196) and stages 5-9 — the part that calls the solver three times with a filter in
 between — are mirrored here, on a volume that is already bootstrapped (a dropped marker's rows are removed from
 the volume instead of re-running the bootstrap).  :func:`calibrate_extrinsics` keeps the reference's entry point and its
@@ -166,12 +167,16 @@ def calibrate_extrinsics(
     filter_percentile: float = 2.5,
     cancellation_token=None,
     progress: Callable[[int, str], None] | None = None,
+    estimate_poses: bool = False,
     _engine_factory=None,
     _triangulate=None,
+    _pnp=None,
 ) -> CalibrationRun:
-    """The reference's entry point (``calibrate_extrinsics.py:44-261``, same arguments, progress marks and errors) for
-    cameras that carry pose estimates: blind intrinsics for uncalibrated cameras, the extraction guards, triangulation
-    on the device, static-marker guard, the three solver passes with the filter in between."""
+    """The reference's entry point (``calibrate_extrinsics.py:44-261``, same arguments, progress marks and errors): blind
+    intrinsics for uncalibrated cameras, the extraction guards, the bootstrap (triangulation on the device; with
+    ``estimate_poses=True`` first the pose network from the board views, as the reference always does), static-marker
+    guard, the three solver passes with the filter in between.  ``estimate_poses=False`` needs cameras that carry pose
+    estimates."""
     from copy import deepcopy
 
     from caliscope_amd.exceptions import CalibrationError
@@ -210,7 +215,8 @@ def calibrate_extrinsics(
     check_cancelled()
 
     report(15, "Bootstrapping poses")
-    volume = CaptureVolume.bootstrap(image_points, cameras, constraints=constraints, _triangulate=_triangulate)
+    volume = CaptureVolume.bootstrap(image_points, cameras, constraints=constraints, estimate_poses=estimate_poses, _triangulate=_triangulate,
+                                     _pnp=_pnp)
     if constraints is not None and (constraints.back_face_thickness_m or 0) > 0:
         firing = _count_firing_cross_face_rows(volume.world_points.df, constraints.distances)
         total = sum(1 for d in constraints.distances if d.object_id_a != d.object_id_b)
@@ -233,7 +239,9 @@ def calibrate_extrinsics(
         for cam in cameras.cameras.values():
             if not cam.ignore and cam.cam_id in synthesized:
                 cam.synthesize_default_intrinsics()
-        volume = CaptureVolume.bootstrap(guarded.image_points, cameras, constraints=guarded.constraints, _triangulate=_triangulate)
+        # (with estimate_poses the pose network is rebuilt without the dropped markers' views, as the reference does)
+        volume = CaptureVolume.bootstrap(guarded.image_points, cameras, constraints=guarded.constraints, estimate_poses=estimate_poses,
+                                         _triangulate=_triangulate, _pnp=_pnp)
     check_cancelled()
     run = refine_calibration(volume, refine_intrinsics=refine_intrinsics, filter_percentile=filter_percentile,
                              cancellation_token=cancellation_token, progress=progress, _engine_factory=_engine_factory, _guard=False)

@@ -541,14 +541,18 @@ class CaptureVolume:
         return self._filter_by_reprojection_thresholds(thresholds, min_per_camera, _engine_factory)
 
     @classmethod
-    def bootstrap(cls, image_points: ImagePoints, camera_array: CameraArray, constraints=None, *, _triangulate=None) -> "CaptureVolume":
+    def bootstrap(cls, image_points: ImagePoints, camera_array: CameraArray, constraints=None, *, estimate_poses: bool = False,
+                  _triangulate=None, _pnp=None) -> "CaptureVolume":
         """Starting volume for ``optimize`` from 2-D observations (reference ``:268-320``): copy the cameras, triangulate
         every point seen by two or more posed cameras (on the device), keep the input untouched.
 
-        The reference first estimates the poses from pairwise PnP / essential-matrix decompositions (OpenCV, upstream of
-        the solver path and not rebuilt here): this ``bootstrap`` takes the poses the cameras already carry — a previous
-        calibration, a rig description, another tool's estimate — and raises ``CalibrationError`` for cameras that have
-        observations but no pose.  Validation and errors otherwise follow the reference (``:288-307``)."""
+        ``estimate_poses=False`` (default): the poses the cameras already carry are used — a previous calibration, a rig
+        description, another tool's estimate — and cameras that have observations but no pose raise ``CalibrationError``.
+        ``estimate_poses=True``: the reference's order — copy the cameras, build the pose network from the board views
+        (PnP per view on the device, :mod:`caliscope_amd.pose_network`), ``apply_to`` the copy (any pose a camera carried
+        is replaced), then triangulate.  That needs object geometry (``obj_loc``); sessions without it would need the
+        essential-matrix bootstrap, which this backend does not have.  ``_pnp`` replaces the device calls of the pose
+        network (tests).  Validation and errors otherwise follow the reference (``:288-307``)."""
         point_cams = set(int(c) for c in image_points.df["cam_id"].unique())
         missing = point_cams - set(camera_array.cameras)
         if missing:
@@ -559,15 +563,27 @@ class CaptureVolume:
                 f"Cannot run extrinsic calibration -- cameras {uncalibrated} have no intrinsic calibration.\n\n"
                 f"Run calibrate_intrinsics() for each camera first."
             )
-        unposed = sorted(cid for cid in point_cams
-                         if not camera_array.cameras[cid].ignore
-                         and (camera_array.cameras[cid].rotation is None or camera_array.cameras[cid].translation is None))
-        if unposed:
-            raise CalibrationError(
-                f"Cameras {unposed} have observations but no pose estimate. This backend refines poses; the initial pose "
-                f"network (PnP / essential matrix) is upstream of it: load a previous calibration or supply estimates."
-            )
-        cameras = deepcopy(camera_array)
+        if estimate_poses:
+            from caliscope_amd.pose_network import build_paired_pose_network, has_object_geometry
+
+            if not has_object_geometry(image_points):
+                raise CalibrationError(
+                    "Pose estimation needs object geometry: obj_loc is all NaN in these observations, and the essential-matrix "
+                    "(epipolar) bootstrap for such sessions is not available in this backend. Supply board observations with "
+                    "obj_loc, or cameras that already carry pose estimates."
+                )
+            cameras = deepcopy(camera_array)
+            build_paired_pose_network(image_points, cameras, _pnp=_pnp).apply_to(cameras)
+        else:
+            unposed = sorted(cid for cid in point_cams
+                             if not camera_array.cameras[cid].ignore
+                             and (camera_array.cameras[cid].rotation is None or camera_array.cameras[cid].translation is None))
+            if unposed:
+                raise CalibrationError(
+                    f"Cameras {unposed} have observations but no pose estimate. This backend refines poses; the initial pose "
+                    f"network (PnP / essential matrix) is upstream of it: load a previous calibration or supply estimates."
+                )
+            cameras = deepcopy(camera_array)
         static_ids = constraints.static_object_ids if constraints else frozenset()
         triangulate = _triangulate or (lambda ip, cams, static: ip.triangulate(cams, static_object_ids=static))
         world_points = triangulate(image_points, cameras, static_ids)

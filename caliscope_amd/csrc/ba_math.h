@@ -326,4 +326,96 @@ CBA_HD void chol3_bwd(const double* L, const double* y, double* x) {
   x[0] = (y[0] - L[1] * x[1] - L[3] * x[2]) * L[0];
 }
 
+// Undistortion of one pixel observation to normalised coordinates (cba_triangulate, cba_pose_pnp_batch).
+// Pinhole: OpenCV's five fixed-point iterations  x <- (x0 - delta(x)) / cdist(x).  Fisheye: Newton on
+// theta_d = theta (1 + k1 theta^2 + ...), at most 10 steps, stop below 1e-8, theta_d clipped to [-pi/2, pi/2].
+CBA_HD void undistort_one(int model, const double* __restrict__ in9, double u, double v, int f32, double* xo, double* yo) {
+  if (f32) { u = (double)(float)u; v = (double)(float)v; }
+  const double fx = in9[0], fy = in9[1], cx = in9[2], cy = in9[3];
+  const double x0 = (u - cx) / fx, y0 = (v - cy) / fy;
+  double x = x0, y = y0;
+  if (model == 0) {
+    const double k1 = in9[4], k2 = in9[5], p1 = in9[6], p2 = in9[7], k3 = in9[8];
+    for (int it = 0; it < 5; ++it) {
+      const double r2 = x * x + y * y;
+      const double icd = 1.0 / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2);
+      const double dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
+      const double dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y;
+      x = (x0 - dx) * icd;
+      y = (y0 - dy) * icd;
+    }
+  } else {
+    const double k1 = in9[4], k2 = in9[5], k3 = in9[6], k4 = in9[7];
+    const double hp = 1.5707963267948966;
+    double td = sqrt(x0 * x0 + y0 * y0);
+    td = fmin(fmax(td, -hp), hp);
+    double scale = 1.0;
+    if (td > 1e-8) {
+      double th = td;
+      for (int it = 0; it < 10; ++it) {
+        const double t2 = th * th, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
+        const double fix = (th * (1.0 + k1 * t2 + k2 * t4 + k3 * t6 + k4 * t8) - td) /
+                           (1.0 + 3.0 * k1 * t2 + 5.0 * k2 * t4 + 7.0 * k3 * t6 + 9.0 * k4 * t8);
+        th -= fix;
+        if (fabs(fix) < 1e-8) break;
+      }
+      scale = tan(th) / td;
+    }
+    x = x0 * scale;
+    y = y0 * scale;
+  }
+  if (f32) { x = (double)(float)x; y = (double)(float)y; }
+  *xo = x; *yo = y;
+}
+
+// Null vector of a symmetric 4 x 4 (the DLT normal matrix of a triangulation): the eigenvector of the smallest eigenvalue by
+// cyclic Jacobi, at most 12 sweeps.  M is overwritten.
+CBA_HD void sym4_null_vector(double (&M)[4][4], double* w) {
+  // V accumulates the rotations (columns = eigenvectors)
+  double V[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) V[r][c] = (r == c) ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 12; ++sweep) {
+    double off = 0.0;
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int r = p + 1; r < 4; ++r) off += M[p][r] * M[p][r];
+    const double diag = M[0][0] * M[0][0] + M[1][1] * M[1][1] + M[2][2] * M[2][2] + M[3][3] * M[3][3];
+    if (off <= 1e-34 * diag) break;
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int r = p + 1; r < 4; ++r) {
+        const double apq = M[p][r];
+        if (apq != 0.0) {
+          const double theta = (M[r][r] - M[p][p]) / (2.0 * apq);
+          const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+          const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {  // columns p, r of M and V
+            const double mkp = M[k][p], mkr = M[k][r];
+            M[k][p] = c * mkp - s * mkr; M[k][r] = s * mkp + c * mkr;
+            const double vkp = V[k][p], vkr = V[k][r];
+            V[k][p] = c * vkp - s * vkr; V[k][r] = s * vkp + c * vkr;
+          }
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {  // rows p, r of M
+            const double mpk = M[p][k], mrk = M[r][k];
+            M[p][k] = c * mpk - s * mrk; M[r][k] = s * mpk + c * mrk;
+          }
+        }
+      }
+  }
+  int best = 0;
+  double smallest = M[0][0];  // (kept beside `best`: M[best][best] is a dynamic index and sent the whole matrix to scratch)
+#pragma unroll
+  for (int k = 1; k < 4; ++k)
+    if (M[k][k] < smallest) { smallest = M[k][k]; best = k; }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) w[k] = (best == 0) ? V[k][0] : (best == 1) ? V[k][1] : (best == 2) ? V[k][2] : V[k][3];
+}
+
 }  // namespace cba
