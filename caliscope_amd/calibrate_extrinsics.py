@@ -1,8 +1,9 @@
 """The solver stages of the reference's extrinsic-calibration use case, on the MI355X engine.
 
 ``calibrate_extrinsics`` (reference ``core/calibrate_extrinsics.py:44-261``) is a nine-stage pipeline; stage 3 (the pose
-bootstrap) runs here for board sessions with ``estimate_poses=True`` (PnP per view on the device,
-``caliscope_amd/pose_network.py``); the essential-matrix bootstrap for sessions without object geometry is not rebuilt.
+bootstrap) runs here with ``estimate_poses``: ``True`` for board sessions (PnP per view on the device,
+``caliscope_amd/pose_network.py``), ``"epipolar"`` / ``"auto"`` for sessions without object geometry (essential-matrix RANSAC on
+the device, ``caliscope_amd/epipolar_pose.py``).
 Stage 4 (static-marker guard, :146-196) and stages 5-9 — the part that calls the solver three times with a filter in
 between — are mirrored here, on a volume that is already bootstrapped (a dropped marker's rows are removed from
 the volume instead of re-running the bootstrap).  :func:`calibrate_extrinsics` keeps the reference's entry point and its
@@ -30,7 +31,7 @@ from typing import Callable
 import numpy as np
 
 from caliscope_amd.bundle_parameterization import IntrinsicEstimate
-from caliscope_amd.capture_volume import CaptureVolume
+from caliscope_amd.capture_volume import CaptureVolume, pose_method
 from caliscope_amd.point_data import STATIC_SYNC_INDEX
 
 logger = logging.getLogger(__name__)
@@ -167,16 +168,17 @@ def calibrate_extrinsics(
     filter_percentile: float = 2.5,
     cancellation_token=None,
     progress: Callable[[int, str], None] | None = None,
-    estimate_poses: bool = False,
+    estimate_poses: bool | str = False,
     _engine_factory=None,
     _triangulate=None,
     _pnp=None,
+    _epi=None,
 ) -> CalibrationRun:
     """The reference's entry point (``calibrate_extrinsics.py:44-261``, same arguments, progress marks and errors): blind
     intrinsics for uncalibrated cameras, the extraction guards, the bootstrap (triangulation on the device; with
-    ``estimate_poses=True`` first the pose network from the board views, as the reference always does), static-marker
-    guard, the three solver passes with the filter in between.  ``estimate_poses=False`` needs cameras that carry pose
-    estimates."""
+    ``estimate_poses=True`` first the pose network from the board views, as the reference always does; ``"epipolar"`` / ``"auto"``
+    as ``CaptureVolume.bootstrap`` takes them), static-marker guard, the three solver passes with the filter in between.
+    ``estimate_poses=False`` needs cameras that carry pose estimates."""
     from copy import deepcopy
 
     from caliscope_amd.exceptions import CalibrationError
@@ -197,7 +199,10 @@ def calibrate_extrinsics(
             synthesized.add(cam.cam_id)
             cam.synthesize_default_intrinsics()
     df = image_points.df
-    if synthesized and df[["obj_loc_x", "obj_loc_y", "obj_loc_z"]].isna().all().all():
+    method = pose_method(estimate_poses)
+    no_geometry = bool(df[["obj_loc_x", "obj_loc_y", "obj_loc_z"]].isna().all().all())
+    # the essential-matrix path has no obj_loc anchor to absorb a focal-length error: gate on the path that will run
+    if synthesized and (no_geometry or method == "epipolar"):
         raise CalibrationError(
             f"Epipolar bootstrap requires calibrated intrinsics, but cameras {sorted(synthesized)} have none and fell back to "
             f"blind defaults (f=width/2). Without object geometry there is no anchor to absorb the focal-length error: "
@@ -216,7 +221,7 @@ def calibrate_extrinsics(
 
     report(15, "Bootstrapping poses")
     volume = CaptureVolume.bootstrap(image_points, cameras, constraints=constraints, estimate_poses=estimate_poses, _triangulate=_triangulate,
-                                     _pnp=_pnp)
+                                     _pnp=_pnp, _epi=_epi)
     if constraints is not None and (constraints.back_face_thickness_m or 0) > 0:
         firing = _count_firing_cross_face_rows(volume.world_points.df, constraints.distances)
         total = sum(1 for d in constraints.distances if d.object_id_a != d.object_id_b)
@@ -241,7 +246,7 @@ def calibrate_extrinsics(
                 cam.synthesize_default_intrinsics()
         # (with estimate_poses the pose network is rebuilt without the dropped markers' views, as the reference does)
         volume = CaptureVolume.bootstrap(guarded.image_points, cameras, constraints=guarded.constraints, estimate_poses=estimate_poses,
-                                         _triangulate=_triangulate, _pnp=_pnp)
+                                         _triangulate=_triangulate, _pnp=_pnp, _epi=_epi)
     check_cancelled()
     run = refine_calibration(volume, refine_intrinsics=refine_intrinsics, filter_percentile=filter_percentile,
                              cancellation_token=cancellation_token, progress=progress, _engine_factory=_engine_factory, _guard=False)

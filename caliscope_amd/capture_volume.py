@@ -83,6 +83,16 @@ class ReprojectionReport:
     n_points: int
 
 
+def pose_method(estimate_poses) -> str | None:
+    """The pose-network method an ``estimate_poses`` value asks for: None (no estimation) for a false bool or None, "pnp" for a
+    true bool (builtin or numpy), else the string itself if it is "pnp", "epipolar" or "auto"; anything else is ``ValueError``."""
+    if estimate_poses is None or isinstance(estimate_poses, (bool, np.bool_)):
+        return "pnp" if estimate_poses else None
+    if isinstance(estimate_poses, str) and estimate_poses in ("pnp", "epipolar", "auto"):
+        return estimate_poses
+    raise ValueError(f"estimate_poses must be a bool, 'pnp', 'epipolar' or 'auto', got {estimate_poses!r}")
+
+
 @dataclass(frozen=True)
 class CaptureVolume:
     camera_array: CameraArray
@@ -541,8 +551,8 @@ class CaptureVolume:
         return self._filter_by_reprojection_thresholds(thresholds, min_per_camera, _engine_factory)
 
     @classmethod
-    def bootstrap(cls, image_points: ImagePoints, camera_array: CameraArray, constraints=None, *, estimate_poses: bool = False,
-                  _triangulate=None, _pnp=None) -> "CaptureVolume":
+    def bootstrap(cls, image_points: ImagePoints, camera_array: CameraArray, constraints=None, *, estimate_poses: bool | str = False,
+                  _triangulate=None, _pnp=None, _epi=None) -> "CaptureVolume":
         """Starting volume for ``optimize`` from 2-D observations (reference ``:268-320``): copy the cameras, triangulate
         every point seen by two or more posed cameras (on the device), keep the input untouched.
 
@@ -550,9 +560,13 @@ class CaptureVolume:
         description, another tool's estimate — and cameras that have observations but no pose raise ``CalibrationError``.
         ``estimate_poses=True``: the reference's order — copy the cameras, build the pose network from the board views
         (PnP per view on the device, :mod:`caliscope_amd.pose_network`), ``apply_to`` the copy (any pose a camera carried
-        is replaced), then triangulate.  That needs object geometry (``obj_loc``); sessions without it would need the
-        essential-matrix bootstrap, which this backend does not have.  ``_pnp`` replaces the device calls of the pose
-        network (tests).  Validation and errors otherwise follow the reference (``:288-307``)."""
+        is replaced), then triangulate.  That needs object geometry (``obj_loc``).  ``estimate_poses="pnp"`` is the same.
+        ``estimate_poses="epipolar"``: the pose network from 2-D correspondences alone (essential-matrix RANSAC per camera
+        pair and resection against a scaffold cloud on the device, :mod:`caliscope_amd.epipolar_pose`; ``obj_loc`` is not
+        read).  ``estimate_poses="auto"``: the reference's branching, PnP with object geometry and epipolar without.  Any
+        other value raises ``ValueError``.  ``_pnp`` / ``_epi`` replace the device calls of the pose network (tests).
+        Validation and errors otherwise follow the reference (``:288-307``)."""
+        method = pose_method(estimate_poses)
         point_cams = set(int(c) for c in image_points.df["cam_id"].unique())
         missing = point_cams - set(camera_array.cameras)
         if missing:
@@ -563,17 +577,17 @@ class CaptureVolume:
                 f"Cannot run extrinsic calibration -- cameras {uncalibrated} have no intrinsic calibration.\n\n"
                 f"Run calibrate_intrinsics() for each camera first."
             )
-        if estimate_poses:
+        if method is not None:
             from caliscope_amd.pose_network import build_paired_pose_network, has_object_geometry
 
-            if not has_object_geometry(image_points):
+            if method == "pnp" and not has_object_geometry(image_points):
                 raise CalibrationError(
-                    "Pose estimation needs object geometry: obj_loc is all NaN in these observations, and the essential-matrix "
-                    "(epipolar) bootstrap for such sessions is not available in this backend. Supply board observations with "
-                    "obj_loc, or cameras that already carry pose estimates."
+                    "PnP pose estimation needs object geometry: obj_loc is all NaN in these observations. Use "
+                    "estimate_poses='epipolar' or 'auto' for the essential-matrix (epipolar) bootstrap, supply board observations "
+                    "with obj_loc, or cameras that already carry pose estimates."
                 )
             cameras = deepcopy(camera_array)
-            build_paired_pose_network(image_points, cameras, _pnp=_pnp).apply_to(cameras)
+            build_paired_pose_network(image_points, cameras, method=method, _pnp=_pnp, _epi=_epi).apply_to(cameras)
         else:
             unposed = sorted(cid for cid in point_cams
                              if not camera_array.cameras[cid].ignore

@@ -362,6 +362,8 @@ CBA_HD double det3(const double* M) {
   return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
 }
 
+CBA_HD bool pnp_dlt_finish(double* A, double* p, double s_o, double* R, double* t);
+
 // Non-planar initial pose by DLT (P34 = 1 on the centred, scaled object points); false when degenerate.
 CBA_HD bool pnp_dlt_init(const double* obj, const double* uv, int n, int f32, const double* cen, double s_o, double* R, double* t) {
   double A[66], p[11];
@@ -379,6 +381,13 @@ CBA_HD bool pnp_dlt_init(const double* obj, const double* uv, int n, int f32, co
     normal_add<11>(A, p, ru, u[0]);
     normal_add<11>(A, p, rv, u[1]);
   }
+  return pnp_dlt_finish(A, p, s_o, R, t);
+}
+
+// The rest of pnp_dlt_init from its accumulated 11 x 11 normal equations (packed lower A, right-hand side p; both overwritten):
+// solve, project the 3 x 3 block onto SO(3), t = p4 / scale.  Also the last step of a resection hypothesis (epipolar_math.h).
+CBA_HD bool pnp_dlt_finish(double* A, double* p, double s_o, double* R, double* t) {
+  const double io = 1.0 / s_o;
   if (!chol_solve<11>(A, p)) return false;
   double M[9] = {p[0] * io, p[1] * io, p[2] * io, p[4] * io, p[5] * io, p[6] * io, p[8] * io, p[9] * io, p[10] * io};
   double p4[3] = {p[3], p[7], 1.0};
@@ -499,10 +508,26 @@ CBA_HD int pnp_view(const double* obj, const double* uv, int n, int min_points, 
   return PNP_OK;
 }
 
+CBA_HD void two_view_dlt(const double* rt, double xa, double ya, double xb, double yb, double* w);
+
 // Squared two-view reprojection error of one common observation: DLT with camera A at [I | 0] and B at [R | t] (rt: R
 // row-major, then t), the null vector of the 4 x 4 normal matrix as cba_triangulate forms it, then reprojection into both.
 // Returns |a - proj_A(X)|^2 + |b - proj_B(X)|^2.
 CBA_HD double pair_obs_sq(const double* rt, double xa, double ya, double xb, double yb) {
+  double w[4];
+  two_view_dlt(rt, xa, ya, xb, yb, w);
+  const double X = w[0] / w[3], Y = w[1] / w[3], Z = w[2] / w[3];
+  const double ex = xa - X / Z, ey = ya - Y / Z;
+  const double bx = rt[0] * X + rt[1] * Y + rt[2] * Z + rt[9];
+  const double by = rt[3] * X + rt[4] * Y + rt[5] * Z + rt[10];
+  const double bz = rt[6] * X + rt[7] * Y + rt[8] * Z + rt[11];
+  const double fx = xb - bx / bz, fy = yb - by / bz;
+  return ex * ex + ey * ey + fx * fx + fy * fy;
+}
+
+// The homogeneous two-view DLT point of one correspondence (A at [I | 0], B at [R | t]): the null vector w[4] of the 4 x 4
+// normal matrix, as cba_triangulate forms it (pair_obs_sq; the cheirality test and the scaffold cloud of epipolar_math.h).
+CBA_HD void two_view_dlt(const double* rt, double xa, double ya, double xb, double yb, double* w) {
   double M[4][4];
   const double ra0[4] = {-1.0, 0.0, xa, 0.0}, ra1[4] = {0.0, -1.0, ya, 0.0};
   double rb0[4], rb1[4];
@@ -520,15 +545,7 @@ CBA_HD double pair_obs_sq(const double* rt, double xa, double ya, double xb, dou
   for (int r = 1; r < 4; ++r)
 #pragma unroll
     for (int c = 0; c < r; ++c) M[r][c] = M[c][r];
-  double w[4];
   sym4_null_vector(M, w);
-  const double X = w[0] / w[3], Y = w[1] / w[3], Z = w[2] / w[3];
-  const double ex = xa - X / Z, ey = ya - Y / Z;
-  const double bx = rt[0] * X + rt[1] * Y + rt[2] * Z + rt[9];
-  const double by = rt[3] * X + rt[4] * Y + rt[5] * Z + rt[10];
-  const double bz = rt[6] * X + rt[7] * Y + rt[8] * Z + rt[11];
-  const double fx = xb - bx / bz, fy = yb - by / bz;
-  return ex * ex + ey * ey + fx * fx + fy * fy;
 }
 
 }  // namespace cba

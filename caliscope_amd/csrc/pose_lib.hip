@@ -10,6 +10,25 @@
 //
 // Both kernels are FP64 VALU with per-thread matrices of at most 66 doubles (the 11 x 11 DLT normal matrix), fully
 // unrolled so that they stay in registers: hipcc -Rpass-analysis=kernel-resource-usage reports ScratchSize 0 for both.
+//
+// The epipolar bootstrap (arithmetic: epipolar_math.h) adds two calls of three steps each, RANSAC over many jobs at once:
+//
+//   k_epi_undistort   one thread per observation row: undistort_one once, however many pairs the row belongs to.
+//   k_epi_hyp         one thread per (pair, hypothesis): 8 distinct correspondences from the counter-based sampler, linear
+//   k_res_hyp         8-point E projected onto the manifold (9 doubles) / one thread per (job, hypothesis): 6-point DLT pose
+//                     (12 doubles).  An invalid hypothesis is all zeros / NaN and scores no inlier.
+//   k_score<ESS>      a 2-D grid: x = tiles of SCORE_BLOCK * SCORE_PER_LANE items of one job, y = jobs, so that one large
+//                     pair (the 2-camera case) still fills the chip.  Hypotheses are staged in LDS SCORE_CHUNK at a time;
+//                     each lane tests its items, each wave counts inliers by ballot + popcount and adds them with one
+//                     integer atomic per wave per hypothesis.  Integer sums do not depend on order: counts are deterministic.
+//   k_epi_refine      one REFINE_BLOCK workgroup per pair / job: the winner is the maximum count, the lowest hypothesis
+//   k_res_refine      on ties; then the inlier flags, cheirality (essential), Levenberg-Marquardt whose normal equations
+//                     are summed by a fixed LDS tree (wg_sum: the same order in tests/native/epipolar_harness.cpp), the
+//                     final flags, counts, conditioning, two-view points / reprojection errors.
+//
+// No host synchronisation inside a call beyond the final copy-back.  The workgroup kernels keep one LDS reduction buffer of
+// EPI_LIN_NSUM x REFINE_BLOCK doubles (46 KiB); the largest per-thread matrices are the 9 x 8 Householder factor (k_epi_hyp)
+// and the 11 x 11 DLT normal matrix (k_res_hyp), fully unrolled: ScratchSize 0 for every kernel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,7 +37,7 @@
 #include <vector>
 
 #include "../../include/caliscope_pose.h"
-#include "pnp_math.h"
+#include "epipolar_math.h"
 
 using namespace cba;
 
@@ -77,6 +96,397 @@ k_pose_pair_rmse(const double* __restrict__ pair_pose, const long* __restrict__ 
     const long m = b - a;
     rmse[p] = m > 0 ? sqrt(tot / (2.0 * (double)m)) : 0.0;
     count[p] = m;
+  }
+}
+
+// ---- epipolar bootstrap ------------------------------------------------------------------------------------------------------
+
+constexpr int HYP_BLOCK = 64;
+constexpr int SCORE_BLOCK = 256;
+constexpr int SCORE_PER_LANE = 4;
+constexpr int SCORE_CHUNK = 128;
+constexpr int REFINE_BLOCK = EPI_REDUCE_NT;
+
+__global__ void __launch_bounds__(SCORE_BLOCK)
+k_epi_undistort(long n_obs, const int* __restrict__ obs_cam, const int* __restrict__ cam_model, const double* __restrict__ cam_intr,
+                const double* __restrict__ obs_xy, int f32, double* __restrict__ und) {
+  const long i = (long)blockIdx.x * SCORE_BLOCK + threadIdx.x;
+  if (i >= n_obs) return;
+  const int c = obs_cam[i];
+  double x, y;
+  undistort_one(cam_model[c], cam_intr + 9 * c, obs_xy[2 * i], obs_xy[2 * i + 1], f32, &x, &y);
+  und[2 * i] = x;
+  und[2 * i + 1] = y;
+}
+
+__device__ __forceinline__ void epi_corr(const double* __restrict__ und, const long* __restrict__ ca, const long* __restrict__ cb, long i,
+                                         double* c) {
+  const long a = ca[i], b = cb[i];
+  c[0] = und[2 * a]; c[1] = und[2 * a + 1]; c[2] = und[2 * b]; c[3] = und[2 * b + 1];
+}
+
+__global__ void __launch_bounds__(HYP_BLOCK)
+k_epi_hyp(long n_pairs, int n_hyp, unsigned long long seed, const long* __restrict__ start, const long* __restrict__ ca,
+          const long* __restrict__ cb, const double* __restrict__ und, double* __restrict__ hyp) {
+  const long q = (long)blockIdx.x * HYP_BLOCK + threadIdx.x;
+  if (q >= n_pairs * n_hyp) return;
+  const long p = q / n_hyp, h = q - p * n_hyp;
+  const long s = start[p], n = start[p + 1] - s;
+  double E[9];
+  if (n < EPI_SAMPLE) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) E[k] = 0.0;
+  } else {
+    int64_t idx[EPI_SAMPLE];
+    sample_distinct<EPI_SAMPLE>(seed, p, h, n, idx);
+    double c[EPI_SAMPLE][4];
+#pragma unroll
+    for (int k = 0; k < EPI_SAMPLE; ++k) epi_corr(und, ca, cb, s + idx[k], c[k]);
+    essential_hypothesis(c, E);
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) hyp[9 * q + k] = E[k];
+}
+
+__global__ void __launch_bounds__(HYP_BLOCK)
+k_res_hyp(long n_jobs, int n_hyp, int min_points, unsigned long long seed, const long* __restrict__ start, const double* __restrict__ obj,
+          const double* __restrict__ uv, double* __restrict__ hyp) {
+  const long q = (long)blockIdx.x * HYP_BLOCK + threadIdx.x;
+  if (q >= n_jobs * n_hyp) return;
+  const long j = q / n_hyp, h = q - j * n_hyp;
+  const long s = start[j], n = start[j + 1] - s;
+  double R[9], t[3];
+  bool ok = false;
+  if (n >= RES_SAMPLE && n >= min_points) {
+    int64_t idx[RES_SAMPLE];
+    sample_distinct<RES_SAMPLE>(seed, j, h, n, idx);
+    double P[RES_SAMPLE][5];
+#pragma unroll
+    for (int k = 0; k < RES_SAMPLE; ++k) {
+      const long i = s + idx[k];
+      P[k][0] = obj[3 * i]; P[k][1] = obj[3 * i + 1]; P[k][2] = obj[3 * i + 2]; P[k][3] = uv[2 * i]; P[k][4] = uv[2 * i + 1];
+    }
+    ok = res_hypothesis(P, R, t);
+  }
+  const double nan = __builtin_nan("");
+#pragma unroll
+  for (int k = 0; k < 9; ++k) hyp[12 * q + k] = ok ? R[k] : nan;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) hyp[12 * q + 9 + k] = ok ? t[k] : nan;
+}
+
+// ESS: items are correspondences (ca, cb into und), hypotheses E[9]; otherwise items are (obj, uv) points, hypotheses [R | t].
+template <bool ESS>
+__global__ void __launch_bounds__(SCORE_BLOCK)
+k_score(long n_jobs, int n_hyp, const long* __restrict__ start, const long* __restrict__ ca, const long* __restrict__ cb,
+        const double* __restrict__ und, const double* __restrict__ obj, const double* __restrict__ uv, const double* __restrict__ thr,
+        const double* __restrict__ hyp, unsigned* __restrict__ count) {
+  constexpr int HW = ESS ? 9 : 12;
+  constexpr int TILE = SCORE_BLOCK * SCORE_PER_LANE;
+  __shared__ double sh[SCORE_CHUNK * HW];
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (long j = blockIdx.y; j < n_jobs; j += gridDim.y) {
+    const long s = start[j], e = start[j + 1];
+    const long base = s + (long)blockIdx.x * TILE;
+    if (base >= e) continue;  // (uniform over the workgroup)
+    const double thr2 = thr[j] * thr[j];
+    double it[SCORE_PER_LANE][5];
+    bool valid[SCORE_PER_LANE];
+#pragma unroll
+    for (int c = 0; c < SCORE_PER_LANE; ++c) {
+      const long i = base + c * SCORE_BLOCK + tid;
+      valid[c] = i < e;
+      const long ii = valid[c] ? i : s;
+      if (ESS) {
+        epi_corr(und, ca, cb, ii, it[c]);
+        it[c][4] = 0.0;
+      } else {
+        it[c][0] = obj[3 * ii]; it[c][1] = obj[3 * ii + 1]; it[c][2] = obj[3 * ii + 2]; it[c][3] = uv[2 * ii]; it[c][4] = uv[2 * ii + 1];
+      }
+    }
+    for (int h0 = 0; h0 < n_hyp; h0 += SCORE_CHUNK) {
+      const int nh = min(SCORE_CHUNK, n_hyp - h0);
+      __syncthreads();
+      for (int k = tid; k < nh * HW; k += SCORE_BLOCK) sh[k] = hyp[((long)j * n_hyp + h0) * HW + k];
+      __syncthreads();
+      for (int h = 0; h < nh; ++h) {
+        const double* H = sh + h * HW;
+        unsigned cnt = 0;
+#pragma unroll
+        for (int c = 0; c < SCORE_PER_LANE; ++c) {
+          bool in;
+          if (ESS) in = valid[c] && epi_sampson(H, it[c][0], it[c][1], it[c][2], it[c][3]) <= thr2;
+          else in = valid[c] && res_err2(H, H + 9, it[c], it[c][3], it[c][4]) <= thr2;
+          cnt += (unsigned)__popcll(__ballot(in));
+        }
+        if (lane == 0 && cnt) atomicAdd(&count[(long)j * n_hyp + h0 + h], cnt);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Fixed-order workgroup sum of K values per thread (the tree of epipolar_math.h EPI_REDUCE_NT); every thread gets the result.
+template <int K>
+__device__ __forceinline__ void wg_sum(const double* acc, double (*red)[REFINE_BLOCK], double* out) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < K; ++k) red[k][tid] = acc[k];
+  __syncthreads();
+#pragma unroll
+  for (int s = REFINE_BLOCK / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) red[k][tid] += red[k][tid + s];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) out[k] = red[k][0];
+  __syncthreads();
+}
+
+// winner: the maximum count, the lowest index on ties
+__device__ __forceinline__ int wg_select(const unsigned* count, int n_hyp, unsigned* bc, int* bi, unsigned* best_count) {
+  const int tid = threadIdx.x;
+  unsigned c = 0;
+  int b = -1;
+  for (int h = tid; h < n_hyp; h += REFINE_BLOCK)
+    if (b < 0 || count[h] > c) { c = count[h]; b = h; }
+  bc[tid] = c; bi[tid] = b;
+  __syncthreads();
+  for (int s = REFINE_BLOCK / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+      const unsigned c2 = bc[tid + s];
+      const int b2 = bi[tid + s];
+      if (b2 >= 0 && (bi[tid] < 0 || c2 > bc[tid] || (c2 == bc[tid] && b2 < bi[tid]))) { bc[tid] = c2; bi[tid] = b2; }
+    }
+    __syncthreads();
+  }
+  const int w = bi[0];
+  *best_count = bc[0];
+  __syncthreads();
+  return w;
+}
+
+struct EpiSumDev {
+  const double* und; const long* ca; const long* cb; const unsigned char* flag; long s, e;
+  double (*red)[REFINE_BLOCK];
+  __device__ void operator()(const double* R, const double* t, double* out) {
+    double E[9], dE[5][9], acc[EPI_NSUM];
+    essential_from_pose(R, t, E);
+    essential_jacobian(R, t, dE);
+#pragma unroll
+    for (int k = 0; k < EPI_NSUM; ++k) acc[k] = 0.0;
+    for (long i = s + threadIdx.x; i < e; i += REFINE_BLOCK)
+      if (flag[i]) {
+        double c[4];
+        epi_corr(und, ca, cb, i, c);
+        epi_sampson_normal(E, dE, c[0], c[1], c[2], c[3], acc);
+      }
+    wg_sum<EPI_NSUM>(acc, red, out);
+  }
+};
+
+__global__ void __launch_bounds__(REFINE_BLOCK)
+k_epi_refine(long n_pairs, int n_hyp, const long* __restrict__ start, const long* __restrict__ ca, const long* __restrict__ cb,
+             const double* __restrict__ und, const double* __restrict__ thr, const double* __restrict__ hyp, const unsigned* __restrict__ count,
+             double* __restrict__ pose, int* __restrict__ status, long* __restrict__ n_inl, long* __restrict__ n_chr, double* __restrict__ cond,
+             int* __restrict__ winner, unsigned char* __restrict__ flag, double* __restrict__ xyz) {
+  __shared__ double red[EPI_LIN_NSUM][REFINE_BLOCK];
+  __shared__ unsigned bc[REFINE_BLOCK];
+  __shared__ int bi[REFINE_BLOCK];
+  __shared__ unsigned icnt[4];
+  const long p = blockIdx.x;
+  const int tid = threadIdx.x;
+  const long s = start[p], e = start[p + 1];
+  const double thr2 = thr[p] * thr[p];
+  const double nan = __builtin_nan("");
+  double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+  int st = EPI_OK, w = -1;
+  unsigned best = 0;
+  if (e - s < EPI_SAMPLE) st = EPI_TOO_FEW;
+  if (st == EPI_OK) {
+    w = wg_select(count + p * n_hyp, n_hyp, bc, bi, &best);
+    if (w < 0 || best < EPI_SAMPLE) st = EPI_FAILED;
+  }
+  double rt[4][12];
+  if (st == EPI_OK) {
+    const double* E = hyp + ((long)p * n_hyp + w) * 9;
+    if (tid < 4) icnt[tid] = 0;
+    // flags of the winner (each thread writes and later reads only its own items)
+    for (long i = s + tid; i < e; i += REFINE_BLOCK) {
+      double c[4];
+      epi_corr(und, ca, cb, i, c);
+      flag[i] = epi_sampson(E, c[0], c[1], c[2], c[3]) <= thr2 ? 1 : 0;
+    }
+    if (!essential_candidates(E, rt)) st = EPI_FAILED;
+  }
+  if (st == EPI_OK) {
+    unsigned mine[4] = {0, 0, 0, 0};
+    for (long i = s + tid; i < e; i += REFINE_BLOCK)
+      if (flag[i]) {
+        double c[4], wv[4];
+        epi_corr(und, ca, cb, i, c);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mine[k] += epi_in_front(rt[k], c[0], c[1], c[2], c[3], wv) ? 1u : 0u;
+      }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) if (mine[k]) atomicAdd(&icnt[k], mine[k]);
+    __syncthreads();
+    int kb = 0;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) if (icnt[k] > icnt[kb]) kb = k;
+    // (selects, not rt[kb]: a dynamic index would send rt to scratch)
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      const double v = kb == 0 ? rt[0][k] : kb == 1 ? rt[1][k] : kb == 2 ? rt[2][k] : rt[3][k];
+      if (k < 9) R[k] = v; else t[k - 9] = v;
+    }
+    EpiSumDev sum{und, ca, cb, flag, s, e, red};
+    if (!pnp_finite(epi_refine(sum, R, t))) st = EPI_FAILED;
+    unsigned prev = best;
+    for (int lo = 0; lo < EPI_LO_ROUNDS && st == EPI_OK; ++lo) {
+      double Ec[9];
+      essential_from_pose(R, t, Ec);
+      __syncthreads();
+      if (tid == 0) icnt[0] = 0;
+      __syncthreads();
+      unsigned m = 0;
+      for (long i = s + tid; i < e; i += REFINE_BLOCK) {
+        double c[4];
+        epi_corr(und, ca, cb, i, c);
+        const unsigned char f = epi_sampson(Ec, c[0], c[1], c[2], c[3]) <= thr2 ? 1 : 0;
+        flag[i] = f;
+        m += f;
+      }
+      if (m) atomicAdd(&icnt[0], m);
+      __syncthreads();
+      const unsigned cnt = icnt[0];
+      if (cnt <= prev) break;
+      prev = cnt;
+      if (!pnp_finite(epi_refine(sum, R, t))) st = EPI_FAILED;
+    }
+  }
+  if (st != EPI_OK) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    t[0] = t[1] = t[2] = 0.0;
+  }
+  // final flags, points, counts (a failed pair: all outliers)
+  double Ef[9], rtf[12];
+  essential_from_pose(R, t, Ef);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) rtf[k] = R[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) rtf[9 + k] = t[k];
+  __syncthreads();
+  if (tid < 2) icnt[tid] = 0;
+  __syncthreads();
+  unsigned m1 = 0, m2 = 0;
+  double lin[EPI_LIN_NSUM];
+#pragma unroll
+  for (int k = 0; k < EPI_LIN_NSUM; ++k) lin[k] = 0.0;
+  for (long i = s + tid; i < e; i += REFINE_BLOCK) {
+    double c[4], wv[4];
+    epi_corr(und, ca, cb, i, c);
+    unsigned char f = 0;
+    double X = nan, Y = nan, Z = nan;
+    if (st == EPI_OK && epi_sampson(Ef, c[0], c[1], c[2], c[3]) <= thr2) {
+      f = 1;
+      epi_linear_normal(c[0], c[1], c[2], c[3], lin);
+      if (epi_in_front(rtf, c[0], c[1], c[2], c[3], wv)) {
+        f = 2;
+        if (fabs(wv[3]) > 1e-12) { X = wv[0] / wv[3]; Y = wv[1] / wv[3]; Z = wv[2] / wv[3]; }
+      }
+    }
+    flag[i] = f;
+    m1 += f >= 1;
+    m2 += f == 2;
+    if (xyz) { xyz[3 * i] = X; xyz[3 * i + 1] = Y; xyz[3 * i + 2] = Z; }
+  }
+  if (m1) atomicAdd(&icnt[0], m1);
+  if (m2) atomicAdd(&icnt[1], m2);
+  double N[EPI_LIN_NSUM];
+  wg_sum<EPI_LIN_NSUM>(lin, red, N);  // (its barriers also publish icnt)
+  if (tid == 0) {
+    const double cd = st == EPI_OK ? epi_conditioning(N, Ef) : 0.0;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) pose[12 * p + k] = rtf[k];
+    status[p] = st;
+    n_inl[p] = icnt[0];
+    n_chr[p] = icnt[1];
+    cond[p] = cd;
+    winner[p] = w;
+  }
+}
+
+struct ResSumDev {
+  const double* obj; const double* uv; const double* Rh; const double* th; double thr2; long s, e;
+  double (*red)[REFINE_BLOCK];
+  __device__ void operator()(const double* R, const double* t, double* out) {
+    double acc[RES_NSUM];
+#pragma unroll
+    for (int k = 0; k < RES_NSUM; ++k) acc[k] = 0.0;
+    for (long i = s + threadIdx.x; i < e; i += REFINE_BLOCK)
+      if (res_err2(Rh, th, obj + 3 * i, uv[2 * i], uv[2 * i + 1]) <= thr2) res_point_normal(R, t, obj + 3 * i, uv[2 * i], uv[2 * i + 1], acc);
+    wg_sum<RES_NSUM>(acc, red, out);
+  }
+};
+
+__global__ void __launch_bounds__(REFINE_BLOCK)
+k_res_refine(long n_jobs, int n_hyp, int min_points, const long* __restrict__ start, const double* __restrict__ obj, const double* __restrict__ uv,
+             const double* __restrict__ thr, const double* __restrict__ hyp, const unsigned* __restrict__ count, double* __restrict__ pose,
+             int* __restrict__ status, long* __restrict__ n_inl, int* __restrict__ winner, double* __restrict__ err_out) {
+  __shared__ double red[RES_NSUM][REFINE_BLOCK];
+  __shared__ unsigned bc[REFINE_BLOCK];
+  __shared__ int bi[REFINE_BLOCK];
+  __shared__ unsigned icnt;
+  const long j = blockIdx.x;
+  const int tid = threadIdx.x;
+  const long s = start[j], e = start[j + 1];
+  const double thr2 = thr[j] * thr[j];
+  double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+  int st = EPI_OK, w = -1;
+  unsigned best = 0;
+  if (e - s < RES_SAMPLE || e - s < min_points) st = EPI_TOO_FEW;
+  if (st == EPI_OK) {
+    w = wg_select(count + j * n_hyp, n_hyp, bc, bi, &best);
+    if (w < 0 || best < RES_SAMPLE) st = EPI_FAILED;
+  }
+  if (st == EPI_OK) {
+    const double* H = hyp + ((long)j * n_hyp + w) * 12;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = H[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = H[9 + k];
+    ResSumDev sum{obj, uv, H, H + 9, thr2, s, e, red};
+    const double cost = res_refine(sum, R, t);
+    if (!pnp_finite(cost)) st = EPI_FAILED;
+  }
+  if (st != EPI_OK) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    t[0] = t[1] = t[2] = 0.0;
+  }
+  if (tid == 0) icnt = 0;
+  __syncthreads();
+  unsigned m = 0;
+  for (long i = s + tid; i < e; i += REFINE_BLOCK) {
+    m += (st == EPI_OK && res_err2(R, t, obj + 3 * i, uv[2 * i], uv[2 * i + 1]) <= thr2) ? 1u : 0u;
+    err_out[i] = st == EPI_OK ? res_err(R, t, obj + 3 * i, uv[2 * i], uv[2 * i + 1]) : __builtin_nan("");
+  }
+  if (m) atomicAdd(&icnt, m);
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) pose[12 * j + k] = R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) pose[12 * j + 9 + k] = t[k];
+    status[j] = st;
+    n_inl[j] = icnt;
+    winner[j] = w;
   }
 }
 
@@ -189,6 +599,153 @@ int cba_pose_pair_rmse(const cba_pose_pair_desc* d, int32_t device, double* rmse
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpy(rmse_out, drmse, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(count_out, dcount, (size_t)n_pairs * sizeof(int64_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  return CBA_OK;
+}
+
+int cba_pose_essential_batch(const cba_pose_essential_desc* d, int32_t device, double* pose_out, int32_t* status_out, int64_t* n_inliers_out,
+                             int64_t* n_cheiral_out, double* conditioning_out, int32_t* winner_out, uint8_t* corr_flag_out, double* xyz_out,
+                             double* undistorted_out) {
+  const char* what = "cba_pose_essential_batch";
+  if (!d || !pose_out || !status_out || !n_inliers_out || !n_cheiral_out || !conditioning_out || !corr_flag_out)
+    return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
+  if (d->n_cams <= 0 || !d->cam_model || !d->cam_intr || d->n_obs < 0 || d->n_pairs < 0 || !d->pair_start ||
+      (d->n_obs > 0 && (!d->obs_xy || !d->obs_cam)) || (d->n_pairs > 0 && !d->threshold))
+    return err(CBA_ERR_INVALID, std::string(what) + ": bad descriptor");
+  if (d->n_hyp < 1 || d->n_hyp > (1 << 16)) return err(CBA_ERR_INVALID, std::string(what) + ": n_hyp out of [1, 65536]");
+  if (d->n_pairs > 0x7fffffff) return err(CBA_ERR_INVALID, std::string(what) + ": too many pairs");
+  // bounds of everything the kernels index, checked on the host before anything reaches the device
+  for (int32_t c = 0; c < d->n_cams; ++c)
+    if (d->cam_model[c] != 0 && d->cam_model[c] != 1) return err(CBA_ERR_INVALID, std::string(what) + ": unknown camera model");
+  for (int64_t i = 0; i < d->n_obs; ++i)
+    if (d->obs_cam[i] < 0 || d->obs_cam[i] >= d->n_cams) return err(CBA_ERR_INVALID, std::string(what) + ": obs_cam out of range at row " + std::to_string(i));
+  if (d->pair_start[0] != 0) return err(CBA_ERR_INVALID, std::string(what) + ": pair_start[0] != 0");
+  for (int64_t p = 0; p < d->n_pairs; ++p) {
+    if (d->pair_start[p + 1] < d->pair_start[p]) return err(CBA_ERR_INVALID, std::string(what) + ": pair_start decreases at pair " + std::to_string(p));
+    if (!(d->threshold[p] > 0.0) || !pnp_finite(d->threshold[p])) return err(CBA_ERR_INVALID, std::string(what) + ": bad threshold at pair " + std::to_string(p));
+  }
+  const int64_t n_pairs = d->n_pairs, n_corr = d->pair_start[n_pairs], n_obs = d->n_obs;
+  if (n_corr > 0 && (!d->corr_a || !d->corr_b)) return err(CBA_ERR_INVALID, std::string(what) + ": bad descriptor");
+  for (int64_t i = 0; i < n_corr; ++i)
+    if (d->corr_a[i] < 0 || d->corr_a[i] >= n_obs || d->corr_b[i] < 0 || d->corr_b[i] >= n_obs)
+      return err(CBA_ERR_INVALID, std::string(what) + ": correspondence " + std::to_string(i) + " indexes no row");
+  int rc = select_device(device, what);
+  if (rc) return rc;
+  if (n_obs == 0 && n_pairs == 0) return CBA_OK;
+  const int n_hyp = d->n_hyp;
+  int64_t max_n = 0;
+  for (int64_t p = 0; p < n_pairs; ++p) max_n = std::max<int64_t>(max_n, d->pair_start[p + 1] - d->pair_start[p]);
+  Buffers buf;
+  void *dmodel = nullptr, *dintr = nullptr, *dxy = nullptr, *dcam = nullptr, *dund = nullptr, *dps = nullptr, *dca = nullptr, *dcb = nullptr,
+       *dthr = nullptr, *dhyp = nullptr, *dcount = nullptr, *dpose = nullptr, *dst = nullptr, *dninl = nullptr, *dnchr = nullptr,
+       *dcond = nullptr, *dwin = nullptr, *dflag = nullptr, *dxyz = nullptr;
+  rc = buf.up(d->cam_model, (size_t)d->n_cams * sizeof(int32_t), &dmodel);
+  if (!rc) rc = buf.up(d->cam_intr, (size_t)d->n_cams * 9 * sizeof(double), &dintr);
+  if (!rc) rc = buf.up(d->obs_xy, (size_t)n_obs * 2 * sizeof(double), &dxy);
+  if (!rc) rc = buf.up(d->obs_cam, (size_t)n_obs * sizeof(int32_t), &dcam);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_obs * 2 * sizeof(double), &dund);
+  if (!rc) rc = buf.up(d->pair_start, (size_t)(n_pairs + 1) * sizeof(int64_t), &dps);
+  if (!rc) rc = buf.up(d->corr_a, (size_t)n_corr * sizeof(int64_t), &dca);
+  if (!rc) rc = buf.up(d->corr_b, (size_t)n_corr * sizeof(int64_t), &dcb);
+  if (!rc) rc = buf.up(d->threshold, (size_t)n_pairs * sizeof(double), &dthr);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * n_hyp * 9 * sizeof(double), &dhyp);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * n_hyp * sizeof(unsigned), &dcount);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * 12 * sizeof(double), &dpose);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * sizeof(int32_t), &dst);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * sizeof(int64_t), &dninl);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * sizeof(int64_t), &dnchr);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * sizeof(double), &dcond);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * sizeof(int32_t), &dwin);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_corr, &dflag);
+  if (!rc && xyz_out) rc = buf.up(nullptr, (size_t)n_corr * 3 * sizeof(double), &dxyz);
+  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
+  hipError_t e = hipSuccess;
+  if (n_pairs > 0) e = hipMemset(dcount, 0, (size_t)n_pairs * n_hyp * sizeof(unsigned));
+  if (e == hipSuccess && n_obs > 0)
+    hipLaunchKernelGGL(k_epi_undistort, dim3((unsigned)((n_obs + SCORE_BLOCK - 1) / SCORE_BLOCK)), dim3(SCORE_BLOCK), 0, 0, (long)n_obs,
+                       (const int*)dcam, (const int*)dmodel, (const double*)dintr, (const double*)dxy, d->float32_io ? 1 : 0, (double*)dund);
+  if (e == hipSuccess && n_pairs > 0) {
+    const long nq = (long)n_pairs * n_hyp;
+    hipLaunchKernelGGL(k_epi_hyp, dim3((unsigned)((nq + HYP_BLOCK - 1) / HYP_BLOCK)), dim3(HYP_BLOCK), 0, 0, (long)n_pairs, n_hyp,
+                       (unsigned long long)d->seed, (const long*)dps, (const long*)dca, (const long*)dcb, (const double*)dund, (double*)dhyp);
+    const long tiles = std::max<long>(1, (long)((max_n + SCORE_BLOCK * SCORE_PER_LANE - 1) / (SCORE_BLOCK * SCORE_PER_LANE)));
+    hipLaunchKernelGGL(k_score<true>, dim3((unsigned)tiles, (unsigned)std::min<int64_t>(n_pairs, 65535)), dim3(SCORE_BLOCK), 0, 0, (long)n_pairs,
+                       n_hyp, (const long*)dps, (const long*)dca, (const long*)dcb, (const double*)dund, (const double*)nullptr,
+                       (const double*)nullptr, (const double*)dthr, (const double*)dhyp, (unsigned*)dcount);
+    hipLaunchKernelGGL(k_epi_refine, dim3((unsigned)n_pairs), dim3(REFINE_BLOCK), 0, 0, (long)n_pairs, n_hyp, (const long*)dps, (const long*)dca,
+                       (const long*)dcb, (const double*)dund, (const double*)dthr, (const double*)dhyp, (const unsigned*)dcount, (double*)dpose,
+                       (int*)dst, (long*)dninl, (long*)dnchr, (double*)dcond, (int*)dwin, (unsigned char*)dflag, (double*)dxyz);
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess && n_pairs > 0) {
+    e = hipMemcpy(pose_out, dpose, (size_t)n_pairs * 12 * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(status_out, dst, (size_t)n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(n_inliers_out, dninl, (size_t)n_pairs * sizeof(int64_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(n_cheiral_out, dnchr, (size_t)n_pairs * sizeof(int64_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(conditioning_out, dcond, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && winner_out) e = hipMemcpy(winner_out, dwin, (size_t)n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && n_corr > 0) e = hipMemcpy(corr_flag_out, dflag, (size_t)n_corr, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && xyz_out && n_corr > 0) e = hipMemcpy(xyz_out, dxyz, (size_t)n_corr * 3 * sizeof(double), hipMemcpyDeviceToHost);
+  }
+  if (e == hipSuccess && undistorted_out && n_obs > 0) e = hipMemcpy(undistorted_out, dund, (size_t)n_obs * 2 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  return CBA_OK;
+}
+
+int cba_pose_resect_batch(const cba_pose_resect_desc* d, int32_t device, double* pose_out, int32_t* status_out, int64_t* n_inliers_out,
+                          int32_t* winner_out, double* err_out) {
+  const char* what = "cba_pose_resect_batch";
+  if (!d || !pose_out || !status_out || !n_inliers_out || !err_out) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
+  if (d->n_jobs < 0 || !d->job_start || (d->n_jobs > 0 && !d->threshold)) return err(CBA_ERR_INVALID, std::string(what) + ": bad descriptor");
+  if (d->n_hyp < 1 || d->n_hyp > (1 << 16)) return err(CBA_ERR_INVALID, std::string(what) + ": n_hyp out of [1, 65536]");
+  if (d->n_jobs > 0x7fffffff) return err(CBA_ERR_INVALID, std::string(what) + ": too many jobs");
+  if (d->job_start[0] != 0) return err(CBA_ERR_INVALID, std::string(what) + ": job_start[0] != 0");
+  for (int64_t j = 0; j < d->n_jobs; ++j) {
+    if (d->job_start[j + 1] < d->job_start[j]) return err(CBA_ERR_INVALID, std::string(what) + ": job_start decreases at job " + std::to_string(j));
+    if (!(d->threshold[j] > 0.0) || !pnp_finite(d->threshold[j])) return err(CBA_ERR_INVALID, std::string(what) + ": bad threshold at job " + std::to_string(j));
+  }
+  const int64_t n_jobs = d->n_jobs, n = d->job_start[n_jobs];
+  if (n > 0 && (!d->obj || !d->uv)) return err(CBA_ERR_INVALID, std::string(what) + ": bad descriptor");
+  int rc = select_device(device, what);
+  if (rc) return rc;
+  if (n_jobs == 0) return CBA_OK;
+  const int n_hyp = d->n_hyp;
+  int64_t max_n = 0;
+  for (int64_t j = 0; j < n_jobs; ++j) max_n = std::max<int64_t>(max_n, d->job_start[j + 1] - d->job_start[j]);
+  Buffers buf;
+  void *djs = nullptr, *dobj = nullptr, *duv = nullptr, *dthr = nullptr, *dhyp = nullptr, *dcount = nullptr, *dpose = nullptr, *dst = nullptr,
+       *dninl = nullptr, *dwin = nullptr, *derr = nullptr;
+  rc = buf.up(d->job_start, (size_t)(n_jobs + 1) * sizeof(int64_t), &djs);
+  if (!rc) rc = buf.up(d->obj, (size_t)n * 3 * sizeof(double), &dobj);
+  if (!rc) rc = buf.up(d->uv, (size_t)n * 2 * sizeof(double), &duv);
+  if (!rc) rc = buf.up(d->threshold, (size_t)n_jobs * sizeof(double), &dthr);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_jobs * n_hyp * 12 * sizeof(double), &dhyp);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_jobs * n_hyp * sizeof(unsigned), &dcount);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_jobs * 12 * sizeof(double), &dpose);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_jobs * sizeof(int32_t), &dst);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_jobs * sizeof(int64_t), &dninl);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_jobs * sizeof(int32_t), &dwin);
+  if (!rc) rc = buf.up(nullptr, (size_t)n * sizeof(double), &derr);
+  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
+  hipError_t e = hipMemset(dcount, 0, (size_t)n_jobs * n_hyp * sizeof(unsigned));
+  if (e == hipSuccess) {
+    const long nq = (long)n_jobs * n_hyp;
+    hipLaunchKernelGGL(k_res_hyp, dim3((unsigned)((nq + HYP_BLOCK - 1) / HYP_BLOCK)), dim3(HYP_BLOCK), 0, 0, (long)n_jobs, n_hyp, (int)d->min_points,
+                       (unsigned long long)d->seed, (const long*)djs, (const double*)dobj, (const double*)duv, (double*)dhyp);
+    const long tiles = std::max<long>(1, (long)((max_n + SCORE_BLOCK * SCORE_PER_LANE - 1) / (SCORE_BLOCK * SCORE_PER_LANE)));
+    hipLaunchKernelGGL(k_score<false>, dim3((unsigned)tiles, (unsigned)std::min<int64_t>(n_jobs, 65535)), dim3(SCORE_BLOCK), 0, 0, (long)n_jobs,
+                       n_hyp, (const long*)djs, (const long*)nullptr, (const long*)nullptr, (const double*)nullptr, (const double*)dobj,
+                       (const double*)duv, (const double*)dthr, (const double*)dhyp, (unsigned*)dcount);
+    hipLaunchKernelGGL(k_res_refine, dim3((unsigned)n_jobs), dim3(REFINE_BLOCK), 0, 0, (long)n_jobs, n_hyp, (int)d->min_points, (const long*)djs,
+                       (const double*)dobj, (const double*)duv, (const double*)dthr, (const double*)dhyp, (const unsigned*)dcount, (double*)dpose,
+                       (int*)dst, (long*)dninl, (int*)dwin, (double*)derr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(pose_out, dpose, (size_t)n_jobs * 12 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(status_out, dst, (size_t)n_jobs * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(n_inliers_out, dninl, (size_t)n_jobs * sizeof(int64_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && winner_out) e = hipMemcpy(winner_out, dwin, (size_t)n_jobs * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && n > 0) e = hipMemcpy(err_out, derr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
   return CBA_OK;
 }

@@ -18,7 +18,8 @@ Where the stages run:
 
 The PnP itself (``csrc/pnp_math.h``) is IPPE + Levenberg-Marquardt for planar boards and a DLT + Levenberg-Marquardt for
 3-D targets: the least-squares pose, where the reference asks cv2 for SOLVEPNP_IPPE / SOLVEPNP_SQPNP.  Sessions without
-object geometry (``obj_loc`` all NaN) need the reference's essential-matrix bootstrap, which is not part of this module.
+object geometry (``obj_loc`` all NaN) take the essential-matrix bootstrap of :mod:`caliscope_amd.epipolar_pose`
+(``build_paired_pose_network(method="epipolar" | "auto")``).
 
 There is no CPU fallback: without the library or a GPU the device stages raise ``BackendError``.  ``_pnp`` replaces both
 device calls (an object with ``pnp_batch`` and ``pair_rmse``, as :class:`DevicePnP`) — the CPU test-suite passes a g++
@@ -593,12 +594,24 @@ def has_object_geometry(image_points) -> bool:
     return bool(cols) and not image_points.df[cols].isna().all().all()
 
 
-def build_paired_pose_network(image_points, camera_array, *, _pnp=None) -> PairedPoseNetwork:
-    """The reference's entry point for sessions with object geometry (the PnP path, outlier threshold 1.5).  Without
-    object geometry it raises ``ValueError``: the essential-matrix path is not available here."""
+POSE_METHODS = ("pnp", "epipolar", "auto")
+
+
+def build_paired_pose_network(image_points, camera_array, *, method: str = "pnp", _pnp=None, _epi=None) -> PairedPoseNetwork:
+    """The reference's entry point.  ``method="pnp"`` (default): the PnP path (outlier threshold 1.5), which needs object
+    geometry and raises ``ValueError`` without it.  ``"epipolar"``: the essential-matrix path of
+    :mod:`caliscope_amd.epipolar_pose` (``obj_loc`` not read).  ``"auto"``: the reference's branching — PnP with object
+    geometry, epipolar when ``obj_loc`` is all NaN."""
+    if method not in POSE_METHODS:
+        raise ValueError(f"method must be one of {POSE_METHODS}, got {method!r}")
+    if method == "epipolar" or (method == "auto" and not has_object_geometry(image_points)):
+        from caliscope_amd.epipolar_pose import build_epipolar_pose_network
+
+        logger.info("Using the epipolar bootstrap (essential matrix per camera pair).")
+        return build_epipolar_pose_network(image_points, camera_array, _epi=_epi)
     if not has_object_geometry(image_points):
-        raise ValueError("No object geometry (obj_loc all NaN): the essential-matrix bootstrap is not available in this "
-                         "backend; supply board observations with obj_loc or posed cameras.")
+        raise ValueError("No object geometry (obj_loc all NaN): the PnP path cannot run and the essential-matrix bootstrap "
+                         "was not requested; pass method='epipolar' or 'auto', or supply board observations with obj_loc.")
     builder = PoseNetworkBuilder(camera_array, image_points, _pnp=_pnp)
     return builder.estimate_camera_to_object_poses().estimate_relative_poses().filter_outliers(threshold=1.5).build()
 

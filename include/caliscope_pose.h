@@ -1,9 +1,11 @@
 /* caliscope_pose.h — C ABI of the pose-bootstrap kernels in libcaliscope_ba.so (caliscope_amd/csrc/pose_lib.hip).
  *
  * The initial pose network of an unposed board session (caliscope_amd/pose_network.py): a PnP solve per board view and
- * the stereo reprojection RMSE of every aggregated camera pair.  Conventions are those of caliscope_ba.h: every entry
+ * the stereo reprojection RMSE of every aggregated camera pair; for sessions without object geometry
+ * (caliscope_amd/epipolar_pose.py) essential-matrix RANSAC per camera pair and RANSAC resection against a point cloud.  Conventions are those of caliscope_ba.h: every entry
  * point returns 0 or a negative CBA_ERR_*, cba_last_error() describes a failure, and there is no CPU fallback (without a
- * HIP device: CBA_ERR_NO_DEVICE).  These symbols are bound by caliscope_amd/pose_network.py, not by caliscope_amd/_lib.py.
+ * HIP device: CBA_ERR_NO_DEVICE).  These symbols are bound by caliscope_amd/pose_network.py and caliscope_amd/epipolar_pose.py, not by
+ * caliscope_amd/_lib.py.
  */
 #ifndef CALISCOPE_POSE_H
 #define CALISCOPE_POSE_H
@@ -52,6 +54,59 @@ typedef struct {
  * rmse_out[p] = sqrt(sum of squared errors / (2 m)) over its m observations (0 when m = 0), count_out[p] = m.  The sum runs
  * in a fixed order: the result does not change from run to run. */
 int cba_pose_pair_rmse(const cba_pose_pair_desc* d, int32_t device, double* rmse_out, int64_t* count_out);
+
+/* 2-D-only sessions (caliscope_amd/epipolar_pose.py).  Statuses: 0 OK, 1 too few correspondences / points, 2 failed (no
+ * hypothesis with a minimal set of inliers, degenerate essential matrix, non-finite refinement). */
+enum cba_epi_status { CBA_EPI_OK = 0, CBA_EPI_TOO_FEW = 1, CBA_EPI_FAILED = 2 };
+
+/* Camera pairs and their correspondences in CSR form.  Correspondence i of pair p (pair_start[p] <= i < pair_start[p+1])
+ * joins observation rows corr_a[i] (camera A) and corr_b[i] (camera B). */
+typedef struct {
+  int32_t n_cams;
+  const int32_t* cam_model;  /* as cba_pose_pnp_desc */
+  const double* cam_intr;
+  int64_t n_obs;
+  const double* obs_xy;      /* [n_obs][2] pixels */
+  const int32_t* obs_cam;    /* [n_obs] camera index */
+  int64_t n_pairs;
+  const int64_t* pair_start; /* [n_pairs + 1], non-decreasing, pair_start[0] = 0 */
+  const int64_t* corr_a;     /* [n_corr] rows of obs_* */
+  const int64_t* corr_b;
+  const double* threshold;   /* [n_pairs] Sampson gate in normalised units (inlier: squared distance <= threshold^2) */
+  int32_t n_hyp;             /* RANSAC hypotheses per pair, 1 .. 65536 */
+  uint64_t seed;
+  int32_t float32_io;        /* round pixels and undistorted points to float32 */
+} cba_pose_essential_desc;
+
+/* Essential-matrix RANSAC of every pair: undistortion of every row once, n_hyp 8-point hypotheses per pair, Sampson
+ * scoring, the winner (most inliers, lowest index on ties) decomposed by cheirality and refined by Levenberg-Marquardt on
+ * its inliers' Sampson residuals.  pose_out[n_pairs][12]: R row-major then unit t of camera B in camera A's frame (I, 0 when
+ * the status is not CBA_EPI_OK); n_inliers_out / n_cheiral_out: inliers and inliers in front of both cameras at the final
+ * pose; conditioning_out: sigma_2 / sigma_1 of the linear fit on the final inliers; winner_out (optional): the winning
+ * hypothesis (-1: none); corr_flag_out[n_corr]: 0 outlier, 1 inlier, 2 inlier in front of both; xyz_out (optional,
+ * [n_corr][3]): the two-view point (A at [I | 0]), NaN unless flag 2 and |w| > 1e-12; undistorted_out (optional, [n_obs][2]).
+ * Deterministic for a given seed. */
+int cba_pose_essential_batch(const cba_pose_essential_desc* d, int32_t device, double* pose_out, int32_t* status_out, int64_t* n_inliers_out,
+                             int64_t* n_cheiral_out, double* conditioning_out, int32_t* winner_out, uint8_t* corr_flag_out, double* xyz_out,
+                             double* undistorted_out);
+
+/* Resection jobs in CSR form: job j holds points job_start[j] .. job_start[j+1] - 1 (object point, normalised image point). */
+typedef struct {
+  int64_t n_jobs;
+  const int64_t* job_start;  /* [n_jobs + 1] */
+  const double* obj;         /* [n][3] */
+  const double* uv;          /* [n][2] */
+  const double* threshold;   /* [n_jobs] reprojection gate, normalised units */
+  int32_t n_hyp;             /* 1 .. 65536 */
+  int32_t min_points;        /* jobs with fewer points (or fewer than 6) are CBA_EPI_TOO_FEW */
+  uint64_t seed;
+} cba_pose_resect_desc;
+
+/* RANSAC resection of every job: n_hyp 6-point DLT hypotheses, reprojection scoring, the winner refined by
+ * Levenberg-Marquardt on its inliers.  pose_out[n_jobs][12]: R, t with X_cam = R X + t; n_inliers_out at the final pose;
+ * winner_out (optional); err_out[n]: |uv - proj| at the final pose (NaN for a job that is not CBA_EPI_OK). */
+int cba_pose_resect_batch(const cba_pose_resect_desc* d, int32_t device, double* pose_out, int32_t* status_out, int64_t* n_inliers_out,
+                          int32_t* winner_out, double* err_out);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,116 @@
+"""The epipolar bootstrap on the MI355X: cba_pose_essential_batch / cba_pose_resect_batch against the g++ build of the same
+arithmetic, and calibrate_extrinsics(estimate_poses="auto" | "epipolar") on 2-D-only sessions from unposed cameras."""
+import numpy as np
+import pytest
+
+from caliscope_amd.capture_volume import CaptureVolume
+from caliscope_amd.epipolar_pose import DeviceEpipolar, pair_correspondences
+from caliscope_amd.pose_network import _intrinsic_tables
+from tests.epipolar_native import HarnessEpipolar, sampson
+from tests.epipolar_scenes import constellation_session, unposed
+from tests.scenario_scenes import keyed_errors
+
+pytestmark = pytest.mark.gpu
+
+
+def _essential_args(n_cams=5, kind="box", seed=42, n_hyp=1024):
+    ip, cams, _ = constellation_session(n_cams=n_cams, n_frames=30, kind=kind, outliers=0.03, seed=seed)
+    df = ip.df
+    arr = lambda c: df[c].to_numpy(dtype=np.int64)  # noqa: E731
+    pairs, start, ra, rb, _ = pair_correspondences(arr("cam_id"), arr("sync_index"), arr("object_id"), arr("keypoint_id"))
+    ids = sorted(cams.cameras)
+    model, intr = _intrinsic_tables(cams, ids)
+    thr = np.array([3.0 / intr[ids.index(a), 0] for a, _ in pairs])
+    return (model, intr, df[["img_loc_x", "img_loc_y"]].to_numpy(), np.searchsorted(ids, arr("cam_id")).astype(np.int32), start, ra, rb, thr,
+            n_hyp, 7)
+
+
+def test_essential_batch_matches_cpu_build_and_repeats():
+    args = _essential_args()
+    dev, cpu = DeviceEpipolar().essential_batch(*args), HarnessEpipolar().essential_batch(*args)
+    np.testing.assert_allclose(dev["undistorted"], cpu["undistorted"], rtol=0, atol=1e-12)
+    assert np.array_equal(dev["status"], cpu["status"]) and (dev["status"] == 0).all()
+    assert np.array_equal(dev["winner"], cpu["winner"])
+    start, thr = args[4], args[7]
+    und = cpu["undistorted"]
+    checked = 0
+    for p in range(len(start) - 1):
+        R, t = cpu["pose"][p, :9].reshape(3, 3), cpu["pose"][p, 9:]
+        E = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]]) @ R
+        s, e = start[p], start[p + 1]
+        d = np.array([sampson(E, *und[args[5][i]], *und[args[6][i]]) for i in range(s, e)])
+        if np.any(np.abs(d / thr[p] ** 2 - 1.0) < 1e-6):
+            continue  # a correspondence on the gate: the two builds may flag it differently
+        checked += 1
+        assert dev["n_inliers"][p] == cpu["n_inliers"][p] and dev["n_cheiral"][p] == cpu["n_cheiral"][p]
+        assert np.array_equal(dev["flag"][s:e], cpu["flag"][s:e])
+        np.testing.assert_allclose(dev["pose"][p], cpu["pose"][p], rtol=0, atol=1e-9)
+        np.testing.assert_allclose(dev["conditioning"][p], cpu["conditioning"][p], rtol=1e-6)
+    assert checked >= len(start) - 2
+    again = DeviceEpipolar().essential_batch(*args)
+    for k in ("pose", "flag", "n_inliers", "conditioning", "winner"):
+        assert np.array_equal(np.nan_to_num(dev[k]), np.nan_to_num(again[k])), k
+
+
+def test_resect_batch_matches_cpu_build():
+    rng = np.random.default_rng(4)
+    from caliscope_amd.cameras import rvec_to_matrix
+
+    sizes, objs, uvs, thr = [], [], [], []
+    for j in range(40):
+        n = 3 if j == 5 else int(rng.integers(50, 400))
+        X = rng.uniform(-1, 1, (n, 3))
+        R, t = rvec_to_matrix(rng.normal(0, 0.5, 3)), np.array([0, 0, 5.0]) + rng.normal(0, 0.3, 3)
+        Y = X @ R.T + t
+        uv = Y[:, :2] / Y[:, 2:] + rng.normal(0, 3e-4, (n, 2))
+        bad = rng.random(n) < 0.2
+        uv[bad] += rng.uniform(-0.1, 0.1, (int(bad.sum()), 2))
+        sizes.append(n); objs.append(X); uvs.append(uv); thr.append(3.0 / 1000)
+    args = (np.concatenate([[0], np.cumsum(sizes)]), np.concatenate(objs), np.concatenate(uvs), np.array(thr), 200, 50, 3)
+    dev, cpu = DeviceEpipolar().resect_batch(*args), HarnessEpipolar().resect_batch(*args)
+    assert np.array_equal(dev["status"], cpu["status"]) and dev["status"][5] == 1 and (np.delete(dev["status"], 5) == 0).all()
+    assert np.array_equal(dev["winner"], cpu["winner"]) and np.array_equal(dev["n_inliers"], cpu["n_inliers"])
+    np.testing.assert_allclose(dev["pose"], cpu["pose"], rtol=0, atol=1e-9)
+    np.testing.assert_allclose(dev["err"], cpu["err"], rtol=1e-6, atol=1e-12)
+    again = DeviceEpipolar().resect_batch(*args)
+    assert np.array_equal(dev["pose"], again["pose"])
+
+
+def _calibrate(ip, cams, method="auto"):
+    from caliscope_amd.calibrate_extrinsics import calibrate_extrinsics
+
+    return calibrate_extrinsics(ip, unposed(cams), None, refine_intrinsics=False, estimate_poses=method).capture_volume
+
+
+@pytest.mark.parametrize("case,rot_max,trans_max", [
+    (dict(n_cams=4), 0.5, 0.008),
+    (dict(n_cams=2), 0.5, 0.010),
+    (dict(n_cams=3, cam_ids=[1, 2, 5]), 0.5, 0.010),
+    (dict(n_cams=4, fisheye=(2,)), 0.5, 0.010),
+    (dict(n_cams=8, kind="body", dropout=0.1, outliers=0.02, radius=3.0), 1.0, 0.020),
+])
+def test_calibrate_extrinsics_two_d_only(case, rot_max, trans_max):
+    ip, cams, truth = constellation_session(n_frames=30, **case)
+    vol = _calibrate(ip, cams)
+    assert set(vol.camera_array.posed_cameras) == set(cams.cameras)
+    trans, rot, _ = keyed_errors(vol, truth)
+    assert rot < rot_max and trans < trans_max, (trans, rot)
+
+
+def test_epipolar_ignores_obj_loc():
+    ip, cams, truth = constellation_session(n_cams=4, n_frames=30, with_obj_loc=True)
+    df = ip.df.copy()
+    df[["obj_loc_x", "obj_loc_y", "obj_loc_z"]] = df[["obj_loc_x", "obj_loc_y", "obj_loc_z"]].to_numpy() * 7.0 + 3.0  # nonsense geometry
+    from caliscope_amd.point_data import ImagePoints
+
+    vol = CaptureVolume.bootstrap(ImagePoints(df), unposed(cams), estimate_poses="epipolar")
+    ref = CaptureVolume.bootstrap(ip, unposed(cams), estimate_poses="epipolar")
+    assert set(vol.camera_array.posed_cameras) == set(cams.cameras)
+    for c in cams.cameras:
+        assert np.array_equal(vol.camera_array.cameras[c].rotation, ref.camera_array.cameras[c].rotation)
+
+
+def test_user_scale_session_completes():
+    ip, cams, _ = constellation_session(n_cams=16, n_frames=3000, kind="body", dropout=0.1, outliers=0.01, radius=3.5, seed=3)
+    vol = CaptureVolume.bootstrap(ip, unposed(cams), estimate_poses="auto")
+    assert set(vol.camera_array.posed_cameras) == set(cams.cameras)
