@@ -3845,6 +3845,24 @@ __device__ __forceinline__ bool con_point_factor(const double* __restrict__ Vblk
   return false;
 }
 
+// A constrained point without observations (only constraint rows see it) is in no chunk: k_backsub never writes its step, and svec still holds
+// the previous one.  Its unconstrained step is dp0 = -V~^-1 g_p (no camera coupling; V = 0, so V~ = lam D^2), written here before
+// k_con_backsub* adds the correction on top.
+__global__ void k_con_orphan_start(const int* __restrict__ pts, int n, VecLayout lay, double lam, const double* __restrict__ Vblk,
+                                   const double* __restrict__ gvec, const double* __restrict__ sinv, double* __restrict__ svec) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int p = pts[t];
+  const double* gp = gvec + lay.ncp_pad;
+  double* sp = svec + lay.ncp_pad;
+  double L[6], y[3], x[3];
+  con_point_factor(Vblk, sinv + lay.ncp_pad, lay, p, lam, L);  // (a failed factor is flagged by k_con_schur*)
+  const double g3[3] = {gp[p], gp[lay.Ppad + p], gp[2 * lay.Ppad + p]};
+  chol3_fwd(L, g3, y);
+  chol3_bwd(L, y, x);
+  sp[p] = -x[0]; sp[lay.Ppad + p] = -x[1]; sp[2 * lay.Ppad + p] = -x[2];
+}
+
 // Woodbury correction of the reduced camera system, one workgroup per component:
 //   Sacc -= G^T M^-1 G,  bacc -= G^T M^-1 h,   G = J_c V~^-1 W^T (rows: sum_i (T_i z)^T),  h = J_c V~^-1 g_p,
 //   z = L_p^-1 (slot coefficient), M = I + Z Z^T factored in place (lower) and kept for k_con_backsub.

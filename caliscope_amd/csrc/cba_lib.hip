@@ -74,6 +74,9 @@ static const char* kTimerNames[T_COUNT] = {
 struct EventPair { hipEvent_t a, b; };
 struct cba_group;
 
+// rows of partial4 (4 doubles each) that ||J v||^2 may fill: the workgroups of k_jv, then those of k_con_jv behind them (run_jv)
+constexpr int JV_ROWS = 2048, CON_ROWS = 1024, PARTIAL4_ROWS = JV_ROWS + CON_ROWS;
+
 struct cba_problem {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -136,6 +139,7 @@ struct cba_problem {
   std::vector<int> h_heavy_pts;
   ConPlan con{};           // rigid-distance constraint rows (cba_set_constraints); con.n_con == 0: none
   int con_grid = 0;        // workgroups of the per-constraint kernels
+  int n_con_orphan = 0; int* con_orphan = nullptr;  // constrained points without observations (k_con_orphan_start)
   int* flags = nullptr;
   double* h_scal = nullptr;  // pinned, mapped: k_publish writes it (d_hscal is the same memory seen from the device)
   int* h_flags = nullptr;
@@ -1086,7 +1090,7 @@ static int configure_kernels(cba_problem* p) {
     int per_cu = p->tab_global ? resident_per_cu(k_jv<NC, 1, true>, lds_jv(p, 1), 2) : resident_per_cu(k_jv<NC, 1>, lds_jv(p, 1), 2);
     if (const char* e = std::getenv("CBA_JV_WGS")) per_cu = std::max(1, std::min(std::atoi(e), 8));
     p->jv_grid = (int)std::max<long>(1, std::min<long>((p->N + BLOCK - 1) / BLOCK, (long)p->cus * per_cu));
-    p->jv_grid = std::min(p->jv_grid, 2048);  // (rows of partial4)
+    p->jv_grid = std::min(p->jv_grid, JV_ROWS);  // (rows of partial4 before the constraint rows' CON_ROWS)
   }
   if (p->n_heavy && (rc = allow_lds(k_heavy_schur<NC>, (size_t)p->ncp * 3 * sizeof(double) + (size_t)p->ncp * sizeof(int)))) return rc;
   if ((rc = allow_lds(k_chol_apply, (size_t)p->ncp * 8))) return rc;
@@ -1451,7 +1455,8 @@ int cba_create(const cba_problem_desc* d, const cba_options* opt, cba_problem** 
   // (+ 1/8: the dealt plan of a two-stage handle has a few chunks — on small problems: workgroups — more or fewer than the cheap one)
   p->partial_capacity = (size_t)std::max<long>((long)p->grid * w_build, (long)(p->tile_grid + p->tile_grid / 8 + 1) * std::max(p->tp.rep, 1) * p->tp.tile_elems);
   TRY(dev_alloc(p, &p->partial, p->partial_capacity));
-  TRY(dev_alloc(p, &p->partial4, (size_t)2048 * 4)); TRY(dev_alloc(p, &p->partial1, (size_t)2048)); TRY(dev_alloc(p, &p->partial4b, (size_t)2048 * 4));  // obs rows + constraint rows
+  // partial4: up to JV_ROWS rows of k_jv followed by up to CON_ROWS rows of k_con_jv (run_jv)
+  TRY(dev_alloc(p, &p->partial4, (size_t)PARTIAL4_ROWS * 4)); TRY(dev_alloc(p, &p->partial1, (size_t)2048)); TRY(dev_alloc(p, &p->partial4b, (size_t)2048 * 4));
   TRY(dev_alloc(p, &p->Sacc, (size_t)ncp * ncp + (size_t)B_SLICES * p->lay.ncp_pad));  // + the rhs accumulator b, B_SLICES rows (k_reg_reduce)
   TRY(dev_alloc(p, &p->tri, (size_t)ncp * (ncp + 1) / 2 + p->lay.ncp_pad));
   if (!p->eval_only) {
@@ -1535,7 +1540,8 @@ int cba_get_info(cba_problem* p, cba_info* o) {
     const bool cs = p->cs.n_sc && !p->det_m && !p->n_heavy;
     const bool camg = cs ? (p->nct == 6 ? build_cs_camg<6>(p) : build_cs_camg<9>(p)) : (p->nct == 6 ? build_camg<6>(p) : build_camg<9>(p));
     const bool uglob = cs && (p->nct == 6 ? build_cs_uglob<6>(p) : build_cs_uglob<9>(p));
-    o->build_camg = (camg ? 1 : 0) | (p->tab_global ? 2 : 0) | (cs ? 4 : 0) | (uglob ? 8 : 0);
+    o->build_camg = (camg ? 1 : 0) | (p->tab_global ? 2 : 0) | (cs ? 4 : 0) | (uglob ? 8 : 0) | (p->backsub_rec ? 16 : 0) |
+                    (p->con.n_con && p->con.small ? 32 : 0);
   }
   return CBA_OK;
 }
@@ -1680,6 +1686,9 @@ static int run_build_into(cba_problem* p, const double* xvec, const double* tab,
     int rho_rows = p->grid;
     if (p->con.n_con) {  // constraint rows: f, u, their share of g_p and of the squared column norms
       HIPCHK(hipMemsetAsync(p->con.cdiag, 0, (size_t)3 * p->lay.Ppad * sizeof(double), p->stream));
+      if (p->n_con_orphan)  // (no observation term: the build left their g_p as the previous linearisation made it)
+        hipLaunchKernelGGL(k_zero_heavy, dim3((p->n_con_orphan + 63) / 64), dim3(64), 0, p->stream, (const int*)p->con_orphan, p->n_con_orphan, p->lay,
+                           g + p->lay.ncp_pad, 3, (double*)nullptr, 0);
       hipLaunchKernelGGL(k_con_eval<true>, dim3(p->con_grid), dim3(BLOCK), 0, p->stream, p->con, xvec, p->lay, p->loss, p->f_scale, g,
                          p->partial1 + p->grid, p->flags, (double*)nullptr);
       rho_rows += p->con_grid;
@@ -1703,6 +1712,9 @@ static int run_jv(cba_problem* p, int nv, int* rows_out = nullptr, const double*
   ScopedTimer t(p, T_JV);
   if (!xvec) { xvec = p->x; tab = p->tab; }  // (the speculative linearisation evaluates the trial point: x_new, tab_new)
   const int grid = nv == 1 ? p->jv_grid : (int)std::min<long>((p->N + BLOCK - 1) / BLOCK, 1024);
+  const int con_rows = p->con.n_con ? p->con_grid : 0;
+  if (grid + con_rows > PARTIAL4_ROWS)  // (nothing launched: the rows would land beyond the end of partial4)
+    return fail(CBA_ERR_UNSUPPORTED, "run_jv: %d rows of k_jv and %d of k_con_jv exceed the %d rows of partial4", grid, con_rows, PARTIAL4_ROWS);
   auto launch_jv = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds_jv(p, nv), p->stream, p->obs_u, p->obs_v, p->obs_cam, p->obs_pt,
                        p->N, xvec, p->lay, tab, p->cam_off, p->C, p->loss, p->f_scale, p->v1, p->v2, p->partial4);
@@ -1710,10 +1722,10 @@ static int run_jv(cba_problem* p, int nv, int* rows_out = nullptr, const double*
   if (nv == 1) { if (p->tab_global) launch_jv(k_jv<NC, 1, true>); else launch_jv(k_jv<NC, 1>); }
   else { if (p->tab_global) launch_jv(k_jv<NC, 2, true>); else launch_jv(k_jv<NC, 2>); }
   int rows = grid;
-  if (p->con.n_con) {
+  if (con_rows) {
     if (nv == 1) hipLaunchKernelGGL(k_con_jv<1>, dim3(p->con_grid), dim3(BLOCK), 0, p->stream, p->con, p->lay, p->v1, p->v2, p->partial4 + 4 * grid);
     else hipLaunchKernelGGL(k_con_jv<2>, dim3(p->con_grid), dim3(BLOCK), 0, p->stream, p->con, p->lay, p->v1, p->v2, p->partial4 + 4 * grid);
-    rows += p->con_grid;
+    rows += con_rows;
   }
   if (rows_out) { *rows_out = rows; return CBA_OK; }  // compact fused step: k_lin_finish sums the rows
   hipLaunchKernelGGL(k_reduce_narrow<false>, dim3(1), dim3(BLOCK), 0, p->stream, p->partial4, rows, 4, p->scal + 12);
@@ -2089,6 +2101,9 @@ static int run_newton_chain(cba_problem* p, double lam, const double* lam_dev, b
       hipLaunchKernelGGL(k_heavy_finish, dim3((p->n_heavy + 63) / 64), dim3(64), 0, p->stream, p->heavy_pts, p->heavy_frag, p->n_heavy, p->lay, lam,
                          p->V, p->g, p->sinv, p->s);
     if (p->con.n_con) {
+      if (p->n_con_orphan)  // the unconstrained step of the constrained points the back-substitution above does not visit
+        hipLaunchKernelGGL(k_con_orphan_start, dim3((p->n_con_orphan + 63) / 64), dim3(64), 0, p->stream, (const int*)p->con_orphan, p->n_con_orphan, p->lay,
+                           lam, (const double*)p->V, (const double*)p->g, (const double*)p->sinv, p->s);
       if (p->con.small)
         hipLaunchKernelGGL(k_con_backsub_small, dim3(p->con.n_comp), dim3(BLOCK), (size_t)(9 * p->con.max_np + 2 * p->con.max_m) * sizeof(double), p->stream,
                            p->con, p->lay, lam, p->V, p->sinv, p->s);
@@ -2314,6 +2329,16 @@ int cba_set_constraints(cba_problem* p, int32_t n_con, const int32_t* groups_a, 
                 "camera coupling (%d rows x %d camera parameters); the limits are 2 GB and 4 GB - use fewer rows per object and frame (DESIGN.md 2.2)",
                 comp_m[K] * 8e-9, comp_m[K], (double)n_con * (p->ncp + 1) * 8e-9, n_con, p->ncp);
   int rc;
+  // constrained points that no observation sees: the build writes neither their V nor their g_p, the back-substitution not their step
+  // (run_build_into zeroes their g_p before the rows add theirs, k_con_orphan_start forms their unconstrained step)
+  std::vector<int> orphan;
+  {
+    std::vector<int> hps((size_t)P + 1);
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipMemcpy(hps.data(), p->pt_start, hps.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (const int q : comp_pts)
+      if (hps[(size_t)q + 1] == hps[q]) orphan.push_back(q);
+  }
   const double ms_graph = lap_ms(t_enter);
   const auto t_up = std::chrono::steady_clock::now();
   upload_stage_acquire(p);
@@ -2324,6 +2349,8 @@ int cba_set_constraints(cba_problem* p, int32_t n_con, const int32_t* groups_a, 
   TRYC(dev_upload(p, &dpt, pt)); TRYC(dev_upload(p, &dlp, lp)); TRYC(dev_upload(p, &dorder, order)); TRYC(dev_upload(p, &dcc, comp_con));
   TRYC(dev_upload(p, &dcp, comp_pt)); TRYC(dev_upload(p, &dcps, comp_pts)); TRYC(dev_upload(p, &dcm, comp_m));
   TRYC(dev_upload(p, &ddist, dist)); TRYC(dev_upload(p, &dw, wgt));
+  int* dorphan = nullptr;
+  if (!orphan.empty()) TRYC(dev_upload(p, &dorphan, orphan));
   ConPlan cp{};
   cp.n_con = n_con; cp.n_comp = K; cp.pt = dpt; cp.lp = dlp; cp.dist = ddist; cp.weight = dw; cp.order = dorder;
   cp.comp_con = dcc; cp.comp_pt = dcp; cp.comp_pts = dcps; cp.comp_m = dcm;
@@ -2357,7 +2384,8 @@ int cba_set_constraints(cba_problem* p, int32_t n_con, const int32_t* groups_a, 
     fprintf(stderr, "  cba_set_constraints: %d rows, %d components: graph %.3f ms, uploads + allocations %.3f, kernel attributes %.3f, memset + sync %.3f\n", n_con, K,
             ms_graph, ms_upload, ms_attr, lap_ms(t_sync));
   p->con = cp;
-  p->con_grid = std::max(1, std::min((n_con + BLOCK - 1) / BLOCK, 1024));
+  p->con_orphan = dorphan; p->n_con_orphan = (int)orphan.size();
+  p->con_grid = std::max(1, std::min((n_con + BLOCK - 1) / BLOCK, CON_ROWS));
   return CBA_OK;
 }
 

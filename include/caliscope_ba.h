@@ -332,7 +332,16 @@ typedef struct {
                                nine-parameter cameras; CBA_CAMTAB_GLOBAL=0/1 forces).  The camera count is then bounded by the per-camera
                                accumulators of the linearisation: ~650 six- / ~320 nine-parameter cameras;
                                bit 2: the linearisation runs over camera-sorted super-chunks (k_build_cs: camera blocks accumulated in registers,
-                               the default; CBA_BUILD_CS=0, deterministic sums or fragments of very large points fall back to k_build). */
+                               the default; CBA_BUILD_CS=0, deterministic sums, heavy points or a chunk whose point range exceeds 512 ids
+                               fall back to k_build);
+                               bit 3: that camera-sorted linearisation adds its camera blocks to ONE global copy by FP64 atomics (the per-camera
+                               blocks no longer fit the LDS: beyond ~650 six- / ~320 nine-parameter cameras);
+                               bit 4: the back-substitution streams the T records of the Schur pass (k_backsub_rec: six-parameter cameras by
+                               default, CBA_BACKSUB_REC=0/1 forces) instead of linearising every observation again; off when a point has more
+                               observations than one chunk holds;
+                               bit 5: the constraint rows run the small-component kernels (k_con_schur_small / k_con_backsub_small: every
+                               component has at most 64 rows and its dense blocks fit 120 KB of LDS, no heavy points; CBA_CON_SMALL=0 turns them
+                               off); 0 without constraint rows. */
 } cba_info;
 int cba_get_info(cba_problem* p, cba_info* out);
 
