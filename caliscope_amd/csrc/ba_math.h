@@ -326,10 +326,34 @@ CBA_HD void chol3_bwd(const double* L, const double* y, double* x) {
   x[0] = (y[0] - L[1] * x[1] - L[3] * x[2]) * L[0];
 }
 
+// tan(x) for |x| <= pi/2 from + - * / alone, without contraction: the same bits from hipcc and from g++ (the maths libraries'
+// tan differ in the last bit, which the pose refinements downstream of undistort_one amplify to 1e-8).  sin and cos of x / 2 by
+// their Taylor series in Horner form (12 terms each: the first one left out is below 1e-19 at pi/4), then tan x = 2 s c / (c^2 - s^2);
+// a few ulp.  At pi/2 itself the denominator is held at 1e-16 (libm's tan gives 1.6e16 there).
+CBA_HD double tan_portable(double x) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double a = 0.5 * x, q = a * a;
+  double s = 1.0, c = 1.0;
+#pragma unroll
+  for (int k = 11; k >= 1; --k) {
+    s = 1.0 - s * q / (double)((2 * k) * (2 * k + 1));
+    c = 1.0 - c * q / (double)((2 * k - 1) * (2 * k));
+  }
+  s *= a;
+  const double den = c * c - s * s;
+  return 2.0 * s * c / (den > 1e-16 ? den : 1e-16);
+}
+
 // Undistortion of one pixel observation to normalised coordinates (cba_triangulate, cba_pose_pnp_batch).
 // Pinhole: OpenCV's five fixed-point iterations  x <- (x0 - delta(x)) / cdist(x).  Fisheye: Newton on
 // theta_d = theta (1 + k1 theta^2 + ...), at most 10 steps, stop below 1e-8, theta_d clipped to [-pi/2, pi/2].
+// No contraction and no library call: the device build and the g++ build return the same bits.
 CBA_HD void undistort_one(int model, const double* __restrict__ in9, double u, double v, int f32, double* xo, double* yo) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
   if (f32) { u = (double)(float)u; v = (double)(float)v; }
   const double fx = in9[0], fy = in9[1], cx = in9[2], cy = in9[3];
   const double x0 = (u - cx) / fx, y0 = (v - cy) / fy;
@@ -359,7 +383,7 @@ CBA_HD void undistort_one(int model, const double* __restrict__ in9, double u, d
         th -= fix;
         if (fabs(fix) < 1e-8) break;
       }
-      scale = tan(th) / td;
+      scale = tan_portable(th) / td;
     }
     x = x0 * scale;
     y = y0 * scale;

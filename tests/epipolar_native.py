@@ -42,8 +42,34 @@ def harness():
                                            D, I32, I64, I64, D, I32, U8, D, D]
         lib.eh_resect_batch.restype = None
         lib.eh_resect_batch.argtypes = [C.c_int64, I64, D, D, D, C.c_int32, C.c_int32, C.c_uint64, D, I32, I64, I32, D]
+        lib.eh_essential_counts.restype = None
+        lib.eh_essential_counts.argtypes = [D, I64, I64, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, I64, I64]
+        lib.eh_resect_counts.restype = None
+        lib.eh_resect_counts.argtypes = [D, D, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, I64, I64]
         _LIB = lib
     return _LIB
+
+
+def essential_counts(und, corr_a, corr_b, s, n, thr, n_hyp, seed, job, items):
+    """Inlier count of every hypothesis of the job holding correspondences s .. s + n - 1 (batch index ``job``) over
+    ``items`` (offsets into the job); ``und`` are the undistorted rows."""
+    und = np.ascontiguousarray(und, dtype=np.float64)
+    corr_a, corr_b = np.ascontiguousarray(corr_a, dtype=np.int64), np.ascontiguousarray(corr_b, dtype=np.int64)
+    items = np.ascontiguousarray(items, dtype=np.int64)
+    count = np.zeros(int(n_hyp), dtype=np.int64)
+    harness().eh_essential_counts(_p(und), _p(corr_a, I64), _p(corr_b, I64), int(s), int(n), float(thr), int(n_hyp), int(seed), int(job),
+                                  len(items), _p(items, I64), _p(count, I64))
+    return count
+
+
+def resect_counts(obj, uv, s, n, thr, n_hyp, seed, job, items):
+    """As ``essential_counts`` for a resection job of points s .. s + n - 1."""
+    obj, uv = np.ascontiguousarray(obj, dtype=np.float64), np.ascontiguousarray(uv, dtype=np.float64)
+    items = np.ascontiguousarray(items, dtype=np.int64)
+    count = np.zeros(int(n_hyp), dtype=np.int64)
+    harness().eh_resect_counts(_p(obj), _p(uv), int(s), int(n), float(thr), int(n_hyp), int(seed), int(job), len(items), _p(items, I64),
+                               _p(count, I64))
+    return count
 
 
 def sample(seed, job, h, n, k):

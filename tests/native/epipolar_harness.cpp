@@ -86,6 +86,48 @@ int eh_decompose(const double* E, int64_t n, const double* c, double* rt_out /*[
   return best;
 }
 
+// The inlier count of every hypothesis of one job over a chosen list of its items (tests: what k_score has to add up over
+// all tiles, and what it would add up over some of them).  The job holds correspondences / points s .. s + n - 1; its
+// hypotheses are drawn as the batch calls draw them for job index `job`; items[] are offsets into the job.
+void eh_essential_counts(const double* und, const int64_t* ca, const int64_t* cb, int64_t s, int64_t n, double thr, int32_t n_hyp, uint64_t seed,
+                         int64_t job, int64_t n_items, const int64_t* items, int64_t* count_out) {
+  auto corr = [&](int64_t i, double* c) { c[0] = und[2 * ca[i]]; c[1] = und[2 * ca[i] + 1]; c[2] = und[2 * cb[i]]; c[3] = und[2 * cb[i] + 1]; };
+  for (int h = 0; h < n_hyp; ++h) {
+    count_out[h] = 0;
+    if (n < EPI_SAMPLE) continue;
+    int64_t idx[EPI_SAMPLE];
+    sample_distinct<EPI_SAMPLE>(seed, job, h, n, idx);
+    double c[EPI_SAMPLE][4], E[9];
+    for (int k = 0; k < EPI_SAMPLE; ++k) corr(s + idx[k], c[k]);
+    essential_hypothesis(c, E);
+    for (int64_t q = 0; q < n_items; ++q) {
+      double cc[4];
+      corr(s + items[q], cc);
+      count_out[h] += epi_sampson(E, cc[0], cc[1], cc[2], cc[3]) <= thr * thr ? 1 : 0;
+    }
+  }
+}
+
+void eh_resect_counts(const double* obj, const double* uv, int64_t s, int64_t n, double thr, int32_t n_hyp, uint64_t seed, int64_t job,
+                      int64_t n_items, const int64_t* items, int64_t* count_out) {
+  for (int h = 0; h < n_hyp; ++h) {
+    count_out[h] = 0;
+    if (n < RES_SAMPLE) continue;
+    int64_t idx[RES_SAMPLE];
+    sample_distinct<RES_SAMPLE>(seed, job, h, n, idx);
+    double P[RES_SAMPLE][5], Rh[9], th[3];
+    for (int k = 0; k < RES_SAMPLE; ++k) {
+      const int64_t i = s + idx[k];
+      P[k][0] = obj[3 * i]; P[k][1] = obj[3 * i + 1]; P[k][2] = obj[3 * i + 2]; P[k][3] = uv[2 * i]; P[k][4] = uv[2 * i + 1];
+    }
+    if (!res_hypothesis(P, Rh, th)) continue;
+    for (int64_t q = 0; q < n_items; ++q) {
+      const int64_t i = s + items[q];
+      count_out[h] += res_err2(Rh, th, obj + 3 * i, uv[2 * i], uv[2 * i + 1]) <= thr * thr ? 1 : 0;
+    }
+  }
+}
+
 // what cba_pose_essential_batch computes (und: [n_obs][2] out)
 void eh_essential_batch(int32_t n_cams, const int32_t* cam_model, const double* cam_intr, int64_t n_obs, const double* obs_xy, const int32_t* obs_cam,
                         int64_t n_pairs, const int64_t* pair_start, const int64_t* ca, const int64_t* cb, const double* thr, int32_t n_hyp, uint64_t seed,
