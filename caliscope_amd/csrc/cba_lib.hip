@@ -253,19 +253,32 @@ static int dev_alloc(cba_problem* p, T** out, size_t count) {
   p->device_bytes += (long)bytes;
   return CBA_OK;
 }
-template <typename T, typename V>
-static int dev_upload(cba_problem* p, T** out, const V& h) {  // V: any contiguous host array of T (std::vector, HostVec, RawVec)
-  static_assert(std::is_same<typename std::remove_cv<typename std::remove_pointer<decltype(h.data())>::type>::type, T>::value, "element type");
-  int rc = dev_alloc(p, out, h.size());
+// `count` host elements into a new buffer: small ones through the pinned buffer of the set-up call and the handle's stream (upload_stage_acquire)
+template <typename T>
+static int dev_upload(cba_problem* p, T** out, const T* h, size_t count) {
+  int rc = dev_alloc(p, out, count);
   if (rc) return rc;
-  const size_t bytes = h.size() * sizeof(T);
+  const size_t bytes = count * sizeof(T);
   if (bytes && p->up_stage && p->stream && bytes <= kUpStageMax && p->up_used + bytes <= p->up_cap) {
-    std::memcpy(p->up_stage + p->up_used, h.data(), bytes);
+    std::memcpy(p->up_stage + p->up_used, h, bytes);
     HIPCHK(hipMemcpyAsync(*out, p->up_stage + p->up_used, bytes, hipMemcpyHostToDevice, p->stream));
     p->up_used += (bytes + 63) & ~(size_t)63;
   } else if (bytes) {
-    HIPCHK(hipMemcpy(*out, h.data(), bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(*out, h, bytes, hipMemcpyHostToDevice));
   }
+  return CBA_OK;
+}
+template <typename T, typename V>
+static int dev_upload(cba_problem* p, T** out, const V& h) {  // V: any contiguous host array of T (std::vector, HostVec, RawVec)
+  static_assert(std::is_same<typename std::remove_cv<typename std::remove_pointer<decltype(h.data())>::type>::type, T>::value, "element type");
+  return dev_upload(p, out, h.data(), h.size());
+}
+// a new buffer, zeroed on the handle's stream
+template <typename T>
+static int dev_zeros(cba_problem* p, T** out, size_t count) {
+  int rc = dev_alloc(p, out, count);
+  if (rc) return rc;
+  HIPCHK(hipMemsetAsync(*out, 0, count * sizeof(T), p->stream));
   return CBA_OK;
 }
 // a pinned buffer for the small uploads of one set-up call (cba_create, cba_set_constraints); given back — after the stream has been waited for — by
@@ -299,27 +312,6 @@ static int stage_sent(cba_problem* p) {
   p->h_vec_in_flight = true;
   return CBA_OK;
 }
-
-// std::vector without value-initialisation of its elements: the threads that fill the observation-sized host arrays of cba_create are the first to
-// touch their pages (zero-filling ~70 bytes per observation on the calling thread was a third of "reorder on host")
-template <typename T>
-struct NoInitAlloc : std::allocator<T> {
-  template <typename U> struct rebind { using other = NoInitAlloc<U>; };
-  NoInitAlloc() = default;
-  template <typename U> NoInitAlloc(const NoInitAlloc<U>&) {}
-  template <typename U, typename... A> void construct(U* ptr, A&&... args) {
-    if constexpr (sizeof...(A) == 0) ::new ((void*)ptr) U; else ::new ((void*)ptr) U(std::forward<A>(args)...);
-  }
-  // large arrays from the pool of huge-page blocks the plan's arrays use (schur_plan.h: a handle's set-up was paying for the page faults of ~100 MB of
-  // freshly mapped host memory per call)
-  T* allocate(size_t n) {
-    void* ptr = rawvec_detail::acquire_tracked(n * sizeof(T));
-    if (!ptr) throw std::bad_alloc();
-    return static_cast<T*>(ptr);
-  }
-  void deallocate(T* ptr, size_t n) noexcept { rawvec_detail::release_tracked(ptr, n * sizeof(T)); }
-};
-template <typename T> using HostVec = std::vector<T, NoInitAlloc<T>>;
 
 // roctx range around the host-side enqueue of a phase: `rocprofv3 --marker-trace --kernel-trace` shows the kernels of an
 // iteration under build / linearize / schur / cholesky / backsub / trial (free when no profiler is attached)
@@ -593,7 +585,7 @@ const char* cba_timer_name(int32_t i) { return (i >= 0 && i < T_COUNT) ? kTimerN
 
 int64_t cba_host_plan(int32_t n_points, int64_t n_obs, const int32_t* obs_pt, const int32_t* obs_cam, int32_t n_cams,
                       int32_t chunk_cap, int64_t* order_out, int64_t* pt_start_out, int64_t* chunk_start_out) {
-  return host_plan_impl([](int code, const char* fmt, auto... args) { return fail(code, fmt, args...); }, n_points, n_obs, obs_pt, obs_cam, n_cams, chunk_cap,
+  return host_plan_impl(fail, n_points, n_obs, obs_pt, obs_cam, n_cams, chunk_cap,
                         order_out, pt_start_out, chunk_start_out);
 }
 
@@ -1099,16 +1091,197 @@ static int configure_kernels(cba_problem* p) {
   return CBA_OK;
 }
 
+// ---- cba_create, step by step: each helper owns one resource of the handle ---------------------------------------------------------------------
+
+// The Schur plan of the register kernels is dealt on its own thread from here on; it reads the sorted cameras and the point table.
+// Two-stage plan: start with the CHEAP plan (a third of the host time, pair kernel 1.5-1.75x slower) and swap the dealt one in when its thread is
+// done — the handle is ready 10 ms (cfg4) to half a second (cfg5) earlier and a solve of a handful of iterations may be over before the dealt plan
+// would have been.  Default from kTwoStageObs observations on (below, the dealt plan is ready before the uploads are); CBA_PLAN=full / swap force
+// one way, cba_plan_wait makes a handle final (benchmarks).  Not with fixed-order sums (the iteration the swap lands on would vary from run to run)
+// nor with the profiling build (it wants the plan it profiles).
+static void start_plan_task(cba_problem* p, const cba_options* opt, int n_cus, const int* hcam, const int* hps) {
+  constexpr long kTwoStageObs = 500000;
+  const char* plan_env = std::getenv("CBA_PLAN");
+  bool plan_two_stage = p->N >= kTwoStageObs;
+  if (plan_env && std::strcmp(plan_env, "swap") == 0) plan_two_stage = true;
+  if (plan_env && (std::strcmp(plan_env, "full") == 0 || std::strcmp(plan_env, "cheap") == 0)) plan_two_stage = false;
+  if ((opt && opt->deterministic) || p->schur_clock) plan_two_stage = false;
+  Reg2Params prm = (p->nct == 9) ? reg2_params<9, Reg3Cfg<9>>(p) : reg2_params<6, Reg3Cfg<6>>(p);
+  if (plan_env) prm.cheap = std::strcmp(plan_env, "cheap") == 0;  // (measurements: the cheap plan for good)
+  p->plan_task = new PlanTask();  // owned by the handle: cba_destroy cancels and joins it while the arrays it reads are alive
+  {  // the workgroup budget of the pair kernel, fixed before the plan thread may want it (two stages: it binds the dealt plan itself)
+    const int cus0 = n_cus > 0 ? n_cus : 256;
+    const size_t tile_lds = (p->nct == 9) ? Reg3Cfg<9>::LDS_BYTES : Reg3Cfg<6>::LDS_BYTES;
+    const int per_cu = std::min(std::max<int>(1, (int)((160 * 1024) / tile_lds)), (p->nct == 9) ? RegCfg<9>::PER_CU : RegCfg<6>::PER_CU);  // LDS, register budget
+    const int mb0 = (opt && opt->max_blocks > 0) ? opt->max_blocks : 2 * cus0;
+    p->plan_max_blocks = std::min(cus0 * per_cu, std::max(mb0, cus0));  // no partial last round
+  }
+  p->plan_task->start(prm, hcam, hps, plan_two_stage, p);
+}
+
+// the handle's stream and its mapped host mailbox (MailLayout), both from the pool of the device where it has them
+static int open_stream_and_mailbox(cba_problem* p, const MailLayout& mail) {
+  {
+    std::lock_guard<std::mutex> lock(g_pool_mu);
+    DevicePool& pool = g_pool[p->device];
+    if (!pool.streams.empty()) { p->stream = pool.streams.back(); pool.streams.pop_back(); }
+    for (size_t i = 0; i < pool.mail.size(); ++i)
+      if (pool.mail[i].second >= mail.total) {
+        p->h_scal = pool.mail[i].first; p->mail_doubles = pool.mail[i].second;
+        pool.mail.erase(pool.mail.begin() + (long)i);
+        break;
+      }
+  }
+  if (!p->stream) HIPCHK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  if (!p->h_scal) {
+    p->mail_doubles = std::max<size_t>(mail.total, MailLayout(96).total);  // (room for 96 camera parameters: small rigs share mailboxes)
+    HIPCHK(hipHostMalloc((void**)&p->h_scal, p->mail_doubles * sizeof(double), hipHostMallocMapped));
+  }
+  HIPCHK(hipHostGetDevicePointer((void**)&p->d_hscal, p->h_scal, 0));
+  p->h_cam = p->h_scal + mail.cam; p->d_hcam = p->d_hscal + mail.cam;
+  p->h_flags = reinterpret_cast<int*>(p->h_scal + mail.flags); p->d_hflags = reinterpret_cast<int*>(p->d_hscal + mail.flags);
+  p->h_bcam = p->h_scal + mail.bcam; p->d_hbcam = p->d_hscal + mail.bcam;
+  std::memset(p->h_scal, 0, mail.total * sizeof(double));
+  return CBA_OK;
+}
+
+#define TRYS(e) do { const int rc_ = (e); if (rc_) return rc_; } while (0)
+
+// the observations in sorted order and their tables; the caller's (u, v) pairs go up as they are and are sorted on the device (the raw copy is
+// scratch: v2's memory is not big enough, it stays in the arena)
+static int upload_observations(cba_problem* p, const double* obs_uv, const SortedObs& obs, const PointTables& tabs) {
+  TRYS(dev_upload(p, &p->obs_cam, obs.cam)); TRYS(dev_upload(p, &p->obs_pt, obs.pt));
+  TRYS(dev_upload(p, &p->order, obs.order)); TRYS(dev_upload(p, &p->pt_start, tabs.pt_start)); TRYS(dev_upload(p, &p->chunk_start, tabs.chunk_start));
+  double* uv_raw = nullptr;
+  TRYS(dev_upload(p, &uv_raw, obs_uv, (size_t)2 * p->N)); TRYS(dev_alloc(p, &p->obs_u, (size_t)p->N)); TRYS(dev_alloc(p, &p->obs_v, (size_t)p->N));
+  hipLaunchKernelGGL(k_gather_uv, dim3((int)std::min<long>((p->N + 255) / 256, 2048)), dim3(256), 0, p->stream, (const double*)uv_raw, (const int*)p->order, p->N, p->obs_u, p->obs_v);
+  return CBA_OK;
+}
+
+static int upload_det_plan(cba_problem* p, const HostDetPlan& plan) {
+  unsigned char* dperm = nullptr; unsigned short* dcst = nullptr;
+  TRYS(dev_upload(p, &dperm, plan.perm)); TRYS(dev_upload(p, &dcst, plan.cst));
+  p->det_m = plan.det_m;
+  p->det = DetPlan{dperm, dcst};
+  return CBA_OK;
+}
+
+// the observations a second time, in (super-chunk, camera, point) order: copied on the device (k_cs_fill)
+static int upload_cs_plan(cba_problem* p, const HostCsPlan& plan) {
+  double *dcu = nullptr, *dcv = nullptr;
+  int *dcc = nullptr, *dcp = nullptr, *dso = nullptr, *dp0 = nullptr, *dnp = nullptr, *dperm = nullptr;
+  TRYS(dev_upload(p, &dperm, plan.cperm));
+  TRYS(dev_alloc(p, &dcu, (size_t)p->N)); TRYS(dev_alloc(p, &dcv, (size_t)p->N)); TRYS(dev_alloc(p, &dcc, (size_t)p->N)); TRYS(dev_alloc(p, &dcp, (size_t)p->N));
+  TRYS(dev_upload(p, &dso, plan.sc_obs)); TRYS(dev_upload(p, &dp0, plan.sc_p0)); TRYS(dev_upload(p, &dnp, plan.sc_np));
+  hipLaunchKernelGGL(k_cs_fill, dim3(plan.n_sc), dim3(256), 0, p->stream, (const int*)dperm, (const int*)dso, (const int*)dp0, (const double*)p->obs_u, (const double*)p->obs_v,
+                     (const int*)p->obs_cam, (const int*)p->obs_pt, dcu, dcv, dcc, dcp);
+  p->cs = CsPlan{dcu, dcv, dcc, dcp, dso, dp0, dnp, plan.n_sc, plan.pmax};
+  return CBA_OK;
+}
+
+static int upload_cameras(cba_problem* p, const double* cam_const, const CameraLayout& cams, const PointTables& tabs) {
+  if (p->n_heavy) {
+    TRYS(dev_upload(p, &p->heavy_pts, tabs.heavy)); TRYS(dev_upload(p, &p->heavy_frag, tabs.heavy_frag));
+    TRYS(dev_alloc(p, &p->heavy_W, (size_t)p->n_heavy * p->ncp * 3));
+  }
+  TRYS(dev_upload(p, &p->cam_const, cam_const, (size_t)p->C * 12));
+  TRYS(dev_upload(p, &p->cam_model, cams.model)); TRYS(dev_upload(p, &p->cam_np, cams.np)); TRYS(dev_upload(p, &p->cam_off, cams.off));
+  TRYS(dev_upload(p, &p->param_cam, cams.param_cam)); TRYS(dev_upload(p, &p->param_loc, cams.param_loc));
+  return CBA_OK;
+}
+
+// camera tables, the vectors of the iteration, the blocks of the build
+static int alloc_vectors(cba_problem* p) {
+  TRYS(dev_alloc(p, &p->tab, (size_t)p->C * CAMTAB_DOUBLES)); TRYS(dev_alloc(p, &p->tab_new, (size_t)p->C * CAMTAB_DOUBLES));
+  for (double** v : {&p->x0, &p->x, &p->x_new, &p->g, &p->s, &p->sinv, &p->v1, &p->v2, &p->sinv2}) TRYS(dev_zeros(p, v, (size_t)p->lay.total()));
+  for (double** v : {&p->sinv_state_c, &p->cam_diag, &p->cam_over1, &p->cam_over2, &p->lb_dev, &p->ub_dev, &p->sinv_state_c2, &p->cam_diag2})
+    TRYS(dev_zeros(p, v, (size_t)p->lay.ncp_pad));
+  TRYS(dev_zeros(p, &p->V, (size_t)6 * p->lay.Ppad));
+  const int ustride = (p->nct == 9) ? UPack<9>::STRIDE : UPack<6>::STRIDE;
+  TRYS(dev_alloc(p, &p->Upacked, (size_t)p->C * ustride + 128));  // + room for the scalars that ride with the blocks (exchange_at)
+  return CBA_OK;
+}
+
+// waits for the plan the handle starts with (the cheap one of a two-stage task) and makes it current
+static int install_first_plan(cba_problem* p, bool plan_timing) {
+  PlanTask& task = *p->plan_task;
+  const auto t_wait = std::chrono::steady_clock::now();
+  task.wait_stage(task.two_stage ? 1 : 2);
+  if (plan_timing) {
+    fprintf(stderr, "  plan: %s took %.3f s on its own threads, started before the uploads; waited %.3f s for it\n", task.two_stage ? "the cheap plan" : "dealt streams and codes",
+            task.two_stage ? task.seconds_cheap : task.seconds, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wait).count());
+    const Reg2Plan& made = task.two_stage ? task.cheap : task.plan;
+    fprintf(stderr, "  plan: its phases: point runs %.4f s, jobs %.4f s, concatenation %.4f s (%.0f MB)\n", made.seconds_runs, made.seconds_jobs, made.seconds_concat,
+            (made.obs.size() + made.codes.size()) * 4e-6);
+  }
+  if (task.two_stage ? task.rc_cheap : task.rc)
+    return fail(CBA_ERR_UNSUPPORTED, "a world point has more observations inside one camera-group tile than a chunk of the pair plan holds (%d records)",
+                (p->nct == 9) ? Reg3Cfg<9>::SCHUNK : Reg3Cfg<6>::SCHUNK);
+  const int rc = install_reg2_plan(p, task.two_stage ? task.cheap : task.plan, task.prm);
+  p->plan_is_cheap = task.two_stage || task.prm.cheap;
+  return rc;
+}
+
+// partial sums of the per-observation kernels, the reduced camera system and its factor, device scalars, the second set of build outputs
+static int alloc_solver_buffers(cba_problem* p) {
+  const int ncp = p->ncp, nct = p->nct;
+  const long tot = p->lay.total();
+  const int ustride = (nct == 9) ? UPack<9>::STRIDE : UPack<6>::STRIDE;
+  const long w_build = (long)p->C * ustride;
+  p->partial_width = w_build;
+  // (+ 1/8: the dealt plan of a two-stage handle has a few chunks — on small problems: workgroups — more or fewer than the cheap one)
+  p->partial_capacity = (size_t)std::max<long>((long)p->grid * w_build, (long)(p->tile_grid + p->tile_grid / 8 + 1) * std::max(p->tp.rep, 1) * p->tp.tile_elems);
+  TRYS(dev_alloc(p, &p->partial, p->partial_capacity));
+  // partial4: up to JV_ROWS rows of k_jv followed by up to CON_ROWS rows of k_con_jv (run_jv)
+  TRYS(dev_alloc(p, &p->partial4, (size_t)PARTIAL4_ROWS * 4)); TRYS(dev_alloc(p, &p->partial1, (size_t)2048)); TRYS(dev_alloc(p, &p->partial4b, (size_t)2048 * 4));
+  TRYS(dev_zeros(p, &p->Sacc, (size_t)ncp * ncp + (size_t)B_SLICES * p->lay.ncp_pad));  // + the rhs accumulator b, B_SLICES rows (k_reg_reduce)
+  TRYS(dev_alloc(p, &p->tri, (size_t)ncp * (ncp + 1) / 2 + p->lay.ncp_pad));
+  if (!p->eval_only) {
+    TRYS(dev_alloc(p, &p->red, (size_t)p->G * p->tp.tile_elems));
+    TRYS(dev_alloc(p, &p->Trec, (size_t)std::max<long>(p->N, 1) * ((nct == 9) ? SchurRec<9>::HREC : SchurRec<6>::HREC)));
+    TRYS(dev_alloc(p, &p->partial_b, (size_t)p->grid * p->lay.ncp_pad));
+  }
+  TRYS(dev_alloc(p, &p->S, (size_t)ncp * ncp)); p->ldw = (ncp + 3) & ~3;
+  if (p->want_chol_trace) TRYS(dev_alloc(p, &p->chol_trace, (size_t)((ncp + NB - 1) / NB + 2) * 8));
+  TRYS(dev_alloc(p, &p->Lbuf, (size_t)(ncp + 1) * p->ldw));
+  TRYS(dev_alloc(p, &p->Xinv, (size_t)((ncp + NB - 1) / NB + 1) * NB * NB));
+  TRYS(dev_zeros(p, &p->Tinv, (size_t)ncp * p->ldw));
+  TRYS(dev_alloc(p, &p->rhs, (size_t)p->lay.ncp_pad));
+  TRYS(dev_zeros(p, &p->scal, 64)); TRYS(dev_zeros(p, &p->flags, 4)); TRYS(dev_alloc(p, &p->xbuf, 128));
+  TRYS(dev_alloc(p, &p->fz, 8)); TRYS(dev_zeros(p, &p->V2, (size_t)6 * p->lay.Ppad)); TRYS(dev_zeros(p, &p->g2, (size_t)tot));
+  TRYS(dev_alloc(p, &p->U2, (size_t)p->C * ustride + 128));
+  return CBA_OK;
+}
+
+// pinned staging for layout conversion (h_vec), from the pool where it has one of a fitting size
+static int open_staging(cba_problem* p) {
+  const size_t tot = (size_t)p->lay.total();
+  {
+    std::lock_guard<std::mutex> lock(g_pool_mu);
+    DevicePool& pool = g_pool[p->device];
+    for (size_t i = 0; i < pool.staging.size(); ++i)
+      if (pool.staging[i].second >= tot && pool.staging[i].second <= 4 * tot + 4096) {
+        p->h_vec = pool.staging[i].first; p->h_vec_doubles = pool.staging[i].second;
+        pool.staging.erase(pool.staging.begin() + (long)i);
+        break;
+      }
+  }
+  HIPCHK(hipEventCreateWithFlags(&p->h_vec_sent, hipEventDisableTiming));
+  if (!p->h_vec) {
+    p->h_vec_doubles = tot;
+    HIPCHK(hipHostMalloc((void**)&p->h_vec, p->h_vec_doubles * sizeof(double), hipHostMallocDefault));
+  }
+  return CBA_OK;
+}
+static int device_synchronize() { HIPCHK(hipDeviceSynchronize()); return CBA_OK; }
+#undef TRYS
+
 extern "C" {
 
 int cba_create(const cba_problem_desc* d, const cba_options* opt, cba_problem** out) {
   if (!d || !out) return fail(CBA_ERR_INVALID, "cba_create: null argument");
   *out = nullptr;
-  if (d->n_cams <= 0 || d->n_points <= 0 || d->n_obs <= 0) return fail(CBA_ERR_INVALID, "cba_create: empty problem (cams=%d points=%d obs=%lld)", d->n_cams, d->n_points, (long long)d->n_obs);
-  if (d->n_obs >= (1LL << 31)) return fail(CBA_ERR_UNSUPPORTED, "cba_create: more than 2^31 observations");
-  if (!d->cam_n_params || !d->cam_model || !d->cam_const || !d->obs_cam || !d->obs_pt || !d->obs_uv) return fail(CBA_ERR_INVALID, "cba_create: null array");
-  if (d->loss < CBA_LOSS_LINEAR || d->loss > CBA_LOSS_ARCTAN) return fail(CBA_ERR_INVALID, "cba_create: unknown loss %d", d->loss);
-  if (d->loss != CBA_LOSS_LINEAR && !(d->f_scale > 0.0)) return fail(CBA_ERR_INVALID, "cba_create: f_scale must be positive");
+  if (const int rc = validate_problem_desc(fail, d)) return rc;
   const double t_enter = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -1136,128 +1309,44 @@ int cba_create(const cba_problem_desc* d, const cba_options* opt, cba_problem** 
     }
   }
 #endif
+  // a failure after the handle owns resources releases the handle, its arena chunks and the pooled stream
   int rc = CBA_OK;
-  auto bail = [&](int code) { cba_destroy(p); return code; };
-  // a HIP failure after the handle owns resources goes through bail(): the handle, its arena chunks and the pooled stream are released
-#define HIPBAIL(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return bail(fail(CBA_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__)); } while (0)
+#define TRY(e) do { rc = (e); if (rc) { cba_destroy(p); return rc; } } while (0)
+  const bool deterministic = opt && opt->deterministic;
 
-  // camera tables
-  std::vector<int> np(p->C), model(p->C), off(p->C);
-  int ncp = 0, nct = 6;
-  for (int c = 0; c < p->C; ++c) {
-    np[c] = d->cam_n_params[c]; model[c] = d->cam_model[c];
-    if (np[c] != 6 && np[c] != 9) return bail(fail(CBA_ERR_INVALID, "camera %d: n_params must be 6 or 9, got %d", c, np[c]));
-    if (model[c] != CBA_MODEL_PINHOLE_BC5 && model[c] != CBA_MODEL_FISHEYE4) return bail(fail(CBA_ERR_INVALID, "camera %d: unknown model %d", c, model[c]));
-    if (model[c] == CBA_MODEL_FISHEYE4 && np[c] != 6) return bail(fail(CBA_ERR_INVALID, "camera %d: fisheye cameras are always locked (6 params)", c));
-    if (!(d->cam_const[c * 12] > 0.0)) return bail(fail(CBA_ERR_INVALID, "camera %d: fx_initial must be positive", c));
-    off[c] = ncp; ncp += np[c];
-    if (np[c] == 9) nct = 9;
-  }
+  CameraLayout cams;
+  TRY(camera_layout(fail, d, cams));
+  const int ncp = cams.ncp, nct = cams.nct;
   p->ncp = ncp; p->nct = nct;
-  p->h_cam_off = off; p->h_cam_np = np;
-  p->lay.ncp = ncp; p->lay.ncp_pad = (ncp + 31) / 32 * 32;
+  p->h_cam_off = cams.off; p->h_cam_np = cams.np;
+  p->lay.ncp = ncp; p->lay.ncp_pad = cams.ncp_pad;
   p->lay.P = p->P; p->lay.Ppad = (p->P + 31) / 32 * 32;
-  std::vector<int> pcam(p->lay.ncp_pad, 0), ploc(p->lay.ncp_pad, 0);
-  for (int c = 0; c < p->C; ++c)
-    for (int r = 0; r < np[c]; ++r) { pcam[off[c] + r] = c; ploc[off[c] + r] = r; }
 
   const bool plan_timing = plan_timing_on();
   auto t_now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_mark = t_now();
   auto lap = [&](const char* what) { if (plan_timing) { const double t = t_now(); fprintf(stderr, "cba_create: %-28s %.6f s\n", what, t - t_mark); t_mark = t; } };
-  // plan: sort by point, chunk table
-  HostVec<int64_t> order(p->N), pstart((size_t)p->P + 1), cstart((size_t)p->N + 2);  // (written by cba_host_plan: order and pstart in full, cstart up to the chunk count)
-  // (cba_host_plan checks the point and camera indices of every observation)
-  int64_t nch = cba_host_plan(p->P, p->N, d->obs_pt, d->obs_cam, p->C, CHUNK, order.data(), pstart.data(), cstart.data());
-  if (nch < 0) return bail((int)nch);
-  p->n_chunks = (int)nch;
-  lap("sort by point, chunk table");
-  HostVec<int> hcam(p->N), hpt(p->N), hord(p->N);
-  std::vector<int> hps((size_t)p->P + 1), hcs((size_t)nch + 1);
-  {  // gather into the sorted order, by a few host threads (1M observations: 6 ms on one)
-    auto gather = [&](int64_t lo, int64_t hi) {
-      for (int64_t i = lo; i < hi; ++i) {
-        const int64_t o = order[i];
-        hcam[i] = d->obs_cam[o]; hpt[i] = d->obs_pt[o]; hord[i] = (int)o;  // (the coordinates are gathered on the device: k_gather_uv)
-      }
-    };
-    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, usable_cpus()), p->N / 65536));
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nth; ++t) pool.emplace_back(gather, p->N * t / nth, p->N * (t + 1) / nth);
-    gather(0, p->N / nth);
-    for (auto& th : pool) th.join();
+  // plan: sort by point, chunk table (cba_host_plan checks the point and camera indices of every observation)
+  SortedObs obs;
+  PointTables tabs;
+  {
+    HostVec<int64_t> order(p->N), pstart((size_t)p->P + 1), cstart((size_t)p->N + 2);  // (written by cba_host_plan: order and pstart in full, cstart up to the chunk count)
+    const int64_t nch = cba_host_plan(p->P, p->N, d->obs_pt, d->obs_cam, p->C, CHUNK, order.data(), pstart.data(), cstart.data());
+    if (nch < 0) TRY((int)nch);
+    p->n_chunks = (int)nch;
+    lap("sort by point, chunk table");
+    gather_sorted(p->N, d->obs_cam, d->obs_pt, order.data(), obs);
+    TRY(point_tables(fail, p->P, pstart.data(), nch, cstart.data(), obs.pt.data(), CHUNK, HEAVY_OBS, tabs));
   }
-  int maxk = 0;
-  for (int q = 0; q <= p->P; ++q) { hps[q] = (int)pstart[q]; if (q) maxk = std::max<int>(maxk, (int)(pstart[q] - pstart[q - 1])); }
-  for (int64_t q = 0; q <= nch; ++q) hcs[q] = (int)cstart[q];
-  p->max_obs_per_point = maxk;
-  // heavy points (static markers observed again in every frame): per-camera Schur sums instead of observation pairs
-  std::vector<int> heavy, heavy_frag;
-  for (int q = 0; q < p->P && maxk > HEAVY_OBS; ++q)
-    if (hps[q + 1] - hps[q] > HEAVY_OBS) { heavy.push_back(q); heavy_frag.push_back(hps[q + 1] - hps[q] > CHUNK ? 1 : 0); }
-  if ((long)heavy.size() > std::max<long>(64, p->P / 64)) {
-    // not a few static points but a dense problem (every point seen by > HEAVY_OBS cameras): the per-point workgroup of
-    // k_heavy_schur is the wrong tool; keep the pair plan (a point with more observations in one tile than a chunk holds is refused below)
-    if (maxk > CHUNK) return bail(fail(CBA_ERR_UNSUPPORTED, "%zu world points have more than %d observations (one has %d); at most %ld such points are supported",
-                                       heavy.size(), HEAVY_OBS, maxk, std::max<long>(64, p->P / 64)));
-    heavy.clear(); heavy_frag.clear();
-  }
-  p->n_heavy = (int)heavy.size();
-  p->h_heavy_pts = heavy;
-  // the Schur plan of the register kernels is dealt on its own thread from here on (declared after the vectors it reads: joined before they go)
+  p->max_obs_per_point = tabs.max_obs_per_point;
+  p->n_heavy = (int)tabs.heavy.size();
+  p->h_heavy_pts = tabs.heavy;
+  p->has_fragments = tabs.has_fragments;
   p->eval_only = opt && opt->evaluation_only != 0;
   choose_schur_groups(p);
-  // Two-stage plan: start with the CHEAP plan (a third of the host time, pair kernel 1.5-1.75x slower) and swap the dealt one in when its thread is
-  // done — the handle is ready 10 ms (cfg4) to half a second (cfg5) earlier and a solve of a handful of iterations may be over before the dealt plan
-  // would have been.  Default from kTwoStageObs observations on (below, the dealt plan is ready before the uploads are); CBA_PLAN=full / swap force
-  // one way, cba_plan_wait makes a handle final (benchmarks).  Not with fixed-order sums (the iteration the swap lands on would vary from run to run)
-  // nor with the profiling build (it wants the plan it profiles).
-  constexpr long kTwoStageObs = 500000;
-  const char* plan_env = std::getenv("CBA_PLAN");
-  bool plan_two_stage = p->N >= kTwoStageObs;
-  if (plan_env && std::strcmp(plan_env, "swap") == 0) plan_two_stage = true;
-  if (plan_env && (std::strcmp(plan_env, "full") == 0 || std::strcmp(plan_env, "cheap") == 0)) plan_two_stage = false;
-  if ((opt && opt->deterministic) || p->schur_clock) plan_two_stage = false;
-  if (!p->eval_only) {
-    Reg2Params prm = (nct == 9) ? reg2_params<9, Reg3Cfg<9>>(p) : reg2_params<6, Reg3Cfg<6>>(p);
-    if (plan_env) prm.cheap = std::strcmp(plan_env, "cheap") == 0;  // (measurements: the cheap plan for good)
-    p->plan_task = new PlanTask();  // owned by the handle: cba_destroy (also through bail) cancels and joins it while the arrays it reads are alive
-    {  // the workgroup budget of the pair kernel, fixed before the plan thread may want it (two stages: it binds the dealt plan itself)
-      const int cus0 = n_cus > 0 ? n_cus : 256;
-      const size_t tile_lds = (nct == 9) ? Reg3Cfg<9>::LDS_BYTES : Reg3Cfg<6>::LDS_BYTES;
-      const int per_cu = std::min(std::max<int>(1, (int)((160 * 1024) / tile_lds)), (nct == 9) ? RegCfg<9>::PER_CU : RegCfg<6>::PER_CU);  // LDS, register budget
-      const int mb0 = (opt && opt->max_blocks > 0) ? opt->max_blocks : 2 * cus0;
-      p->plan_max_blocks = std::min(cus0 * per_cu, std::max(mb0, cus0));  // no partial last round
-    }
-    p->plan_task->start(prm, hcam.data(), hps.data(), plan_two_stage, p);
-  }
+  if (!p->eval_only) start_plan_task(p, opt, n_cus, obs.cam.data(), tabs.pt_start.data());  // (before the uploads: it works beside them)
 
-  {
-    // one mapped host allocation for the three mailboxes: scalars (64 doubles), camera blocks (3 ncp + 8 doubles), flags (4 ints)
-    const size_t n_mail = 64 + ((size_t)3 * ncp + 8) + 2 + (size_t)4 * ncp;  // scalars | three camera blocks + sequence | flags | four camera blocks
-    {
-      std::lock_guard<std::mutex> lock(g_pool_mu);
-      DevicePool& pool = g_pool[dev];
-      if (!pool.streams.empty()) { p->stream = pool.streams.back(); pool.streams.pop_back(); }
-      for (size_t i = 0; i < pool.mail.size(); ++i)
-        if (pool.mail[i].second >= n_mail) {
-          p->h_scal = pool.mail[i].first; p->mail_doubles = pool.mail[i].second;
-          pool.mail.erase(pool.mail.begin() + (long)i);
-          break;
-        }
-    }
-    if (!p->stream) HIPBAIL(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    if (!p->h_scal) {
-      p->mail_doubles = std::max<size_t>(n_mail, 64 + 7 * 96 + 10);  // (room for 96 camera parameters: small rigs share mailboxes)
-      HIPBAIL(hipHostMalloc((void**)&p->h_scal, p->mail_doubles * sizeof(double), hipHostMallocMapped));
-    }
-    HIPBAIL(hipHostGetDevicePointer((void**)&p->d_hscal, p->h_scal, 0));
-    p->h_cam = p->h_scal + 64; p->d_hcam = p->d_hscal + 64;
-    p->h_flags = reinterpret_cast<int*>(p->h_cam + ((size_t)3 * ncp + 8)); p->d_hflags = reinterpret_cast<int*>(p->d_hcam + ((size_t)3 * ncp + 8));
-    p->h_bcam = p->h_cam + ((size_t)3 * ncp + 8) + 2; p->d_hbcam = p->d_hcam + ((size_t)3 * ncp + 8) + 2;
-  }
-  std::memset(p->h_scal, 0, (64 + ((size_t)3 * ncp + 8) + 2 + (size_t)4 * ncp) * sizeof(double));
-
+  TRY(open_stream_and_mailbox(p, MailLayout(ncp)));
   const int cus = n_cus > 0 ? n_cus : 256;
   p->cus = cus;
   const int max_blocks = (opt && opt->max_blocks > 0) ? opt->max_blocks : 2 * cus;  // two persistent workgroups per CU for the per-observation kernels
@@ -1266,242 +1355,43 @@ int cba_create(const cba_problem_desc* d, const cba_options* opt, cba_problem** 
   p->grid_backsub = std::max(1, std::min(p->n_chunks, 2 * cus));
   if (const char* e = std::getenv("CBA_BACKSUB_WGS")) p->grid_backsub = std::max(1, std::min(p->n_chunks, std::min(std::max(std::atoi(e), 1), 8) * cus));  // occupancy sweeps
 
-#define TRY(e) do { rc = (e); if (rc) return bail(rc); } while (0)
   lap("reorder on host");
-  upload_stage_acquire(p);
-  TRY(dev_upload(p, &p->obs_cam, hcam)); TRY(dev_upload(p, &p->obs_pt, hpt));
-  TRY(dev_upload(p, &p->order, hord)); TRY(dev_upload(p, &p->pt_start, hps)); TRY(dev_upload(p, &p->chunk_start, hcs));
-  {  // the caller's (u, v) pairs as they are, sorted on the device (the raw copy is scratch: v2's memory is not big enough, it stays in the arena)
-    double* uv_raw = nullptr;
-    TRY(dev_alloc(p, &uv_raw, (size_t)2 * p->N)); TRY(dev_alloc(p, &p->obs_u, (size_t)p->N)); TRY(dev_alloc(p, &p->obs_v, (size_t)p->N));
-    {
-      const size_t bytes = (size_t)2 * p->N * sizeof(double);
-      if (p->up_stage && bytes <= kUpStageMax && p->up_used + bytes <= p->up_cap) {
-        std::memcpy(p->up_stage + p->up_used, d->obs_uv, bytes);
-        HIPBAIL(hipMemcpyAsync(uv_raw, p->up_stage + p->up_used, bytes, hipMemcpyHostToDevice, p->stream));
-        p->up_used += (bytes + 63) & ~(size_t)63;
-      } else {
-        HIPBAIL(hipMemcpy(uv_raw, d->obs_uv, bytes, hipMemcpyHostToDevice));
-      }
-    }
-    hipLaunchKernelGGL(k_gather_uv, dim3((int)std::min<long>((p->N + 255) / 256, 2048)), dim3(256), 0, p->stream, (const double*)uv_raw, (const int*)p->order, p->N, p->obs_u, p->obs_v);
+  upload_stage_acquire(p);  // the uploads are staged asynchronous copies: one wait at the end
+  TRY(upload_observations(p, d->obs_uv, obs, tabs));
+  if (deterministic) {
+    HostDetPlan det;
+    TRY(det_plan(fail, p->C, nct, p->n_chunks, tabs.chunk_start.data(), obs.cam.data(), CHUNK, DET_ROUND, BLOCK, det));
+    TRY(upload_det_plan(p, det));
   }
-  if (opt && opt->deterministic) {
-    // fixed-order per-camera sums (k_build / k_tprep, det_round): per chunk the observation order by camera and the camera offsets
-    const int need = (p->C * DET_ROUND + BLOCK - 1) / BLOCK;
-    // tasks per thread of the fixed-order sums: 3, 5, 8 (<= 227 cameras) and, six-parameter cameras only, 16 (<= 455 by the task count; the LDS copy of
-    // the camera table next to k_tprep's staging and parking areas admits 385: configure_kernels reports the bytes beyond that).  Nine-parameter cameras stop at 227: six
-    // rounds of 16 running sums are 96 doubles per thread.
-    p->det_m = need <= 3 ? 3 : need <= 5 ? 5 : need <= 8 ? 8 : (nct == 6 && need <= 16) ? 16 : -1;
-    if (p->det_m < 0) return bail(fail(CBA_ERR_UNSUPPORTED, "deterministic sums support up to %d %s-parameter cameras, the problem has %d",
-                                       (nct == 6 ? 16 : 8) * BLOCK / DET_ROUND, nct == 6 ? "six" : "nine", p->C));
-    std::vector<unsigned char> perm((size_t)std::max<int64_t>(nch, 1) * CHUNK, 0);
-    std::vector<unsigned short> cst((size_t)std::max<int64_t>(nch, 1) * (p->C + 1), 0);
-    for (int64_t c = 0; c < nch; ++c) {
-      const int o0 = hcs[c], n = hcs[c + 1] - o0;
-      unsigned short* cs = &cst[(size_t)c * (p->C + 1)];
-      for (int k = 0; k < n; ++k) cs[hcam[o0 + k] + 1]++;
-      for (int q = 0; q < p->C; ++q) cs[q + 1] += cs[q];
-      std::vector<unsigned short> cur(cs, cs + p->C);
-      for (int k = 0; k < n; ++k) perm[(size_t)c * CHUNK + cur[hcam[o0 + k]]++] = (unsigned char)k;  // stable: observation order inside a camera
-    }
-    unsigned char* dperm = nullptr; unsigned short* dcst = nullptr;
-    TRY(dev_upload(p, &dperm, perm)); TRY(dev_upload(p, &dcst, cst));
-    p->det = DetPlan{dperm, dcst};
-  }
+  TRY(dev_upload(p, &p->chunk_pts, tabs.chunk_pts));
   {
-    std::vector<int> hcp((size_t)std::max<int64_t>(nch, 1) * 2, 0);
-    for (int64_t q = 0; q < nch; ++q) {
-      hcp[2 * q] = hpt[hcs[q]];
-      hcp[2 * q + 1] = hpt[hcs[q + 1] - 1] - hpt[hcs[q]] + 1;
-      if (hps[hpt[hcs[q]] + 1] - hps[hpt[hcs[q]]] > CHUNK) { hcp[2 * q + 1] = -1; p->has_fragments = true; }  // fragment of a point larger than a chunk
-    }
-    TRY(dev_upload(p, &p->chunk_pts, hcp));
-    // camera-sorted super-chunks for k_build_cs: consecutive chunks while observations <= CS_MAX_OBS and points <= CS_MAX_PTS, their observations
-    // a second time in (super-chunk, camera, point) order.  Not for the fixed-order sums (their own per-chunk order) nor with fragments of
-    // points larger than a chunk (those add to V / g by global atomics in k_build).
+    // Cap ~2000 observations for six-parameter cameras (two workgroups per CU), ~4000 for nine-parameter ones (54 values per camera change:
+    // longer runs pay; measured on cfg4 / cfg5: 59 / 72 / 120 us at 2048 / 3072 / 4096, 545 / 530 / 508 us).
     const char* cs_env = std::getenv("CBA_BUILD_CS");
-    bool cs_ok = !(opt && opt->deterministic) && !(cs_env && cs_env[0] == '0') && nch > 0;
-    for (int64_t q = 0; q < nch && cs_ok; ++q)
-      if (hcp[2 * q + 1] < 0 || hcp[2 * q + 1] > CS_MAX_PTS) cs_ok = false;
-    if (cs_ok) {
-      // Size: every workgroup of the launch (p->grid persistent ones) should get the same number of super-chunks — with 1.3 per workgroup a
-      // quarter of the pass is a tail.  Cap ~2000 observations for six-parameter cameras (two workgroups per CU), ~4000 for nine-parameter
-      // ones (54 values per camera change: longer runs pay; measured on cfg4 / cfg5: 59 / 72 / 120 us at 2048 / 3072 / 4096, 545 / 530 / 508 us).
-      const int64_t s_cap = (nct == 9) ? 4096 : 2048;
-      const int64_t wgs = std::max(1, p->grid);  // the persistent workgroups of the launch
-      int64_t rounds = std::max<int64_t>(1, (p->N + wgs * s_cap - 1) / (wgs * s_cap));
-      std::vector<int> sc_chunk, sc_obs, sc_p0, sc_np;
-      int pmax = 0;
-      // Round 6: the super-chunks are cut at the chunk boundaries nearest to k N / (rounds * workgroups), so that there are EXACTLY rounds * workgroups of
-      // them (fewer on a small problem) and workgroup w, which takes super-chunks w, w + grid, ..., gets `rounds` of about the same size.  Until round 5 they
-      // were filled greedily up to N / (rounds * workgroups) observations: whole chunks leave each a little short of that, cfg4 ended with 1143 super-chunks
-      // of 1750 observations for 1024 slots, and 119 of the 512 workgroups walked three of them while the others walked two (device stamps, round 6:
-      // workgroup lifetimes 42 / 53 / 63 us min / mean / max; cfg5 236 / 273 / 337).  A cut that would exceed the caps (observations, points of the LDS
-      // stage) asks for one more round.
-      for (int attempt = 0; attempt < 8; ++attempt, ++rounds) {
-        const int64_t n_target = std::min<int64_t>(std::max<int64_t>(1, wgs * rounds), nch);
-        sc_chunk.assign(1, 0); sc_obs.assign(1, 0); sc_p0.clear(); sc_np.clear();
-        pmax = 0;
-        bool fits = true;
-        int64_t q = 0;
-        for (int64_t k = 0; k < n_target && q < nch; ++k) {
-          const int64_t goal = (p->N * (k + 1) + n_target - 1) / n_target;  // observations behind super-chunk k
-          int64_t e = q + 1;
-          while (e < nch && (k + 1 == n_target || hcs[e + 1] <= goal || (hcs[e] < goal && goal - hcs[e] > hcs[e + 1] - goal))) ++e;  // nearest boundary
-          if (k + 1 == n_target) e = nch;
-          const int np_here = hcp[2 * (e - 1)] + hcp[2 * (e - 1) + 1] - hcp[2 * q];
-          if (hcs[e] - hcs[q] > s_cap + CHUNK || np_here > CS_MAX_PTS) { fits = false; break; }
-          sc_chunk.push_back((int)e); sc_obs.push_back(hcs[e]);
-          sc_p0.push_back(hcp[2 * q]); sc_np.push_back(np_here);
-          pmax = std::max(pmax, np_here);
-          q = e;
-        }
-        if (fits && q == nch) break;
-        if (attempt == 7) {  // (irregular point sizes: the greedy fill of rounds 3-5, which always fits)
-          const int64_t s_target = std::max<int64_t>(CHUNK, (p->N + wgs * rounds - 1) / (wgs * rounds));
-          sc_chunk.assign(1, 0); sc_obs.assign(1, 0); sc_p0.clear(); sc_np.clear();
-          pmax = 0;
-          for (int64_t qq = 0; qq < nch;) {
-            int64_t e = qq + 1;
-            while (e < nch && hcs[e + 1] - hcs[qq] <= s_target && hcp[2 * e] + hcp[2 * e + 1] - hcp[2 * qq] <= CS_MAX_PTS) ++e;
-            sc_chunk.push_back((int)e); sc_obs.push_back(hcs[e]);
-            sc_p0.push_back(hcp[2 * qq]); sc_np.push_back(hcp[2 * (e - 1)] + hcp[2 * (e - 1) + 1] - hcp[2 * qq]);
-            pmax = std::max(pmax, sc_np.back());
-            qq = e;
-          }
-        }
-      }
-      const int n_sc = (int)sc_p0.size();
-      HostVec<int> cperm(p->N);  // position in (super-chunk, camera, point) order -> sorted observation; the copy itself is made on the device (k_cs_fill)
-      auto fill = [&](int s0, int s1) {
-        std::vector<int> start((size_t)p->C + 1);
-        for (int sidx = s0; sidx < s1; ++sidx) {
-          const int o0 = sc_obs[sidx], o1 = sc_obs[sidx + 1];
-          std::fill(start.begin(), start.end(), 0);
-          for (int i = o0; i < o1; ++i) start[(size_t)hcam[i] + 1]++;
-          for (int c = 0; c < p->C; ++c) start[(size_t)c + 1] += start[c];
-          for (int i = o0; i < o1; ++i) {  // stable: point order inside a camera
-            cperm[o0 + start[hcam[i]]++] = i;
-          }
-        }
-      };
-      {
-        const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, usable_cpus()), n_sc / 64));
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nth; ++t) pool.emplace_back(fill, (int)((int64_t)n_sc * t / nth), (int)((int64_t)n_sc * (t + 1) / nth));
-        fill(0, (int)((int64_t)n_sc / nth));
-        for (auto& th : pool) th.join();
-      }
-      double *dcu = nullptr, *dcv = nullptr;
-      int *dcc = nullptr, *dcp = nullptr, *dso = nullptr, *dp0 = nullptr, *dnp = nullptr;
-      int* dperm = nullptr;
-      TRY(dev_upload(p, &dperm, cperm));
-      TRY(dev_alloc(p, &dcu, (size_t)p->N)); TRY(dev_alloc(p, &dcv, (size_t)p->N)); TRY(dev_alloc(p, &dcc, (size_t)p->N)); TRY(dev_alloc(p, &dcp, (size_t)p->N));
-      TRY(dev_upload(p, &dso, sc_obs)); TRY(dev_upload(p, &dp0, sc_p0)); TRY(dev_upload(p, &dnp, sc_np));
-      hipLaunchKernelGGL(k_cs_fill, dim3(n_sc), dim3(256), 0, p->stream, (const int*)dperm, (const int*)dso, (const int*)dp0, (const double*)p->obs_u, (const double*)p->obs_v,
-                         (const int*)p->obs_cam, (const int*)p->obs_pt, dcu, dcv, dcc, dcp);
-      p->cs = CsPlan{dcu, dcv, dcc, dcp, dso, dp0, dnp, n_sc, (pmax + 31) / 32 * 32};
-    }
+    HostCsPlan cs;
+    cs_plan(!(cs_env && cs_env[0] == '0'), deterministic, p->C, p->N, p->n_chunks, tabs.chunk_start.data(), tabs.chunk_pts.data(), obs.cam.data(), p->grid,
+            (nct == 9) ? 4096 : 2048, CHUNK, CS_MAX_PTS, cs);
+    if (cs.n_sc) TRY(upload_cs_plan(p, cs));
   }
-  if (p->n_heavy) {
-    TRY(dev_upload(p, &p->heavy_pts, heavy)); TRY(dev_upload(p, &p->heavy_frag, heavy_frag));
-    TRY(dev_alloc(p, &p->heavy_W, (size_t)p->n_heavy * ncp * 3));
-  }
-  std::vector<double> cc(d->cam_const, d->cam_const + (size_t)p->C * 12);
-  TRY(dev_upload(p, &p->cam_const, cc));
-  TRY(dev_upload(p, &p->cam_model, model)); TRY(dev_upload(p, &p->cam_np, np)); TRY(dev_upload(p, &p->cam_off, off));
-  TRY(dev_upload(p, &p->param_cam, pcam)); TRY(dev_upload(p, &p->param_loc, ploc));
+  TRY(upload_cameras(p, d->cam_const, cams, tabs));
   lap("upload observations");
-  TRY(dev_alloc(p, &p->tab, (size_t)p->C * CAMTAB_DOUBLES)); TRY(dev_alloc(p, &p->tab_new, (size_t)p->C * CAMTAB_DOUBLES));
-  const long tot = p->lay.total();
-  for (double** v : {&p->x0, &p->x, &p->x_new, &p->g, &p->s, &p->sinv, &p->v1, &p->v2, &p->sinv2}) {
-    TRY(dev_alloc(p, v, (size_t)tot));
-    if (hipMemsetAsync(*v, 0, tot * sizeof(double), p->stream) != hipSuccess) return bail(fail(CBA_ERR_HIP, "hipMemset failed"));
-  }
-  for (double** v : {&p->sinv_state_c, &p->cam_diag, &p->cam_over1, &p->cam_over2, &p->lb_dev, &p->ub_dev, &p->sinv_state_c2, &p->cam_diag2}) {
-    TRY(dev_alloc(p, v, (size_t)p->lay.ncp_pad));
-    if (hipMemsetAsync(*v, 0, (size_t)p->lay.ncp_pad * sizeof(double), p->stream) != hipSuccess) return bail(fail(CBA_ERR_HIP, "hipMemset failed"));
-  }
-  TRY(dev_alloc(p, &p->V, (size_t)6 * p->lay.Ppad));
-  HIPBAIL(hipMemsetAsync(p->V, 0, (size_t)6 * p->lay.Ppad * sizeof(double), p->stream));
-  const int ustride = (nct == 9) ? UPack<9>::STRIDE : UPack<6>::STRIDE;
-  TRY(dev_alloc(p, &p->Upacked, (size_t)p->C * ustride + 128));  // + room for the scalars that ride with the blocks (exchange_at)
+  TRY(alloc_vectors(p));
   lap("allocate vectors");
   if (nct == 9) TRY(configure_kernels<9>(p)); else TRY(configure_kernels<6>(p));
   lap("reorder, upload, allocate");
-  if (!p->eval_only) {
-    PlanTask& task = *p->plan_task;
-    const double t_wait = t_now();
-    task.wait_stage(task.two_stage ? 1 : 2);
-    if (plan_timing)
-      fprintf(stderr, "  plan: %s took %.3f s on its own threads, started before the uploads; waited %.3f s for it\n", task.two_stage ? "the cheap plan" : "dealt streams and codes",
-              task.two_stage ? task.seconds_cheap : task.seconds, t_now() - t_wait);
-    if (plan_timing) {
-      const Reg2Plan& made = task.two_stage ? task.cheap : task.plan;
-      fprintf(stderr, "  plan: its phases: point runs %.4f s, jobs %.4f s, concatenation %.4f s (%.0f MB)\n", made.seconds_runs, made.seconds_jobs, made.seconds_concat,
-              (made.obs.size() + made.codes.size()) * 4e-6);
-    }
-    if (task.two_stage ? task.rc_cheap : task.rc)
-      return bail(fail(CBA_ERR_UNSUPPORTED, "a world point has more observations inside one camera-group tile than a chunk of the pair plan holds (%d records)",
-                       (nct == 9) ? Reg3Cfg<9>::SCHUNK : Reg3Cfg<6>::SCHUNK));
-    rc = install_reg2_plan(p, task.two_stage ? task.cheap : task.plan, task.prm);
-    p->plan_is_cheap = task.two_stage || task.prm.cheap;
-    if (rc) return bail(rc);
-  }
+  if (!p->eval_only) TRY(install_first_plan(p, plan_timing));
   lap("Schur plan (streams, pairs, upload)");
-  const long w_build = (long)p->C * ustride;
-  p->partial_width = w_build;
-  // (+ 1/8: the dealt plan of a two-stage handle has a few chunks — on small problems: workgroups — more or fewer than the cheap one)
-  p->partial_capacity = (size_t)std::max<long>((long)p->grid * w_build, (long)(p->tile_grid + p->tile_grid / 8 + 1) * std::max(p->tp.rep, 1) * p->tp.tile_elems);
-  TRY(dev_alloc(p, &p->partial, p->partial_capacity));
-  // partial4: up to JV_ROWS rows of k_jv followed by up to CON_ROWS rows of k_con_jv (run_jv)
-  TRY(dev_alloc(p, &p->partial4, (size_t)PARTIAL4_ROWS * 4)); TRY(dev_alloc(p, &p->partial1, (size_t)2048)); TRY(dev_alloc(p, &p->partial4b, (size_t)2048 * 4));
-  TRY(dev_alloc(p, &p->Sacc, (size_t)ncp * ncp + (size_t)B_SLICES * p->lay.ncp_pad));  // + the rhs accumulator b, B_SLICES rows (k_reg_reduce)
-  TRY(dev_alloc(p, &p->tri, (size_t)ncp * (ncp + 1) / 2 + p->lay.ncp_pad));
-  if (!p->eval_only) {
-    TRY(dev_alloc(p, &p->red, (size_t)p->G * p->tp.tile_elems));
-    TRY(dev_alloc(p, &p->Trec, (size_t)std::max<long>(p->N, 1) * ((nct == 9) ? SchurRec<9>::HREC : SchurRec<6>::HREC)));
-    TRY(dev_alloc(p, &p->partial_b, (size_t)p->grid * p->lay.ncp_pad));
-  }
-  TRY(dev_alloc(p, &p->S, (size_t)ncp * ncp)); p->ldw = (ncp + 3) & ~3;
-  if (p->want_chol_trace) TRY(dev_alloc(p, &p->chol_trace, (size_t)((ncp + NB - 1) / NB + 2) * 8));
-  TRY(dev_alloc(p, &p->Lbuf, (size_t)(ncp + 1) * p->ldw));
-  TRY(dev_alloc(p, &p->Xinv, (size_t)((ncp + NB - 1) / NB + 1) * NB * NB));
-  TRY(dev_alloc(p, &p->Tinv, (size_t)ncp * p->ldw));
-  HIPBAIL(hipMemsetAsync(p->Tinv, 0, (size_t)ncp * p->ldw * sizeof(double), p->stream));
-  TRY(dev_alloc(p, &p->rhs, (size_t)p->lay.ncp_pad));
-  TRY(dev_alloc(p, &p->scal, 64)); TRY(dev_alloc(p, &p->flags, 4)); TRY(dev_alloc(p, &p->xbuf, 128));
-  TRY(dev_alloc(p, &p->fz, 8)); TRY(dev_alloc(p, &p->V2, (size_t)6 * p->lay.Ppad)); TRY(dev_alloc(p, &p->g2, (size_t)tot));
-  TRY(dev_alloc(p, &p->U2, (size_t)p->C * ustride + 128));
-  HIPBAIL(hipMemsetAsync(p->V2, 0, (size_t)6 * p->lay.Ppad * sizeof(double), p->stream)); HIPBAIL(hipMemsetAsync(p->g2, 0, (size_t)tot * sizeof(double), p->stream));
-  HIPBAIL(hipMemsetAsync(p->scal, 0, 64 * sizeof(double), p->stream));
-  HIPBAIL(hipMemsetAsync(p->flags, 0, 4 * sizeof(int), p->stream));
-  HIPBAIL(hipMemsetAsync(p->Sacc, 0, ((size_t)ncp * ncp + (size_t)B_SLICES * p->lay.ncp_pad) * sizeof(double), p->stream));
-#undef TRY
-  {
-    std::lock_guard<std::mutex> lock(g_pool_mu);
-    DevicePool& pool = g_pool[dev];
-    for (size_t i = 0; i < pool.staging.size(); ++i)
-      if (pool.staging[i].second >= (size_t)tot && pool.staging[i].second <= 4 * (size_t)tot + 4096) {
-        p->h_vec = pool.staging[i].first; p->h_vec_doubles = pool.staging[i].second;
-        pool.staging.erase(pool.staging.begin() + (long)i);
-        break;
-      }
-  }
-  HIPBAIL(hipEventCreateWithFlags(&p->h_vec_sent, hipEventDisableTiming));
-  if (!p->h_vec) {
-    p->h_vec_doubles = (size_t)tot;
-    HIPBAIL(hipHostMalloc((void**)&p->h_vec, p->h_vec_doubles * sizeof(double), hipHostMallocDefault));
-  }
+  TRY(alloc_solver_buffers(p));
+  TRY(open_staging(p));
   lap("solver buffers");
-  HIPBAIL(hipDeviceSynchronize());
+  TRY(device_synchronize());  // the staged uploads, the zeroing: the caller's arrays and the pinned buffer are free again
+#undef TRY
   upload_stage_release(p);
   lap("device synchronize");
   if (p->plan_task) {
     if (p->plan_task->two_stage) {  // the thread goes on dealing: it reads these two arrays
-      p->plan_task->hcam_keep = std::move(hcam);
-      p->plan_task->hps_keep = std::move(hps);
+      p->plan_task->hcam_keep = std::move(obs.cam);
+      p->plan_task->hps_keep = std::move(tabs.pt_start);
     } else {
       drop_plan_task(p);
     }
@@ -2269,96 +2159,38 @@ int cba_set_constraints(cba_problem* p, int32_t n_con, const int32_t* groups_a, 
   HIPCHK(hipSetDevice(p->device));
   const auto t_enter = std::chrono::steady_clock::now();
   auto lap_ms = [&](std::chrono::steady_clock::time_point since) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - since).count(); };
-  const int P = p->P;
-  for (long e = 0; e < (long)n_con * 4; ++e)
-    if (groups_a[e] < 0 || groups_a[e] >= P || groups_b[e] < 0 || groups_b[e] >= P)
-      return fail(CBA_ERR_INVALID, "cba_set_constraints: point index out of range in constraint %ld", e / 4);
-  // connected components of the constraint graph (union-find over world points)
-  std::vector<int> parent(P);
-  for (int q = 0; q < P; ++q) parent[q] = q;
-  auto find = [&](int a) { while (parent[a] != a) { parent[a] = parent[parent[a]]; a = parent[a]; } return a; };
-  for (int c = 0; c < n_con; ++c) {
-    const int r0 = find(groups_a[4 * c]);
-    for (int s = 0; s < 8; ++s) {
-      const int q = (s < 4) ? groups_a[4 * c + s] : groups_b[4 * c + s - 4];
-      const int r = find(q);
-      if (r != r0) parent[r] = r0;
-    }
-  }
-  std::vector<int> comp_of_root(P, -1), con_comp(n_con);
-  int K = 0;
-  for (int c = 0; c < n_con; ++c) {
-    const int r = find(groups_a[4 * c]);
-    if (comp_of_root[r] < 0) comp_of_root[r] = K++;
-    con_comp[c] = comp_of_root[r];
-  }
-  std::vector<int> comp_con(K + 1, 0), order(n_con);
-  for (int c = 0; c < n_con; ++c) comp_con[con_comp[c] + 1]++;
-  for (int k = 0; k < K; ++k) comp_con[k + 1] += comp_con[k];
-  {
-    std::vector<int> cur(comp_con.begin(), comp_con.end() - 1);
-    for (int c = 0; c < n_con; ++c) order[cur[con_comp[c]]++] = c;  // order[i] = caller's row of the i-th constraint here
-  }
-  std::vector<int> pt((size_t)n_con * 8), lp((size_t)n_con * 8), comp_pt(K + 1, 0), comp_pts;
-  std::vector<double> dist(n_con), wgt(n_con);
-  std::vector<long> comp_m(K + 1, 0);
-  std::vector<int> local(P, -1);
-  long max_m = 0;
-  int max_pts = 0;  // beyond CON_LDS_POINTS the per-point factors of a component live in global scratch (ConPlan::big)
-  for (int k = 0; k < K; ++k) {
-    const int first = (int)comp_pts.size();
-    for (int i = comp_con[k]; i < comp_con[k + 1]; ++i) {
-      const int c = order[i];
-      dist[i] = distances[c]; wgt[i] = weights[c];
-      for (int s = 0; s < 8; ++s) {
-        const int q = (s < 4) ? groups_a[4 * c + s] : groups_b[4 * c + s - 4];
-        if (local[q] < 0) { local[q] = (int)comp_pts.size() - first; comp_pts.push_back(q); }
-        pt[(size_t)i * 8 + s] = q; lp[(size_t)i * 8 + s] = local[q];
-      }
-    }
-    for (size_t j = first; j < comp_pts.size(); ++j) local[comp_pts[j]] = -1;
-    comp_pt[k + 1] = (int)comp_pts.size();
-    const long m = comp_con[k + 1] - comp_con[k];
-    comp_m[k + 1] = comp_m[k] + m * m;
-    max_m = std::max(max_m, m);
-    max_pts = std::max(max_pts, (int)comp_pts.size() - first);
-  }
-  // memory of the Woodbury correction: M (sum of m^2 over the components) and G (n_con x (ncp + 1)), doubles
-  if (comp_m[K] > (1L << 28) || (long)n_con * (p->ncp + 1) > (1L << 29))
-    return fail(CBA_ERR_UNSUPPORTED, "cba_set_constraints: the constraint rows need %.1f GB for the per-component matrices (sum of m^2 = %ld) and %.1f GB for their "
-                "camera coupling (%d rows x %d camera parameters); the limits are 2 GB and 4 GB - use fewer rows per object and frame (DESIGN.md 2.2)",
-                comp_m[K] * 8e-9, comp_m[K], (double)n_con * (p->ncp + 1) * 8e-9, n_con, p->ncp);
-  int rc;
-  // constrained points that no observation sees: the build writes neither their V nor their g_p, the back-substitution not their step
-  // (run_build_into zeroes their g_p before the rows add theirs, k_con_orphan_start forms their unconstrained step)
+  HostConPlan plan;
+  int rc = constraint_plan(fail, p->P, p->ncp, n_con, groups_a, groups_b, distances, weights, CON_LDS_POINTS, plan);
+  if (rc) return rc;
+  const int K = plan.n_comp, max_pts = plan.max_pts;
+  const long max_m = plan.max_m;
+  // (run_build_into zeroes the g_p of the orphans before the rows add theirs, k_con_orphan_start forms their unconstrained step)
   std::vector<int> orphan;
   {
-    std::vector<int> hps((size_t)P + 1);
+    std::vector<int> hps((size_t)p->P + 1);
     HIPCHK(hipStreamSynchronize(p->stream));
     HIPCHK(hipMemcpy(hps.data(), p->pt_start, hps.size() * sizeof(int), hipMemcpyDeviceToHost));
-    for (const int q : comp_pts)
-      if (hps[(size_t)q + 1] == hps[q]) orphan.push_back(q);
+    orphan = constraint_orphans(plan.comp_pts, hps.data());
   }
   const double ms_graph = lap_ms(t_enter);
   const auto t_up = std::chrono::steady_clock::now();
   upload_stage_acquire(p);
-  int *dpt = nullptr, *dlp = nullptr, *dorder = nullptr, *dcc = nullptr, *dcp = nullptr, *dcps = nullptr;
+  int *dpt = nullptr, *dlp = nullptr, *dorder = nullptr, *dcc = nullptr, *dcp = nullptr, *dcps = nullptr, *dorphan = nullptr;
   long* dcm = nullptr;
   double *ddist = nullptr, *dw = nullptr;
 #define TRYC(e) do { rc = (e); if (rc) return rc; } while (0)
-  TRYC(dev_upload(p, &dpt, pt)); TRYC(dev_upload(p, &dlp, lp)); TRYC(dev_upload(p, &dorder, order)); TRYC(dev_upload(p, &dcc, comp_con));
-  TRYC(dev_upload(p, &dcp, comp_pt)); TRYC(dev_upload(p, &dcps, comp_pts)); TRYC(dev_upload(p, &dcm, comp_m));
-  TRYC(dev_upload(p, &ddist, dist)); TRYC(dev_upload(p, &dw, wgt));
-  int* dorphan = nullptr;
+  TRYC(dev_upload(p, &dpt, plan.pt)); TRYC(dev_upload(p, &dlp, plan.lp)); TRYC(dev_upload(p, &dorder, plan.order)); TRYC(dev_upload(p, &dcc, plan.comp_con));
+  TRYC(dev_upload(p, &dcp, plan.comp_pt)); TRYC(dev_upload(p, &dcps, plan.comp_pts)); TRYC(dev_upload(p, &dcm, plan.comp_m));
+  TRYC(dev_upload(p, &ddist, plan.dist)); TRYC(dev_upload(p, &dw, plan.wgt));
   if (!orphan.empty()) TRYC(dev_upload(p, &dorphan, orphan));
   ConPlan cp{};
   cp.n_con = n_con; cp.n_comp = K; cp.pt = dpt; cp.lp = dlp; cp.dist = ddist; cp.weight = dw; cp.order = dorder;
   cp.comp_con = dcc; cp.comp_pt = dcp; cp.comp_pts = dcps; cp.comp_m = dcm;
   cp.heavy_pts = p->heavy_pts; cp.heavy_W = p->heavy_W; cp.n_heavy = p->n_heavy;
   TRYC(dev_alloc(p, &cp.f, (size_t)n_con)); TRYC(dev_alloc(p, &cp.u, (size_t)n_con * 3)); TRYC(dev_alloc(p, &cp.z, (size_t)n_con * 24));
-  TRYC(dev_alloc(p, &cp.M, (size_t)std::max<long>(comp_m[K], 1))); TRYC(dev_alloc(p, &cp.G, (size_t)n_con * (p->ncp + 1)));
+  TRYC(dev_alloc(p, &cp.M, (size_t)std::max<long>(plan.comp_m[K], 1))); TRYC(dev_alloc(p, &cp.G, (size_t)n_con * (p->ncp + 1)));
   TRYC(dev_alloc(p, &cp.cdiag, (size_t)3 * p->lay.Ppad)); TRYC(dev_alloc(p, &cp.w, (size_t)n_con));
-  if (max_pts > CON_LDS_POINTS) TRYC(dev_alloc(p, &cp.big, comp_pts.size() * 9));
+  if (plan.big) TRYC(dev_alloc(p, &cp.big, plan.comp_pts.size() * 9));
 #undef TRYC
   const double ms_upload = lap_ms(t_up);
   const auto t_attr = std::chrono::steady_clock::now();

@@ -45,6 +45,7 @@
 #include <type_traits>
 #include <sys/mman.h>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace cba {
@@ -121,6 +122,27 @@ inline void release_tracked(void* ptr, size_t bytes) {
   release(ptr, cap);
 }
 }  // namespace rawvec_detail
+
+// std::vector without value-initialisation of its elements: the threads that fill the observation-sized host arrays of cba_create are the first to
+// touch their pages (zero-filling ~70 bytes per observation on the calling thread was a third of "reorder on host")
+template <typename T>
+struct NoInitAlloc : std::allocator<T> {
+  template <typename U> struct rebind { using other = NoInitAlloc<U>; };
+  NoInitAlloc() = default;
+  template <typename U> NoInitAlloc(const NoInitAlloc<U>&) {}
+  template <typename U, typename... A> void construct(U* ptr, A&&... args) {
+    if constexpr (sizeof...(A) == 0) ::new ((void*)ptr) U; else ::new ((void*)ptr) U(std::forward<A>(args)...);
+  }
+  // large arrays from the pool of huge-page blocks the plan's arrays use (a handle's set-up was paying for the page faults of ~100 MB of
+  // freshly mapped host memory per call)
+  T* allocate(size_t n) {
+    void* ptr = rawvec_detail::acquire_tracked(n * sizeof(T));
+    if (!ptr) throw std::bad_alloc();
+    return static_cast<T*>(ptr);
+  }
+  void deallocate(T* ptr, size_t n) noexcept { rawvec_detail::release_tracked(ptr, n * sizeof(T)); }
+};
+template <typename T> using HostVec = std::vector<T, NoInitAlloc<T>>;
 
 template <typename T>
 struct RawVec {

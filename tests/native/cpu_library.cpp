@@ -139,19 +139,12 @@ int cba_device_count(void) { return 1; }  // "the host": this build exists for m
 int cba_create(const cba_problem_desc* d, const cba_options*, cba_problem** out) {
   if (!d || !out) return failf(CBA_ERR_INVALID, "cba_create: null argument");
   *out = nullptr;
-  if (d->n_cams <= 0 || d->n_points <= 0 || d->n_obs <= 0) return failf(CBA_ERR_INVALID, "cba_create: empty problem (cams=%d points=%d obs=%lld)", d->n_cams, d->n_points, (long long)d->n_obs);
+  if (const int rc = validate_problem_desc(failf, d)) return rc;  // the product's own checks (csrc/host_plan.h)
+  CameraLayout cams;
+  if (const int rc = camera_layout(failf, d, cams)) return rc;
   BaModel* md = new BaModel;
   md->C = d->n_cams; md->P = d->n_points; md->N = d->n_obs; md->loss = d->loss; md->f_scale = d->f_scale;
-  for (int c = 0; c < md->C; ++c) {
-    const int np = d->cam_n_params[c], mo = d->cam_model[c];
-    if ((np != 6 && np != 9) || (mo != CBA_MODEL_PINHOLE_BC5 && mo != CBA_MODEL_FISHEYE4) || (mo == CBA_MODEL_FISHEYE4 && np != 6) ||
-        !(d->cam_const[c * 12] > 0.0)) {
-      delete md;
-      return failf(CBA_ERR_INVALID, "camera %d: invalid description (n_params %d, model %d)", c, np, mo);
-    }
-    md->np.push_back(np); md->model.push_back(mo); md->off.push_back(md->ncp);
-    md->ncp += np;
-  }
+  md->np = cams.np; md->model = cams.model; md->off = cams.off; md->ncp = cams.ncp;
   md->n = md->ncp + 3 * md->P;
   md->cconst.assign(d->cam_const, d->cam_const + (size_t)md->C * 12);
   md->ocam.assign(d->obs_cam, d->obs_cam + md->N); md->opt.assign(d->obs_pt, d->obs_pt + md->N);
@@ -292,7 +285,7 @@ int cba_reduced_system(cba_problem* p, double* S, double* rhs) {
 
 int64_t cba_host_plan(int32_t n_points, int64_t n_obs, const int32_t* obs_pt, const int32_t* obs_cam, int32_t n_cams,
                       int32_t chunk_cap, int64_t* order_out, int64_t* pt_start_out, int64_t* chunk_start_out) {
-  return host_plan_impl([](int code, const char* fmt, auto... args) { return failf(code, fmt, args...); }, n_points, n_obs, obs_pt, obs_cam, n_cams, chunk_cap,
+  return host_plan_impl(failf, n_points, n_obs, obs_pt, obs_cam, n_cams, chunk_cap,
                         order_out, pt_start_out, chunk_start_out);
 }
 
