@@ -159,6 +159,62 @@ def _count_firing_cross_face_rows(world_df, distances) -> int:
     return sum(1 for d in cross if by_point.get((d.object_id_a, d.keypoint_id_a), set()) & by_point.get((d.object_id_b, d.keypoint_id_b), set()))
 
 
+MAX_PLAUSIBLE_INTRINSIC_RMSE = 0.005   # of max(width, height): 9.6 px at 1920; board corners are detected to a fraction of a pixel
+PLAUSIBLE_FOCAL_RANGE = (0.1, 10.0)    # of max(width, height): fields of view from ~6 to ~157 degrees
+
+
+def _plausible_intrinsics(cam, report) -> str | None:
+    """Why the calibrated intrinsics of ``cam`` are not taken over (None: they are).  A least-squares minimum can be a wrong one
+    (views that are not rigid, a mislabelled object): its reprojection error or its focal length then give it away."""
+    m = float(max(cam.size))
+    res = report.result
+    if not res.reprojection_error <= MAX_PLAUSIBLE_INTRINSIC_RMSE * m:
+        return f"reprojection RMSE {res.reprojection_error:.1f} px exceeds {MAX_PLAUSIBLE_INTRINSIC_RMSE * m:.1f} px"
+    for f in (res.camera_matrix[0, 0], res.camera_matrix[1, 1]):
+        if not PLAUSIBLE_FOCAL_RANGE[0] * m <= f <= PLAUSIBLE_FOCAL_RANGE[1] * m:
+            return f"focal length {f:.0f} px is outside [{PLAUSIBLE_FOCAL_RANGE[0] * m:.0f}, {PLAUSIBLE_FOCAL_RANGE[1] * m:.0f}]"
+    return None
+
+
+def _estimate_missing_intrinsics(image_points, cameras, _intr) -> dict:
+    """``estimate_intrinsics=True``: ``{cam_id: (matrix, distortions, error, grid_count)}`` of the non-ignored cameras without
+    intrinsics that the board views calibrate (whatever pose bootstrap follows: the views carry ``obj_loc``).  Without object
+    geometry there is nothing to calibrate against: the existing error of ``calibrate_extrinsics``.  A camera whose calibration
+    does not solve, or solves to an implausible minimum, is left without intrinsics (the caller then falls back to blind defaults)."""
+    from caliscope_amd.calibrate_intrinsics import calibrate_camera_array_intrinsics
+    from caliscope_amd.exceptions import CalibrationError
+
+    missing = sorted(c.cam_id for c in cameras.cameras.values() if not c.ignore and (c.matrix is None or c.distortions is None))
+    if not missing:
+        return {}
+    df = image_points.df
+    if bool(df[["obj_loc_x", "obj_loc_y", "obj_loc_z"]].isna().all().all()):
+        raise CalibrationError(
+            f"Epipolar bootstrap requires calibrated intrinsics, but cameras {missing} have none and fell back to "
+            f"blind defaults (f=width/2). Without object geometry there is no anchor to absorb the focal-length error: "
+            f"supply real intrinsics first, then re-run extrinsic calibration."
+        )
+    calibrated, reports = calibrate_camera_array_intrinsics(image_points, cameras, only_missing=True, _solver=_intr)
+    out = {}
+    for cam_id in missing:
+        if reports[cam_id].result is None:
+            logger.warning(f"Camera {cam_id}: intrinsic calibration from the board views did not solve; falling back to blind defaults")
+            continue
+        why = _plausible_intrinsics(calibrated.cameras[cam_id], reports[cam_id])
+        if why is not None:
+            logger.warning(f"Camera {cam_id}: intrinsic calibration from the board views rejected ({why}); falling back to blind defaults")
+            continue
+        cam = calibrated.cameras[cam_id]
+        out[cam_id] = (cam.matrix, cam.distortions, cam.error, cam.grid_count)
+    return out
+
+
+def _apply_estimated_intrinsics(cameras, estimated: dict) -> None:
+    for cam_id, (matrix, distortions, error, grid_count) in estimated.items():
+        cam = cameras.cameras[cam_id]
+        cam.matrix, cam.distortions, cam.error, cam.grid_count = matrix.copy(), distortions.copy(), error, grid_count
+
+
 def calibrate_extrinsics(
     image_points,
     camera_array,
@@ -169,16 +225,22 @@ def calibrate_extrinsics(
     cancellation_token=None,
     progress: Callable[[int, str], None] | None = None,
     estimate_poses: bool | str = False,
+    estimate_intrinsics: bool = False,
     _engine_factory=None,
     _triangulate=None,
     _pnp=None,
     _epi=None,
+    _intr=None,
 ) -> CalibrationRun:
     """The reference's entry point (``calibrate_extrinsics.py:44-261``, same arguments, progress marks and errors): blind
     intrinsics for uncalibrated cameras, the extraction guards, the bootstrap (triangulation on the device; with
     ``estimate_poses=True`` first the pose network from the board views, as the reference always does; ``"epipolar"`` / ``"auto"``
     as ``CaptureVolume.bootstrap`` takes them), static-marker guard, the three solver passes with the filter in between.
-    ``estimate_poses=False`` needs cameras that carry pose estimates."""
+    ``estimate_poses=False`` needs cameras that carry pose estimates.  ``estimate_intrinsics=True``: cameras without intrinsics are
+    calibrated from the session's board views on the device (``caliscope_amd/calibrate_intrinsics.py``, all of them in one call)
+    instead of receiving blind defaults, which also makes fisheye cameras without intrinsics usable; they are not listed in
+    ``synthesized_cam_ids``.  A camera whose calibration does not solve, or ends at an implausible minimum (reprojection RMSE above
+    0.5 % of the image size, focal length outside 0.1 ... 10 image sizes), falls back to the blind defaults and is listed."""
     from copy import deepcopy
 
     from caliscope_amd.exceptions import CalibrationError
@@ -194,6 +256,10 @@ def calibrate_extrinsics(
     report(5, "Preparing cameras")
     cameras = deepcopy(camera_array)
     synthesized = set()
+    estimated = {}
+    if estimate_intrinsics:
+        estimated = _estimate_missing_intrinsics(image_points, cameras, _intr)
+        _apply_estimated_intrinsics(cameras, estimated)
     for cam in cameras.cameras.values():
         if not cam.ignore and (cam.matrix is None or cam.distortions is None):
             synthesized.add(cam.cam_id)
@@ -241,6 +307,7 @@ def calibrate_extrinsics(
     if dropped:
         report(20, "Re-bootstrapping after dropping markers")
         cameras = deepcopy(camera_array)
+        _apply_estimated_intrinsics(cameras, estimated)
         for cam in cameras.cameras.values():
             if not cam.ignore and cam.cam_id in synthesized:
                 cam.synthesize_default_intrinsics()

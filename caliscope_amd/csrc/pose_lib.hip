@@ -26,9 +26,24 @@
 //                     are summed by a fixed LDS tree (wg_sum: the same order in tests/native/epipolar_harness.cpp), the
 //                     final flags, counts, conditioning, two-view points / reprojection errors.
 //
-// No host synchronisation inside a call beyond the final copy-back.  The workgroup kernels keep one LDS reduction buffer of
-// EPI_LIN_NSUM x REFINE_BLOCK doubles (46 KiB); the largest per-thread matrices are the 9 x 8 Householder factor (k_epi_hyp)
-// and the 11 x 11 DLT normal matrix (k_res_hyp), fully unrolled: ScratchSize 0 for every kernel.
+// The intrinsic calibration (arithmetic: intrinsic_math.h) is one call of two launches:
+//
+//   k_pose_pnp        as above, with the START intrinsics of every camera: the start pose of every view.
+//   k_intrinsics      one REFINE_BLOCK workgroup per camera, the whole Levenberg-Marquardt loop of intr_calibrate in one launch.
+//                     Threads stride over the camera's views (handed out sorted by corner count): a thread linearises a view,
+//                     eliminates its 6 x 6 pose block in registers and adds the view's part of the reduced NI x NI system to its
+//                     partial; wg_sum of the NI (NI + 1) / 2 + NI + 1 partials in a fixed order; every thread solves the reduced
+//                     system redundantly, back-substitutes its own views and evaluates their trial cost.  Per-view pose, trial
+//                     pose and the A_v^-1 terms live in a global work array (INTR_WORK doubles per view; each thread touches only
+//                     the rows of its own views, so no barrier guards them).  No atomics: bit-identical from run to run.
+//
+// No host synchronisation inside a call beyond the final copy-back.  The epipolar workgroup kernels keep one LDS reduction buffer
+// of EPI_LIN_NSUM x REFINE_BLOCK doubles (46 KiB), k_intrinsics one of INTR_NSUM_MAX x REFINE_BLOCK doubles (55 KiB).  The largest
+// per-thread matrices of the bootstrap kernels are the 9 x 8 Householder factor (k_epi_hyp) and the 11 x 11 DLT normal matrix
+// (k_res_hyp), fully unrolled: ScratchSize 0 for each of them.  k_intrinsics fills the register file (256 VGPRs + 228 AGPRs, no VGPR
+// spill) and has 24 bytes of scratch per lane: one store and two loads per corner in its fisheye instance (the stores of the lens's
+// `r > 1e-8` branches, merged into one through a selected address); its pinhole instance has none in the corner loops
+// (INTEGRATION.md section 3d).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +53,7 @@
 
 #include "../../include/caliscope_pose.h"
 #include "epipolar_math.h"
+#include "intrinsic_math.h"
 
 using namespace cba;
 
@@ -490,6 +506,88 @@ k_res_refine(long n_jobs, int n_hyp, int min_points, const long* __restrict__ st
   }
 }
 
+// ---- intrinsic calibration ---------------------------------------------------------------------------------------------------
+
+// The functor of intr_calibrate on the device: the workgroup's threads stride over the camera's views.
+template <int MODEL>
+struct IntrSumDev {
+  const long* views; long nv;
+  const long* view_start; const double* xy; const double* obj; int f32;
+  const double* pnp_pose; const int* pnp_status;
+  double* work; int* vstat; double* pose_out; double* view_rmse;
+  double (*red)[REFINE_BLOCK];
+  __device__ int n_of(long v) const { return (int)(view_start[v + 1] - view_start[v]); }
+  __device__ void screen(const double* in0, double* out) {
+    double acc[2] = {0.0, 0.0};
+    for (long q = threadIdx.x; q < nv; q += REFINE_BLOCK) {
+      const long v = views[q], a = view_start[v];
+      const int st = intr_view_screen<MODEL>(in0, obj + 3 * a, xy + 2 * a, n_of(v), f32, pnp_status[v], pnp_pose + 12 * v, work + v * INTR_WORK);
+      vstat[v] = st;
+      if (st == PNP_OK) { acc[0] += 1.0; acc[1] += (double)n_of(v); }
+    }
+    wg_sum<2>(acc, red, out);
+  }
+  __device__ void reduce(const double* in, double mu, double* out) {
+    double acc[IntrDim<MODEL>::NSUM];
+#pragma unroll
+    for (int k = 0; k < IntrDim<MODEL>::NSUM; ++k) acc[k] = 0.0;
+    for (long q = threadIdx.x; q < nv; q += REFINE_BLOCK) {
+      const long v = views[q], a = view_start[v];
+      if (vstat[v] == PNP_OK) intr_view_reduce<MODEL>(in, mu, obj + 3 * a, xy + 2 * a, n_of(v), f32, work + v * INTR_WORK, acc);
+    }
+    wg_sum<IntrDim<MODEL>::NSUM>(acc, red, out);
+  }
+  __device__ void trial(const double* in_new, const double* di, double* out) {
+    double acc[2] = {0.0, 0.0};
+    for (long q = threadIdx.x; q < nv; q += REFINE_BLOCK) {
+      const long v = views[q], a = view_start[v];
+      if (vstat[v] == PNP_OK) intr_view_trial<MODEL>(in_new, di, obj + 3 * a, xy + 2 * a, n_of(v), f32, work + v * INTR_WORK, acc);
+    }
+    wg_sum<2>(acc, red, out);
+  }
+  __device__ void accept() {
+    for (long q = threadIdx.x; q < nv; q += REFINE_BLOCK)
+      if (vstat[views[q]] == PNP_OK) intr_view_accept(work + views[q] * INTR_WORK);
+  }
+  __device__ void finish(const double* in, bool ok) {
+    for (long q = threadIdx.x; q < nv; q += REFINE_BLOCK) {
+      const long v = views[q], a = view_start[v];
+      intr_view_finish<MODEL>(in, ok, obj + 3 * a, xy + 2 * a, n_of(v), f32, vstat[v], work + v * INTR_WORK, pose_out + 12 * v, view_rmse + v);
+    }
+  }
+};
+
+__global__ void __launch_bounds__(REFINE_BLOCK)
+k_intrinsics(const int* __restrict__ cam_model, const double* __restrict__ cam_start, const long* __restrict__ cam_view_start,
+             const long* __restrict__ cam_views, const long* __restrict__ view_start, const double* __restrict__ obs_xy,
+             const double* __restrict__ obs_obj, int f32, int max_iter, const double* __restrict__ pnp_pose, const int* __restrict__ pnp_status,
+             double* __restrict__ work, double* __restrict__ intr_out, double* __restrict__ rmse_out, int* __restrict__ status_out,
+             int* __restrict__ iters_out, double* __restrict__ pose_out, double* __restrict__ view_rmse_out, int* __restrict__ view_status_out) {
+  __shared__ double red[INTR_NSUM_MAX][REFINE_BLOCK];
+  const int c = blockIdx.x;
+  const long vs = cam_view_start[c], nv = cam_view_start[c + 1] - vs;
+  double in9[9], rmse;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) in9[k] = cam_start[9 * c + k];
+  int st, it;
+  if (cam_model[c] == MODEL_FISHEYE4) {  // (uniform over the workgroup)
+    IntrSumDev<MODEL_FISHEYE4> sum{cam_views + vs, nv, view_start, obs_xy, obs_obj, f32, pnp_pose, pnp_status, work, view_status_out, pose_out,
+                                   view_rmse_out, red};
+    st = intr_calibrate<MODEL_FISHEYE4>(sum, in9, max_iter, &rmse, &it);
+  } else {
+    IntrSumDev<MODEL_PINHOLE_BC5> sum{cam_views + vs, nv, view_start, obs_xy, obs_obj, f32, pnp_pose, pnp_status, work, view_status_out, pose_out,
+                                      view_rmse_out, red};
+    st = intr_calibrate<MODEL_PINHOLE_BC5>(sum, in9, max_iter, &rmse, &it);
+  }
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) intr_out[9 * c + k] = in9[k];
+    rmse_out[c] = rmse;
+    status_out[c] = st;
+    iters_out[c] = it;
+  }
+}
+
 int err(int code, const std::string& msg) { return cba_set_error(code, msg.c_str()); }  // returns `code`
 
 // device buffers of one call, freed on every path
@@ -746,6 +844,98 @@ int cba_pose_resect_batch(const cba_pose_resect_desc* d, int32_t device, double*
   if (e == hipSuccess) e = hipMemcpy(n_inliers_out, dninl, (size_t)n_jobs * sizeof(int64_t), hipMemcpyDeviceToHost);
   if (e == hipSuccess && winner_out) e = hipMemcpy(winner_out, dwin, (size_t)n_jobs * sizeof(int32_t), hipMemcpyDeviceToHost);
   if (e == hipSuccess && n > 0) e = hipMemcpy(err_out, derr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  return CBA_OK;
+}
+
+int cba_pose_intrinsics_batch(const cba_intrinsics_desc* d, int32_t device, double* intr_out, double* rmse_out, int32_t* status_out,
+                              int32_t* iters_out, double* pose_out, double* view_rmse_out, int32_t* view_status_out) {
+  const char* what = "cba_pose_intrinsics_batch";
+  if (!d || !intr_out || !rmse_out || !status_out) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
+  if (d->n_cams <= 0 || !d->cam_model || !d->cam_size || d->n_views < 0 || d->max_iter < 0 ||
+      (d->n_views > 0 && (!d->view_start || !d->view_cam || !d->obs_xy || !d->obs_obj || !pose_out || !view_rmse_out || !view_status_out)))
+    return err(CBA_ERR_INVALID, std::string(what) + ": bad descriptor");
+  // bounds of everything the kernels index, checked on the host before anything reaches the device
+  for (int32_t c = 0; c < d->n_cams; ++c) {
+    if (d->cam_model[c] != 0 && d->cam_model[c] != 1) return err(CBA_ERR_INVALID, std::string(what) + ": unknown camera model");
+    const bool own = d->cam_start && d->cam_start[9 * c] > 0.0;
+    if (!own && (!(d->cam_size[2 * c] > 0.0) || !(d->cam_size[2 * c + 1] > 0.0) || !pnp_finite(d->cam_size[2 * c]) || !pnp_finite(d->cam_size[2 * c + 1])))
+      return err(CBA_ERR_INVALID, std::string(what) + ": camera " + std::to_string(c) + " has no image size");
+    if (own)
+      for (int k = 0; k < 9; ++k)
+        if (!pnp_finite(d->cam_start[9 * c + k]) || (k == 1 && !(d->cam_start[9 * c + 1] > 0.0)))
+          return err(CBA_ERR_INVALID, std::string(what) + ": bad start intrinsics of camera " + std::to_string(c));
+  }
+  const int64_t n_views = d->n_views;
+  if (n_views > 0 && d->view_start[0] != 0) return err(CBA_ERR_INVALID, std::string(what) + ": view_start[0] != 0");
+  for (int64_t v = 0; v < n_views; ++v) {
+    if (d->view_start[v + 1] < d->view_start[v]) return err(CBA_ERR_INVALID, std::string(what) + ": view_start decreases at view " + std::to_string(v));
+    if (d->view_start[v + 1] - d->view_start[v] > (int64_t)1 << 30) return err(CBA_ERR_INVALID, std::string(what) + ": view too large");
+    if (d->view_cam[v] < 0 || d->view_cam[v] >= d->n_cams) return err(CBA_ERR_INVALID, std::string(what) + ": view_cam out of range at view " + std::to_string(v));
+  }
+  int rc = select_device(device, what);
+  if (rc) return rc;
+  const int32_t n_cams = d->n_cams;
+  const int64_t n_obs = n_views > 0 ? d->view_start[n_views] : 0;
+  std::vector<double> start((size_t)n_cams * 9);
+  for (int32_t c = 0; c < n_cams; ++c) {
+    if (d->cam_start && d->cam_start[9 * c] > 0.0) std::copy(d->cam_start + 9 * c, d->cam_start + 9 * c + 9, start.begin() + 9 * c);
+    else intr_start(d->cam_model[c], d->cam_size[2 * c], d->cam_size[2 * c + 1], &start[9 * c]);
+  }
+  // views by corner count (stable), then the list of each camera in that order
+  std::vector<int64_t> order(n_views), cam_view_start(n_cams + 1, 0), cam_views(n_views), fill(n_cams, 0);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {
+    return d->view_start[x + 1] - d->view_start[x] < d->view_start[y + 1] - d->view_start[y];
+  });
+  for (int64_t v = 0; v < n_views; ++v) ++cam_view_start[d->view_cam[v] + 1];
+  for (int32_t c = 0; c < n_cams; ++c) cam_view_start[c + 1] += cam_view_start[c];
+  for (int64_t v : order) {
+    const int32_t c = d->view_cam[v];
+    cam_views[cam_view_start[c] + fill[c]++] = v;
+  }
+  Buffers buf;
+  void *dord = nullptr, *dvs = nullptr, *dvc = nullptr, *dmodel = nullptr, *dstart = nullptr, *dxy = nullptr, *dobj = nullptr, *dund = nullptr,
+       *dpnp = nullptr, *dprm = nullptr, *dpst = nullptr, *dcvs = nullptr, *dcv = nullptr, *dwork = nullptr, *dintr = nullptr, *drmse = nullptr,
+       *dst = nullptr, *dit = nullptr, *dpose = nullptr, *dvr = nullptr, *dvst = nullptr;
+  rc = buf.up(order.data(), (size_t)n_views * sizeof(int64_t), &dord);
+  if (!rc) rc = buf.up(d->view_start, (size_t)(n_views > 0 ? n_views + 1 : 0) * sizeof(int64_t), &dvs);
+  if (!rc) rc = buf.up(d->view_cam, (size_t)n_views * sizeof(int32_t), &dvc);
+  if (!rc) rc = buf.up(d->cam_model, (size_t)n_cams * sizeof(int32_t), &dmodel);
+  if (!rc) rc = buf.up(start.data(), (size_t)n_cams * 9 * sizeof(double), &dstart);
+  if (!rc) rc = buf.up(d->obs_xy, (size_t)n_obs * 2 * sizeof(double), &dxy);
+  if (!rc) rc = buf.up(d->obs_obj, (size_t)n_obs * 3 * sizeof(double), &dobj);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_obs * 2 * sizeof(double), &dund);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_views * 12 * sizeof(double), &dpnp);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_views * sizeof(double), &dprm);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_views * sizeof(int32_t), &dpst);
+  if (!rc) rc = buf.up(cam_view_start.data(), (size_t)(n_cams + 1) * sizeof(int64_t), &dcvs);
+  if (!rc) rc = buf.up(cam_views.data(), (size_t)n_views * sizeof(int64_t), &dcv);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_views * INTR_WORK * sizeof(double), &dwork);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * 9 * sizeof(double), &dintr);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(double), &drmse);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &dst);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &dit);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_views * 12 * sizeof(double), &dpose);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_views * sizeof(double), &dvr);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_views * sizeof(int32_t), &dvst);
+  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
+  const int f32 = d->float32_io ? 1 : 0;
+  if (n_views > 0)
+    hipLaunchKernelGGL(k_pose_pnp, dim3((unsigned)((n_views + POSE_BLOCK - 1) / POSE_BLOCK)), dim3(POSE_BLOCK), 0, 0, (long)n_views, (const long*)dord,
+                       (const long*)dvs, (const int*)dvc, (const int*)dmodel, (const double*)dstart, (const double*)dxy, (const double*)dobj,
+                       (int)INTR_MIN_POINTS, f32, (double*)dund, (double*)dpnp, (double*)dprm, (int*)dpst);
+  hipLaunchKernelGGL(k_intrinsics, dim3((unsigned)n_cams), dim3(REFINE_BLOCK), 0, 0, (const int*)dmodel, (const double*)dstart, (const long*)dcvs,
+                     (const long*)dcv, (const long*)dvs, (const double*)dxy, (const double*)dobj, f32, (int)d->max_iter, (const double*)dpnp,
+                     (const int*)dpst, (double*)dwork, (double*)dintr, (double*)drmse, (int*)dst, (int*)dit, (double*)dpose, (double*)dvr, (int*)dvst);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(intr_out, dintr, (size_t)n_cams * 9 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(rmse_out, drmse, (size_t)n_cams * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(status_out, dst, (size_t)n_cams * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && iters_out) e = hipMemcpy(iters_out, dit, (size_t)n_cams * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && n_views > 0) e = hipMemcpy(pose_out, dpose, (size_t)n_views * 12 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && n_views > 0) e = hipMemcpy(view_rmse_out, dvr, (size_t)n_views * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && n_views > 0) e = hipMemcpy(view_status_out, dvst, (size_t)n_views * sizeof(int32_t), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
   return CBA_OK;
 }

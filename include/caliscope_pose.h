@@ -108,6 +108,38 @@ typedef struct {
 int cba_pose_resect_batch(const cba_pose_resect_desc* d, int32_t device, double* pose_out, int32_t* status_out, int64_t* n_inliers_out,
                           int32_t* winner_out, double* err_out);
 
+/* Intrinsic calibration of every camera of a rig from its board views (caliscope_amd/calibrate_intrinsics.py).  Statuses per
+ * camera: 0 OK, 1 too few (fewer than 3 usable views, or fewer residuals than unknowns), 2 failed (no solvable system at the
+ * start, non-finite result).  View statuses are cba_pnp_status. */
+enum cba_intr_status { CBA_INTR_OK = 0, CBA_INTR_TOO_FEW = 1, CBA_INTR_FAILED = 2 };
+
+typedef struct {
+  int32_t n_cams;
+  const int32_t* cam_model;  /* [n_cams] 0 pinhole (fx fy cx cy k1 k2 p1 p2 k3), 1 fisheye (fx fy cx cy k1..k4) */
+  const double* cam_size;    /* [n_cams][2] image width, height in pixels */
+  const double* cam_start;   /* optional [n_cams][9] start intrinsics fx fy cx cy d0..d4; a row whose fx is not > 0 (and a null
+                                pointer) takes the default: pinhole f = max(w, h), c = ((w-1)/2, (h-1)/2); fisheye f = max(w, h) / pi,
+                                c = (w/2 - 0.5, h/2 - 0.5); zero coefficients */
+  int64_t n_views;
+  const int64_t* view_start; /* [n_views + 1], non-decreasing, view_start[0] = 0: views in CSR form as cba_pose_pnp_desc */
+  const int32_t* view_cam;   /* [n_views] */
+  const double* obs_xy;      /* [n_obs][2] pixels */
+  const double* obs_obj;     /* [n_obs][3] object points; a NaN z is read as 0 */
+  int32_t float32_io;        /* round pixels and object points to float32 (the reference's astype(np.float32)) */
+  int32_t max_iter;          /* linearisations per camera; 0: the default (100) */
+} cba_intrinsics_desc;
+
+/* One workgroup per camera: start poses by PnP on the pixels undistorted with the start intrinsics (views with fewer than 4
+ * corners, a failed PnP, a fisheye corner beyond 1.5 rad or a corner behind the camera at the start are left out), then
+ * Levenberg-Marquardt over the intrinsics and one pose per view on the pixel reprojection error, skew fixed at 0.
+ * intr_out[n_cams][9]: fx fy cx cy d0..d4 (the start values when the status is not OK); rmse_out[n_cams]: sqrt(sum |e|^2 /
+ * n_corners) in pixels over the views used (0 when not OK); iters_out (optional): linearisations; pose_out[n_views][12]: R
+ * row-major then t of every view (I, 0 for a view left out; for a camera that is not OK the pose at which its solve stopped, the
+ * PnP start pose when it never stepped); view_rmse_out[n_views]: the same RMSE per view (0 for a view left
+ * out); view_status_out[n_views].  Sums run in a fixed order: the result does not change from run to run. */
+int cba_pose_intrinsics_batch(const cba_intrinsics_desc* d, int32_t device, double* intr_out, double* rmse_out, int32_t* status_out,
+                              int32_t* iters_out, double* pose_out, double* view_rmse_out, int32_t* view_status_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,154 @@
+"""Intrinsic calibration on the MI355X: cba_pose_intrinsics_batch against the g++ build of the same header, run-to-run identity,
+and calibrate_extrinsics(estimate_intrinsics=True) on sessions whose cameras carry neither intrinsics nor poses."""
+import numpy as np
+import pytest
+
+from caliscope_amd.calibrate_intrinsics import DeviceIntrinsics
+from caliscope_amd.cameras import CameraArray, CameraData
+from caliscope_amd.exceptions import CalibrationError
+from tests import intrinsic_scenes as S
+from tests.intrinsic_native import HarnessIntrinsics
+from tests.test_intrinsic_calibration import NOISY_TOL, _with_views
+
+pytestmark = pytest.mark.gpu
+
+# cba_pose_pnp_batch against its CPU build holds atol = 1e-12 * max(1, |value|) (tests/test_pose_bootstrap_gpu.py), and so does this
+# solve.  Why no wider bound is needed: both builds run the same source without contraction and sum in the same order, so they differ
+# only through sin / cos / atan in the last bit, i.e. ~1 ulp of a ~2e3 px coordinate (2e-13 px) per residual.  The minimum does not
+# depend on the start, and the Gauss-Newton polish ends with steps of ~1e-14 relative (g++ build, these scenes), so each build sits
+# within ~1e-14 relative of its own fixed point; two roundings of the same cost have fixed points ~7e-13 apart on values of ~1e3
+# (the g++ build against scipy on the noise-free scenes of tests/test_intrinsic_calibration.py), i.e. 1e-3 of this bound.
+# DEVICE_FACTOR is the place for a factor MEASURED on a GPU run (with the observed value beside it); it may never take the bound
+# beyond the harness-against-yardstick tolerance.  The test prints the observed figure.
+# Observed on an MI355X: 0.019 ... 0.065 of the base bound over the six cases (iteration counts differ by one on some cameras):
+# no widening needed.
+DEVICE_FACTOR = 1.0
+BASE_ATOL = 1e-12
+
+
+def _scene_sets():
+    noisy = [S.camera_scene(seed, fisheye=False, noise=0.3) for seed in range(3)] + [S.camera_scene(seed, fisheye=True, noise=0.3) for seed in range(3)]
+    # (fisheye at f = 430 and 860 as in the CPU test: at 860 the 1.5 rad screen leaves a view out)
+    noisy += [S.camera_scene(7, fisheye=True, noise=0.3, intr=S.fisheye_truth(430.0)[0], dist=S.FISHEYE_D),
+              S.camera_scene(8, fisheye=True, noise=0.3, intr=S.fisheye_truth(860.0)[0], dist=S.FISHEYE_D)]
+    base = S.camera_scene(21, n_views=12, noise=0.3)
+    X, uv, rv, t = base.views[0]
+    Xl, uvl, rvl, tl = base.views[1]
+    row = np.flatnonzero(np.isclose(Xl[:, 1], Xl[0, 1]))
+    edges = [_with_views(base, base.views[:2]),                                                        # 2 views: TOO_FEW
+             _with_views(base, [(X[:3], uv[:3], rv, t), (Xl[row], uvl[row], rvl, tl)] + base.views[2:]),  # a short and a collinear view
+             _with_views(base, [(X, np.column_stack([uv[:, 0], np.full(len(uv), 500.0)]), rv, t) for X, uv, rv, t in base.views]),  # one image row
+             _with_views(base, []),                                                                    # no view at all
+             S.camera_scene(22, n_views=8, fisheye=True, noise=0.3)]
+    return {"noisy": noisy, "rig": S.rig_scenes(), "edges": edges}
+
+
+@pytest.mark.parametrize("name", ["noisy", "rig", "edges"])
+@pytest.mark.parametrize("f32", [True, False])
+def test_device_matches_cpu_build(name, f32, capsys):
+    """Statuses and view statuses equal; intrinsics and RMSE of every solved camera, poses and RMSE of its views with >= 8 corners
+    within BASE_ATOL * DEVICE_FACTOR * max(1, |value|); cameras that did not solve return the start values bit for bit."""
+    scenes = _scene_sets()[name]
+    args = S.pack(scenes)
+    model, size, vstart, vcam, xy, obj = args
+    dev = DeviceIntrinsics().intrinsics_batch(model, size, None, vstart, vcam, xy, obj, f32, 0)
+    cpu = HarnessIntrinsics().intrinsics_batch(model, size, None, vstart, vcam, xy, obj, f32, 0)
+    intr_d, rmse_d, st_d, it_d, pose_d, vr_d, vst_d = dev
+    intr_c, rmse_c, st_c, it_c, pose_c, vr_c, vst_c = cpu
+    assert np.array_equal(st_d, st_c) and np.array_equal(vst_d, vst_c)
+    assert all(np.isfinite(a).all() for a in (intr_d, rmse_d, pose_d, vr_d))
+    bad = st_c != 0
+    assert np.array_equal(intr_d[bad], intr_c[bad]) and (rmse_d[bad] == 0).all()  # start values, bit for bit
+    ok = ~bad
+    n_corners = np.diff(vstart)
+    well = (vst_c == 0) & ok[vcam] & (n_corners >= 8)
+    scale = lambda ref: BASE_ATOL * np.maximum(1.0, np.abs(ref))
+    worst = 0.0
+    for d, c in ((intr_d[ok], intr_c[ok]), (rmse_d[ok], rmse_c[ok]), (pose_d[well], pose_c[well]), (vr_d[well], vr_c[well])):
+        if c.size:
+            worst = max(worst, float((np.abs(d - c) / scale(c)).max()))
+    with capsys.disabled():
+        print(f"device vs g++ build [{name}, float32_io={f32}]: largest difference {worst:.3g} x 1e-12 max(1, |value|); iterations "
+              f"{it_d.tolist()} / {it_c.tolist()}")
+    assert BASE_ATOL * DEVICE_FACTOR * 2000.0 <= NOISY_TOL  # never beyond the harness-against-yardstick tolerance (values up to ~2e3)
+    assert worst <= DEVICE_FACTOR, worst
+    left = (vst_c != 0)
+    eye = np.concatenate([np.eye(3).ravel(), np.zeros(3)])
+    assert np.array_equal(pose_d[left], np.tile(eye, (int(left.sum()), 1))) and (vr_d[left] == 0).all()
+
+
+@pytest.mark.parametrize("f32", [True, False])
+def test_nan_z_is_read_as_zero_on_the_device(f32):
+    """The C ABI promises "a NaN z is read as 0" and the Python layer never sends one (it replaces NaN on the host): a direct call
+    with NaN obj z equals the call with z = 0 bit for bit, on the device as on the g++ build, and the two builds agree on statuses."""
+    sc = S.camera_scene(23, n_views=15, noise=0.3)
+    fe = S.camera_scene(24, n_views=10, fisheye=True, noise=0.3)
+    model, size, vstart, vcam, xy, obj = S.pack([sc, fe])
+    assert (obj[:, 2] == 0).all()
+    nan = obj.copy()
+    nan[:, 2] = np.nan
+    zero = DeviceIntrinsics().intrinsics_batch(model, size, None, vstart, vcam, xy, obj, f32, 0)
+    dev = DeviceIntrinsics().intrinsics_batch(model, size, None, vstart, vcam, xy, nan, f32, 0)
+    cpu = HarnessIntrinsics().intrinsics_batch(model, size, None, vstart, vcam, xy, nan, f32, 0)
+    assert all(np.array_equal(x, y) for x, y in zip(dev, zero))
+    assert (dev[2] == 0).all() and (dev[6] == 0).all() and np.array_equal(dev[2], cpu[2]) and np.array_equal(dev[6], cpu[6])
+    assert all(np.isfinite(a).all() for a in (dev[0], dev[1], dev[4], dev[5]))
+    np.testing.assert_allclose(dev[0], cpu[0], rtol=0, atol=BASE_ATOL * DEVICE_FACTOR * max(1.0, np.abs(cpu[0]).max()))
+
+
+def test_two_runs_are_bit_identical():
+    scenes = S.rig_scenes()
+    model, size, vstart, vcam, xy, obj = S.pack(scenes)
+    a = DeviceIntrinsics().intrinsics_batch(model, size, None, vstart, vcam, xy, obj, True, 0)
+    b = DeviceIntrinsics().intrinsics_batch(model, size, None, vstart, vcam, xy, obj, True, 0)
+    assert all(np.array_equal(x, y) for x, y in zip(a, b))
+    assert (a[2] == 0).all()
+
+
+def _bare(cams):
+    return CameraArray({c: CameraData(cam_id=c, size=cam.size, fisheye=cam.fisheye) for c, cam in cams.cameras.items()})
+
+
+def test_ring_session_without_intrinsics_and_poses(capsys):
+    """A ring board session with ALL intrinsics and poses removed: calibrate_extrinsics(estimate_intrinsics=True, estimate_poses=True)
+    converges, every focal length within 1 % of the truth (the reference's bar, SURVEY.md section 4 test_intrinsic_recovery), and
+    the final RMSE is not above the parent behaviour's on the same session (blind f = width / 2 defaults refined by the bundle
+    adjustment).  The RMSE of a run started from the TRUE intrinsics is the floor and is printed.  Measured on an MI355X: 0.5554 px
+    (estimated), 4.0069 px (blind), 0.5514 px (floor); calibrated focal lengths 1386.3 ... 1398.3 for a true 1394.6."""
+    from caliscope_amd.calibrate_extrinsics import calibrate_extrinsics
+
+    ip, cams = S.ring_board_session()
+    est = calibrate_extrinsics(ip, _bare(cams), None, estimate_intrinsics=True, estimate_poses=True)
+    blind = calibrate_extrinsics(ip, _bare(cams), None, estimate_intrinsics=False, estimate_poses=True)
+    known = CameraArray({c: CameraData(cam_id=c, size=cam.size, matrix=cam.matrix.copy(), distortions=cam.distortions.copy()) for c, cam in cams.cameras.items()})
+    floor = calibrate_extrinsics(ip, known, None, estimate_poses=True)
+    r_est, r_blind, r_floor = (r.capture_volume.reprojection_report.overall_rmse for r in (est, blind, floor))
+    with capsys.disabled():
+        print(f"ring session final RMSE: estimated intrinsics {r_est:.6f} px, blind defaults {r_blind:.6f} px, true intrinsics (floor) {r_floor:.6f} px")
+        for e in est.intrinsic_estimates:
+            print(f"  cam {e.cam_id}: f calibrated {e.f_initial:.2f}, after bundle adjustment {e.f_recovered:.2f}, truth {cams.cameras[e.cam_id].matrix[0, 0]:.2f}")
+    assert est.capture_volume.optimization_status.converged
+    assert est.synthesized_cam_ids == frozenset() and blind.synthesized_cam_ids == frozenset(cams.cameras)
+    assert set(est.capture_volume.camera_array.posed_cameras) == set(cams.cameras)
+    for c, cam in est.capture_volume.camera_array.cameras.items():
+        f_true = cams.cameras[c].matrix[0, 0]
+        assert abs(cam.matrix[0, 0] - f_true) <= 0.01 * f_true and abs(cam.matrix[1, 1] - f_true) <= 0.01 * f_true, (c, cam.matrix)
+    assert len(est.intrinsic_estimates) == len(cams.cameras)
+    for e in est.intrinsic_estimates:
+        assert abs(e.f_initial - cams.cameras[e.cam_id].matrix[0, 0]) <= 0.01 * cams.cameras[e.cam_id].matrix[0, 0]
+    assert r_est <= r_blind, (r_est, r_blind)
+
+
+def test_fisheye_camera_without_intrinsics_goes_through():
+    from caliscope_amd.calibrate_extrinsics import calibrate_extrinsics
+
+    ip, cams = S.ring_board_session(fisheye_cam=2)
+    with pytest.raises(CalibrationError, match="fisheye"):
+        calibrate_extrinsics(ip, _bare(cams), None, estimate_poses=True)
+    run = calibrate_extrinsics(ip, _bare(cams), None, estimate_intrinsics=True, estimate_poses=True)
+    vol = run.capture_volume
+    assert run.synthesized_cam_ids == frozenset() and vol.optimization_status is not None and vol.optimization_status.converged
+    assert set(vol.camera_array.posed_cameras) == set(cams.cameras)
+    fish = vol.camera_array.cameras[2]
+    assert fish.fisheye and len(np.asarray(fish.distortions).ravel()) == 4
+    assert abs(fish.matrix[0, 0] - 700.0) <= 0.01 * 700.0, fish.matrix
