@@ -100,6 +100,17 @@ class TriangulateDesc(C.Structure):
     ]
 
 
+class ScaleDesc(C.Structure):
+    _fields_ = [
+        ("n_world", C.c_int64),
+        ("world_xyz", c_double_p),
+        ("n_groups", C.c_int64),
+        ("group_start", c_int64_p),
+        ("ent_world", c_int64_p),
+        ("ent_obj", c_double_p),
+    ]
+
+
 # name -> (restype, argtypes): every symbol include/caliscope_ba.h declares
 SIGNATURES = {
     "cba_create": (C.c_int, [C.POINTER(ProblemDesc), C.POINTER(Options), C.POINTER(C.c_void_p)]),
@@ -146,6 +157,7 @@ SIGNATURES = {
     "cba_enable_timers": (C.c_int, [C.c_void_p, C.c_int32]),
     "cba_host_plan": (C.c_int64, [C.c_int32, C.c_int64, c_int32_p, c_int32_p, C.c_int32, C.c_int32, c_int64_p, c_int64_p, c_int64_p]),
     "cba_triangulate": (C.c_int, [C.POINTER(TriangulateDesc), C.c_int32, c_double_p, c_double_p]),
+    "cba_scale_errors": (C.c_int, [C.POINTER(ScaleDesc), C.c_int32, c_double_p]),
     "cba_trim": (C.c_int64, []),
     "cba_last_error": (C.c_char_p, []),
     "cba_set_error": (C.c_int, [C.c_int32, C.c_char_p]),

@@ -10,6 +10,10 @@ Same public surface as the reference's ``core/capture_volume.py`` for the BA pat
 * ``CaptureVolume.reprojection_report``     <- ``:150-235`` (``overall_rmse = sqrt(mean(ex^2+ey^2))`` in pixels)
 * ``CaptureVolume.filter_by_percentile_error`` (the stage between the product's passes,
   ``calibrate_extrinsics.py:244``)
+* ``CaptureVolume.compute_volumetric_scale_accuracy``  <- ``:755-831`` (grouping by sorts and prefix sums, all pairwise distances
+  in one device call, ``cba_scale_errors``)
+* ``CaptureVolume.align_to_object`` / ``rotate`` / ``translate`` / ``scaled`` / ``oriented`` / ``grounded`` / ``centered``
+  <- ``:833-1329`` (the frame and the metric scale of a solved volume; host work, O(points))
 
 The marshalling of DataFrames into flat arrays follows ``:346-358`` but is vectorised (the reference uses a
 Python list comprehension over every observation, and a Python loop to build ``img_to_obj_map``).  The solver
@@ -21,6 +25,8 @@ call goes through :func:`caliscope_amd.least_squares.least_squares`, i.e. the MI
 from __future__ import annotations
 
 import logging
+import warnings
+from collections import Counter
 from copy import deepcopy
 from dataclasses import dataclass, field
 from functools import cached_property
@@ -36,6 +42,10 @@ from caliscope_amd.least_squares import least_squares
 from caliscope_amd.constraints import ConstraintSet, ConstraintViolation, DistanceConstraint, RigidityReport
 from caliscope_amd.point_data import STATIC_SYNC_INDEX, ImagePoints, WorldPoints
 from caliscope_amd.engine import STATUS_REASONS
+from caliscope_amd.alignment import SimilarityTransform, apply_similarity_transform, estimate_similarity_transform
+from caliscope_amd.coordinate_frame import world_basis_from_up_and_forward
+from caliscope_amd.scale_accuracy import DeviceScaleErrors, VolumetricScaleReport, frame_errors_from_stats
+from caliscope_amd.scale_cues import CameraDistance, DepthObservation, SegmentLength
 
 logger = logging.getLogger(__name__)
 
@@ -549,6 +559,308 @@ class CaptureVolume:
             raise ValueError(f"min_per_camera must be >= 1, got {min_per_camera}")
         thresholds = {cam_id: float(max_pixels) for cam_id in self.camera_array.posed_cameras}
         return self._filter_by_reprojection_thresholds(thresholds, min_per_camera, _engine_factory)
+
+    # -- scale accuracy (reference :755-831) ---------------------------------------------------------------
+    def _scale_groups(self):
+        """The (frame, object) groups of the scale report as flat arrays, or None when no observation carries object geometry:
+        ``(sync[g], object_id[g], n_cameras[g], n_corners[g], group_start[g + 1], ent_world[e], ent_obj[e, 3])``, groups sorted by
+        (sync_index, object_id), only those with at least three joined rows.  What the reference does per group with a filter of the
+        whole world table and a merge is here one sort of the image rows, one of the world keys and a binary search per distinct
+        (group, keypoint)."""
+        idf, wdf = self.image_points._df, self.world_points._df
+        loc = [idf[c].to_numpy(dtype=np.float64) for c in ("obj_loc_x", "obj_loc_y", "obj_loc_z")]
+        rows = np.flatnonzero(~(np.isnan(loc[0]) | np.isnan(loc[1])))
+        if rows.size == 0:
+            return None
+        sync, obj, kp, cam = (idf[c].to_numpy()[rows] for c in ("sync_index", "object_id", "keypoint_id", "cam_id"))
+        order = np.lexsort((obj, sync))  # stable: the rows of a group keep their table order
+        rows, sync, obj, kp, cam = rows[order], sync[order], obj[order], kp[order], cam[order]
+        new = np.r_[True, (sync[1:] != sync[:-1]) | (obj[1:] != obj[:-1])]
+        gid = np.cumsum(new) - 1
+        g_sync, g_obj = sync[new], obj[new]
+        n_groups = len(g_sync)
+        # distinct cameras of a group (all its rows, whether or not their keypoint has a world point)
+        by_cam = np.lexsort((cam, gid))
+        c2, g2 = cam[by_cam], gid[by_cam]
+        n_cams = np.bincount(g2[np.r_[True, (c2[1:] != c2[:-1]) | (g2[1:] != g2[:-1])]], minlength=n_groups)
+        # the object point of a keypoint: the group's first row of it
+        by_kp = np.lexsort((kp, gid))
+        k3, g3 = kp[by_kp], gid[by_kp]
+        first = np.r_[True, (k3[1:] != k3[:-1]) | (g3[1:] != g3[:-1])]
+        u_row, u_gid, u_kp = rows[by_kp][first], g3[first], k3[first]
+        u_loc = np.column_stack([a[u_row] for a in loc])
+        static_ids = self.constraints.static_object_ids if self.constraints else frozenset()
+        g_world_sync = np.where(np.isin(g_obj, list(static_ids)), STATIC_SYNC_INDEX, g_sync) if static_ids else g_sync
+        # world rows of every (group, keypoint): the three keys as ranks folded into one, duplicates of a world key all kept
+        w_keys = [wdf[c].to_numpy() for c in _KEY]
+        u_keys = [g_world_sync[u_gid], g_obj[u_gid], u_kp]
+        w_fold, u_fold = np.zeros(len(wdf), dtype=np.int64), np.zeros(len(u_gid), dtype=np.int64)
+        for w, u in zip(w_keys, u_keys):
+            values = np.unique(np.concatenate([w, u]))
+            w_fold = w_fold * len(values) + np.searchsorted(values, w)
+            u_fold = u_fold * len(values) + np.searchsorted(values, u)
+        w_order = np.argsort(w_fold, kind="stable")
+        w_sorted = w_fold[w_order]
+        lo, hi = np.searchsorted(w_sorted, u_fold, "left"), np.searchsorted(w_sorted, u_fold, "right")
+        count = hi - lo
+        e_u = np.repeat(np.arange(len(u_fold)), count)
+        e_world = w_order[lo[e_u] + (np.arange(len(e_u)) - np.repeat(np.cumsum(count) - count, count))]
+        e_gid, e_loc = u_gid[e_u], u_loc[e_u]
+        # z: 0 for a group whose joined rows have none (a planar board), else rows without one are dropped
+        z_missing = np.isnan(e_loc[:, 2])
+        all_missing = np.bincount(e_gid, weights=z_missing, minlength=n_groups) == np.bincount(e_gid, minlength=n_groups)
+        e_loc[all_missing[e_gid] & z_missing, 2] = 0.0
+        keep = ~np.isnan(e_loc[:, 2])
+        e_world, e_gid, e_loc = e_world[keep], e_gid[keep], e_loc[keep]
+        size = np.bincount(e_gid, minlength=n_groups)
+        good = size >= 3
+        keep = good[e_gid]
+        e_world, e_gid, e_loc = e_world[keep], e_gid[keep], e_loc[keep]
+        in_table_order = np.lexsort((e_world, e_gid))  # (the left table of the reference's merge is the world table)
+        group_start = np.concatenate([[0], np.cumsum(size[good])]).astype(np.int64)
+        return (g_sync[good], g_obj[good], n_cams[good], size[good], group_start, e_world[in_table_order].astype(np.int64),
+                np.ascontiguousarray(e_loc[in_table_order]))
+
+    def compute_volumetric_scale_accuracy(self, *, _solver=None) -> VolumetricScaleReport:
+        """Per (frame, rigid object): all pairwise distances of the triangulated corners against the object's own geometry
+        (``obj_loc``), in millimetres; distances between different objects are never formed.  An empty report when no observation
+        carries object geometry.  The distances are one device call (``cba_scale_errors``); ``_solver`` replaces it (tests)."""
+        static_ids = self.constraints.static_object_ids if self.constraints else frozenset()
+        groups = self._scale_groups()
+        if groups is None:
+            return VolumetricScaleReport.empty()
+        g_sync, g_obj, n_cams, n_corners, group_start, ent_world, ent_obj = groups
+        if len(g_sync) == 0:
+            return VolumetricScaleReport(frame_errors=(), static_object_ids=static_ids)
+        backend = _solver or DeviceScaleErrors()
+        stats = backend.scale_errors(self.world_points.points, group_start, ent_world, ent_obj)
+        return VolumetricScaleReport(frame_errors=frame_errors_from_stats(stats, g_sync, g_obj, n_corners, n_cams), static_object_ids=static_ids)
+
+    # -- the frame and the scale of a solved volume (reference :833-1329) ------------------------------------
+    def _transformed(self, transform: SimilarityTransform) -> "CaptureVolume":
+        """This volume in another frame: new cameras and points, the same observations, constraints and optimisation status.
+        Coordinates change, keys do not: the observation -> world-point map and the constraint rows are handed on."""
+        cameras, points = apply_similarity_transform(self.camera_array, self.world_points, transform)
+        out = CaptureVolume(camera_array=cameras, image_points=self.image_points, world_points=points, constraints=self.constraints,
+                            _optimization_status=self._optimization_status, _known_map=self.img_to_obj_map)
+        kept = getattr(self, "_constraint_cache", None)
+        if kept is not None:
+            object.__setattr__(out, "_constraint_cache", kept)
+        return out
+
+    def align_to_object(self, sync_index: int | None, object_id: int | None = None) -> "CaptureVolume":
+        """Move the volume into the frame of one rigid object at one sync index (a rigid fit of its triangulated corners to their
+        ``obj_loc``): origin and axes are the object's own.  ``object_id`` may be left out when the frame shows one object only.
+        ``sync_index=None`` is for a static marker, whose world points sit at ``STATIC_SYNC_INDEX``."""
+        idf, wdf = self.image_points._df, self.world_points._df
+        static_ids = self.constraints.static_object_ids if self.constraints else frozenset()
+        if sync_index is None:
+            if object_id is None:
+                raise ValueError("sync_index=None requires an explicit object_id")
+            if object_id not in static_ids:
+                raise ValueError(f"sync_index=None is only valid for static markers, but object_id={object_id} is not static")
+        img_rows = np.flatnonzero(idf["sync_index"].to_numpy() == sync_index) if sync_index is not None else np.arange(len(idf))
+        if img_rows.size == 0:
+            raise ValueError(f"No image observations at sync_index={sync_index}")
+        img_obj = idf["object_id"].to_numpy()[img_rows]
+        if object_id is None:
+            present = pd.unique(img_obj)
+            if len(present) > 1:
+                raise ValueError(f"Multiple markers present at sync_index {sync_index}; specify object_id (available: {sorted(present)})")
+            object_id = int(present[0])
+        world_si = STATIC_SYNC_INDEX if object_id in static_ids else (sync_index if sync_index is not None else 0)
+        img_rows = img_rows[img_obj == object_id]
+        world_rows = np.flatnonzero((wdf["sync_index"].to_numpy() == world_si) & (wdf["object_id"].to_numpy() == object_id))
+        if img_rows.size == 0:
+            raise ValueError(f"No image observations for object_id={object_id} at sync_index={sync_index}")
+        if world_rows.size == 0:
+            raise ValueError(f"No world points for object_id={object_id} at sync_index={world_si}")
+        # object point of a keypoint: its first observation; world rows in table order, each with the object point of its keypoint
+        kp_img = idf["keypoint_id"].to_numpy()[img_rows]
+        kps, first = np.unique(kp_img, return_index=True)
+        kp_world = wdf["keypoint_id"].to_numpy()[world_rows]
+        at = np.minimum(np.searchsorted(kps, kp_world), len(kps) - 1)
+        hit = kps[at] == kp_world
+        src_rows, loc_rows = world_rows[hit], img_rows[first[at[hit]]]
+        target = np.column_stack([idf[c].to_numpy(dtype=np.float64)[loc_rows] for c in ("obj_loc_x", "obj_loc_y", "obj_loc_z")]).reshape(-1, 3)
+        if np.isnan(target[:, 2]).all():
+            logger.info("obj_loc_z is all NaN, assuming planar board with z=0")
+            target[:, 2] = 0.0
+        valid = ~np.isnan(target).any(axis=1)
+        if int(valid.sum()) < 3:
+            raise ValueError(f"Need at least 3 valid correspondences for object_id={object_id}, got {int(valid.sum())}")
+        source = self.world_points.points[src_rows[valid]]
+        transform = estimate_similarity_transform(source, target[valid], rigid=True)
+        logger.info(f"Estimated alignment: scale={transform.scale:.6f}, translation={transform.translation}, "
+                    f"rotation_det={np.linalg.det(transform.rotation):.6f}")
+        return self._transformed(transform)
+
+    def rotate(self, axis: str, angle_degrees: float) -> "CaptureVolume":
+        """Rotate the coordinate system about "x", "y" or "z" (right-hand rule, degrees); cameras and points move together."""
+        if axis not in ("x", "y", "z"):
+            raise ValueError(f"Invalid axis '{axis}'. Must be 'x', 'y', or 'z'")
+        angle = np.radians(angle_degrees)
+        c, s = np.cos(angle), np.sin(angle)
+        k = "xyz".index(axis)
+        a, b = (k + 1) % 3, (k + 2) % 3
+        rotation = np.eye(3, dtype=np.float64)
+        rotation[a, a], rotation[a, b], rotation[b, a], rotation[b, b] = c, -s, s, c
+        return self._transformed(SimilarityTransform(rotation=rotation, translation=np.zeros(3, dtype=np.float64), scale=1.0))
+
+    def translate(self, x: float = 0.0, y: float = 0.0, z: float = 0.0) -> "CaptureVolume":
+        """Shift the coordinate system by (x, y, z) metres: added to every world point, the cameras carried along."""
+        return self._transformed(SimilarityTransform(rotation=np.eye(3, dtype=np.float64), translation=np.array([x, y, z], dtype=np.float64), scale=1.0))
+
+    def _anchor_cam_id(self) -> int:
+        """The lowest posed cam_id: the camera that fixes yaw and the XY origin of a volume without a board."""
+        posed = self.camera_array.posed_cameras
+        if not posed:
+            raise ValueError("No posed cameras; cannot anchor a shape-only volume.")
+        return min(posed)
+
+    def _camera_center(self, cam_id: int) -> np.ndarray:
+        cam = self.camera_array.cameras[cam_id]
+        if cam.rotation is None or cam.translation is None:
+            raise ValueError(f"Camera {cam_id} has no pose; cannot compute its center.")
+        return -cam.rotation.T @ cam.translation
+
+    def scaled(self, *cues) -> "CaptureVolume":
+        """Uniform scale from one or more metric cues (:mod:`caliscope_amd.scale_cues`).  One cue sets the scale exactly; several
+        are combined by least squares weighted with their ``sigma_m``, and two whose implied scales differ by more than 2 sigma
+        raise a ``warnings.warn``.  ``CameraDistance`` and ``SegmentLength`` are strict (``ValueError`` for a camera or keypoint that
+        is not there); ``DepthObservation`` cues that cannot be resolved are skipped with one aggregated warning.  No cue, or none
+        that resolves, is a ``ValueError``."""
+        if not cues:
+            raise ValueError("scaled() requires at least one cue; got none.")
+        depth_cues = [cue for cue in cues if isinstance(cue, DepthObservation)]
+        depth_outcome = iter(self._compile_depth_cues(depth_cues))
+        compiled, skipped = [], []
+        for cue in cues:
+            if isinstance(cue, DepthObservation):
+                outcome = next(depth_outcome)
+                (skipped if isinstance(outcome, str) else compiled).append(outcome)
+            else:
+                compiled.append(self._compile_cue(cue))
+        if skipped:
+            breakdown = ", ".join(f"{count} {reason}" for reason, count in sorted(Counter(skipped).items()))
+            warnings.warn(f"Skipped {len(skipped)} of {len(depth_cues)} depth cues as unresolvable ({breakdown}).", stacklevel=2)
+        if not compiled:
+            raise ValueError(f"All {len(cues)} scale cues were unresolvable; cannot determine scale.")
+        d_arb, d_met, sigma = (np.array([c[k] for c in compiled], dtype=np.float64) for k in range(3))
+        if len(compiled) == 1:
+            scale = float(d_met[0] / d_arb[0])
+        else:
+            scale = float(np.sum(d_met * d_arb / sigma**2)) / float(np.sum(d_arb**2 / sigma**2))
+            implied, sigma_scale = d_met / d_arb, sigma / d_arb
+            two_sigma = 2.0 * np.hypot(sigma_scale[:, None], sigma_scale[None, :])
+            apart = np.abs(implied[:, None] - implied[None, :]) > two_sigma
+            for i, j in np.argwhere(np.triu(apart, 1)).tolist():  # (row-major: the order of the reference's double loop)
+                warnings.warn(f"Scale cues {i} and {j} disagree: implied scales {implied[i]:.6g} vs {implied[j]:.6g} differ by more than "
+                              f"2 sigma ({float(two_sigma[i, j]):.6g}).", stacklevel=2)
+        return self._transformed(SimilarityTransform(rotation=np.eye(3, dtype=np.float64), translation=np.zeros(3, dtype=np.float64), scale=scale))
+
+    def _compile_cue(self, cue) -> tuple[float, float, float]:
+        """(distance in the volume's units, metres, sigma in metres) of a ``CameraDistance`` or ``SegmentLength``; ``ValueError``
+        when it names something the volume does not have."""
+        if isinstance(cue, CameraDistance):
+            posed = self.camera_array.posed_cameras
+            for cam_id in (cue.cam_a, cue.cam_b):
+                if cam_id not in posed:
+                    raise ValueError(f"CameraDistance references cam_id {cam_id}, which is not a posed camera.")
+            d_arb = float(np.linalg.norm(self._camera_center(cue.cam_a) - self._camera_center(cue.cam_b)))
+            if d_arb == 0.0:
+                raise ValueError(f"Cameras {cue.cam_a} and {cue.cam_b} coincide; distance cue is degenerate.")
+            return d_arb, float(cue.meters), float(cue.sigma_m)
+        if isinstance(cue, SegmentLength):
+            wdf = self.world_points._df
+            coords = ["x_coord", "y_coord", "z_coord"]
+            side_a = wdf[wdf["keypoint_id"] == cue.keypoint_id_a][["sync_index", "object_id", *coords]]
+            side_b = wdf[wdf["keypoint_id"] == cue.keypoint_id_b][["sync_index", "object_id", *coords]]
+            both = side_a.merge(side_b, on=["sync_index", "object_id"], suffixes=("_a", "_b"))
+            if both.empty:
+                raise ValueError(f"SegmentLength found no frame where both keypoints {cue.keypoint_id_a} and {cue.keypoint_id_b} are triangulated.")
+            delta = both[[f"{c}_a" for c in coords]].to_numpy() - both[[f"{c}_b" for c in coords]].to_numpy()
+            return float(np.median(np.linalg.norm(delta, axis=1))), float(cue.meters), float(cue.sigma_m)
+        raise TypeError(f"Unknown scale cue type: {type(cue).__name__}")
+
+    def _compile_depth_cues(self, cues) -> list:
+        """Per ``DepthObservation``: (depth in the volume's units, metres, sigma) or the reason it cannot be used — "unposed camera",
+        "no world point", "ambiguous match" (more than one world point of that keypoint at that sync index), "non-positive depth",
+        tested in that order.  All cues are looked up in the world table with one sort of its (sync_index, keypoint_id) keys."""
+        if not cues:
+            return []
+        wdf = self.world_points._df
+        w_sync, w_kp = wdf["sync_index"].to_numpy(), wdf["keypoint_id"].to_numpy()
+        c_sync = np.array([int(c.sync_index) for c in cues], dtype=np.int64)
+        c_kp = np.array([int(c.keypoint_id) for c in cues], dtype=np.int64)
+        kp_values = np.unique(np.concatenate([w_kp, c_kp]))
+        sync_values = np.unique(np.concatenate([w_sync, c_sync]))
+        w_fold = np.searchsorted(sync_values, w_sync) * len(kp_values) + np.searchsorted(kp_values, w_kp)
+        c_fold = np.searchsorted(sync_values, c_sync) * len(kp_values) + np.searchsorted(kp_values, c_kp)
+        order = np.argsort(w_fold, kind="stable")
+        w_sorted = w_fold[order]
+        lo = np.searchsorted(w_sorted, c_fold, "left")
+        count = np.searchsorted(w_sorted, c_fold, "right") - lo
+        row = order[np.minimum(lo, max(len(order) - 1, 0))] if len(order) else np.zeros(len(cues), dtype=np.int64)
+        posed = self.camera_array.posed_cameras
+        cam_ids = sorted(posed)
+        index_of = {c: i for i, c in enumerate(cam_ids)}
+        cam_idx = np.array([index_of.get(c.cam_id, -1) for c in cues], dtype=np.int64)
+        z_row = np.array([posed[c].rotation[2] for c in cam_ids], dtype=np.float64).reshape(-1, 3)
+        z_off = np.array([posed[c].translation[2] for c in cam_ids], dtype=np.float64)
+        xyz = self.world_points.points[row] if len(order) else np.zeros((len(cues), 3))
+        safe = np.maximum(cam_idx, 0)
+        depth = (np.einsum("ij,ij->i", z_row[safe], xyz) + z_off[safe]) if cam_ids else np.zeros(len(cues))
+        reason = np.select([cam_idx < 0, count == 0, count > 1, ~(depth > 0.0)], [1, 2, 3, 4], 0).tolist()
+        names = (None, "unposed camera", "no world point", "ambiguous match", "non-positive depth")
+        return [names[r] if r else (float(d), float(c.depth_m), float(c.sigma_m)) for r, d, c in zip(reason, depth.tolist(), cues)]
+
+    def _compile_depth_cue(self, cue: DepthObservation):
+        """One depth cue: ``(d_arbitrary, d_metric, sigma_m)`` or the reason it is skipped."""
+        return self._compile_depth_cues([cue])[0]
+
+    def oriented(self, up: dict) -> "CaptureVolume":
+        """Rotate so that the vertical becomes +Z.  ``up``: cam_id -> that camera's up vector in its own frame; each is taken into
+        the world (``R^T up``), their mean is the vertical.  Yaw: the optical axis of the anchor camera (lowest posed cam_id),
+        projected onto the horizontal plane, becomes +Y.  Scale and origin stay.  The angle of every camera's vertical from the
+        consensus and the largest angle between two of them are logged."""
+        if not up:
+            raise ValueError("oriented() requires at least one up vector.")
+        world_ups = []
+        for cam_id, up_cam in up.items():
+            cam = self.camera_array.cameras.get(cam_id)
+            if cam is None or cam.rotation is None:
+                raise ValueError(f"oriented() references cam_id {cam_id}, which is not a posed camera.")
+            world_ups.append(cam.rotation.T @ np.asarray(up_cam, dtype=np.float64))
+        consensus = np.mean(np.stack(world_ups), axis=0)
+        length = float(np.linalg.norm(consensus))
+        if length < 1e-9:
+            raise ValueError("Consensus up vector is degenerate (per-camera verticals cancel).")
+        consensus = consensus / length
+        units = np.stack([w / np.linalg.norm(w) for w in world_ups])
+        from_consensus = np.degrees(np.arccos(np.clip(units @ consensus, -1.0, 1.0)))
+        between = np.degrees(np.arccos(np.clip(units @ units.T, -1.0, 1.0)))[np.triu_indices(len(units), 1)]
+        per_cam = ", ".join(f"cam {cam_id}: {deg:.2f}" for cam_id, deg in zip(up.keys(), from_consensus.tolist()))
+        logger.info(f"Vertical agreement (deg from consensus): {per_cam}; max pairwise disagreement {float(between.max()) if between.size else 0.0:.2f}")
+        forward = self.camera_array.cameras[self._anchor_cam_id()].rotation.T @ np.array([0.0, 0.0, 1.0])
+        rotation = world_basis_from_up_and_forward(consensus, forward=forward)
+        return self._transformed(SimilarityTransform(rotation=rotation, translation=np.zeros(3, dtype=np.float64), scale=1.0))
+
+    def grounded(self, mode: str = "lowest_point", *, lowest_point_height_m: float = 0.0) -> "CaptureVolume":
+        """Shift so that the floor is Z = 0 and the XY origin lies under the anchor camera.  The floor is the 1st percentile of the
+        world Z taken as an order statistic (``method="lower"``: one stray low point does not bury it; the minimum on small sets),
+        lifted by ``lowest_point_height_m`` when the lowest point is known to sit that far above the ground."""
+        if mode != "lowest_point":
+            raise ValueError(f"grounded() only supports mode='lowest_point', got {mode!r}.")
+        floor = float(np.percentile(self.world_points._df["z_coord"].to_numpy(), 1.0, method="lower"))
+        anchor = self._camera_center(self._anchor_cam_id())
+        return self.translate(x=-anchor[0], y=-anchor[1], z=-floor + lowest_point_height_m)
+
+    def centered(self) -> "CaptureVolume":
+        """Shift so that the XY origin is the centroid of the posed cameras' centres; Z stays."""
+        centers = np.array([self._camera_center(cam_id) for cam_id in self.camera_array.posed_cameras])
+        xy = centers[:, :2].mean(axis=0)
+        return self.translate(x=-xy[0], y=-xy[1])
 
     @classmethod
     def bootstrap(cls, image_points: ImagePoints, camera_array: CameraArray, constraints=None, *, estimate_poses: bool | str = False,

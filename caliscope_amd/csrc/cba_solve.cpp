@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/caliscope_ba.h"
+#include "scale_math.h"
 #include "trf_math.h"
 
 namespace {
@@ -420,4 +421,25 @@ extern "C" int cba_solve(cba_problem* p, const double* x0, const cba_solve_optio
   out->t_rejected_s = t_rejected; out->n_rejected_timed = n_rejected_timed;
   calls.print(out->t_total_s, iteration);
   return CBA_OK;
+}
+
+// ---- cba_scale_errors: the host half (checks and binning, csrc/scale_math.h), then the launch of scale_lib.hip ------------------
+extern "C" int cba_scale_errors(const cba_scale_desc* d, int32_t device, double* stats_out) {
+  if (!d || !stats_out) return cba_set_error(CBA_ERR_INVALID, "cba_scale_errors: null argument");
+  if (d->n_groups < 0 || d->n_world < 0 || !d->group_start) return cba_set_error(CBA_ERR_INVALID, "cba_scale_errors: bad descriptor");
+  if (d->n_groups == 0) return CBA_OK;
+  const int64_t n_groups = d->n_groups, n_ent = d->group_start[n_groups];
+  if (n_ent > 0 && (!d->ent_world || !d->ent_obj || !d->world_xyz)) return cba_set_error(CBA_ERR_INVALID, "cba_scale_errors: bad descriptor");
+  if (n_groups > ((int64_t)1 << 30)) return cba_set_error(CBA_ERR_UNSUPPORTED, "cba_scale_errors: more than 2^30 groups");
+  // bounds of everything the kernels index, and the binning, before anything reaches the device
+  cba::ScalePlan plan;
+  std::string msg;
+  const int prc = cba::scale_plan(d->n_world, n_groups, d->group_start, d->ent_world, plan, msg);
+  if (prc) return cba_set_error(prc == -4 ? CBA_ERR_UNSUPPORTED : CBA_ERR_INVALID, msg.c_str());
+  if (!cba_scale_launch) return cba_set_error(CBA_ERR_UNSUPPORTED, "cba_scale_errors: this build has no device kernels");
+  std::vector<int64_t> list;
+  list.reserve((size_t)n_groups);
+  for (const auto* v : {&plan.small, &plan.lds_small, &plan.lds_large, &plan.direct}) list.insert(list.end(), v->begin(), v->end());
+  const int64_t counts[4] = {(int64_t)plan.small.size(), (int64_t)plan.lds_small.size(), (int64_t)plan.lds_large.size(), (int64_t)plan.direct.size()};
+  return cba_scale_launch(d, device, list.data(), counts, stats_out);
 }

@@ -398,6 +398,27 @@ typedef struct {
 /* xyz_out [n_points][3]; undistorted_out [n_obs][2] or NULL.  device = HIP device ordinal. */
 int cba_triangulate(const cba_triangulate_desc* d, int32_t device, double* xyz_out, double* undistorted_out);
 
+/* ---- the step after the path: scale accuracy of a calibrated volume ----
+ *
+ * Replaces the per-(frame, object) loop of the reference's `compute_volumetric_scale_accuracy` (core/capture_volume.py:783-826) and the
+ * two `pdist` calls of `compute_frame_scale_error` (core/scale_accuracy.py:277-293).  A group is one rigid object in one frame: entry e
+ * of group g, group_start[g] <= e < group_start[g + 1], pairs the world point world_xyz[ent_world[e]] with the object point
+ * ent_obj[e]; err = |w_i - w_j| - |o_i - o_j| over all pairs i < j of the group, plain FP64, every sum in a fixed order (two calls
+ * return the same bits).  Groups are binned by size on the host: one thread per group up to 12 entries, one workgroup per group
+ * above, with the group's coordinates staged in LDS up to 1024 entries (csrc/scale_math.h).  A group may have at most 32 768
+ * entries (536 854 528 pairs): CBA_ERR_UNSUPPORTED beyond.  An entry index outside [0, n_world) or a decreasing group_start is
+ * CBA_ERR_INVALID, the message names the position.  n_groups == 0 succeeds without a launch. */
+#define CBA_SCALE_NSTAT 8
+typedef struct {
+  int64_t n_world;   const double* world_xyz;    /* [n_world][3] */
+  int64_t n_groups;  const int64_t* group_start; /* [n_groups + 1], non-decreasing, group_start[0] = 0 */
+  const int64_t* ent_world;                      /* [n_ent] row of world_xyz (groups may share rows: static markers) */
+  const double* ent_obj;                         /* [n_ent][3] object point of the entry */
+} cba_scale_desc;
+/* stats_out [n_groups][8]: sum err, sum err^2, max |err|, D_ref, centroid x y z, n_pairs (as double).
+ * err over all pairs of the group; a group of fewer than two entries gets zeros. */
+int cba_scale_errors(const cba_scale_desc* d, int32_t device, double* stats_out);
+
 /* Give back what the library keeps between handles: per device up to four 4 MB arena chunks, streams, mapped mailboxes and pinned staging buffers of
  * destroyed handles, and the process-wide pool of huge-page host blocks the set-up's large arrays come from (up to 3 GB after a 10M-observation
  * handle).  Live handles are not touched.  A long-lived host process (the reference's GUI session) calls it when a calibration is done:
