@@ -6,7 +6,10 @@ Host-side mirror of the reference's ``core/calibrate_intrinsics.py`` under the s
 * :func:`calibrate_camera_array_intrinsics`: every non-ignored camera of a :class:`CameraArray` in ONE device call, the
   ``matrix`` / ``distortions`` / ``error`` / ``grid_count`` fields set as ``run_intrinsic_calibration`` step 3 sets them.  With
   ``frames=None`` every frame with at least four corners is used (the reference sub-samples to about 30 frames because
-  ``cv2.calibrateCamera`` cannot afford more).
+  ``cv2.calibrateCamera`` cannot afford more); ``frames="select"`` runs the reference's frame selection for all cameras first
+  (``caliscope_amd/frame_selector.py``, one more device call) and attaches each camera's coverage report;
+* :class:`IntrinsicCalibrationReport`, :class:`IntrinsicCalibrationOutput` and :func:`run_intrinsic_calibration`: the reference's
+  one-camera workflow, selection -> solve -> calibrated camera and report.
 
 Where the work runs: the views are gathered with numpy (one sort of the rows); start poses (``k_pose_pnp`` with the start
 intrinsics) and the whole Levenberg-Marquardt solve (``k_intrinsics``, one workgroup per camera) run on the device through
@@ -17,8 +20,7 @@ a GPU the call raises ``BackendError``.  ``_solver`` replaces the device call (a
 Differences from cv2, on purpose: the result is the least-squares minimum of the pixel reprojection error, not cv2's bits (cv2 stops
 after 30 iterations or a 2.2e-16 change); the fisheye model has no skew (``cv2.fisheye.calibrate`` estimates one unless told not
 to; the camera model of this project has none); the fisheye start (f = max(w, h) / pi, c = (w/2 - 0.5, h/2 - 0.5)) is this project's
-choice; views whose start pose cannot be found are left out and reported instead of failing the call.  The reference's frame
-selection (``select_calibration_frames``, ``IntrinsicCoverageReport``) is not ported.
+choice; views whose start pose cannot be found are left out and reported instead of failing the call.
 """
 
 from __future__ import annotations
@@ -26,12 +28,13 @@ from __future__ import annotations
 import ctypes as C
 import logging
 from copy import deepcopy
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import numpy as np
 
 from caliscope_amd import _lib
 from caliscope_amd.exceptions import BackendError
+from caliscope_amd.frame_selector import IntrinsicCoverageReport, rig_cameras, select_calibration_frames, select_rig
 
 logger = logging.getLogger(__name__)
 
@@ -119,7 +122,8 @@ class CameraIntrinsicsReport:
     """What :func:`calibrate_camera_array_intrinsics` reports per camera: ``result`` (None unless ``status == 0``), the status
     (0 ok, 1 too few usable views, 2 solve failed), the number of linearisations, and per view handed to the solver — a view is
     one object in one frame, the key of the pose bootstrap — its ``sync_index``, ``object_id``, status (0 used, 1 too few corners,
-    2 left out: no start pose) and RMS reprojection error in pixels."""
+    2 left out: no start pose) and RMS reprojection error in pixels.  ``coverage``: the camera's frame-selection report when the
+    call selected the frames (``frames="select"``), else None."""
 
     result: IntrinsicCalibrationResult | None
     status: int
@@ -128,6 +132,31 @@ class CameraIntrinsicsReport:
     view_status: np.ndarray
     view_rmse: np.ndarray
     object_id: np.ndarray | None = None
+    coverage: IntrinsicCoverageReport | None = None
+
+
+@dataclass(frozen=True)
+class IntrinsicCalibrationReport:
+    """How the intrinsic calibration of one camera was derived (reference ``calibrate_intrinsics.py:53-73``): RMSE on the calibration
+    frames in pixels and their number, the selection's coverage fractions and orientation diversity, and the selected
+    ``sync_index`` values."""
+
+    rmse: float
+    frames_used: int
+    coverage_fraction: float
+    edge_coverage_fraction: float
+    corner_coverage_fraction: float
+    orientation_sufficient: bool
+    orientation_count: int
+    selected_frames: tuple[int, ...]
+
+
+@dataclass(frozen=True)
+class IntrinsicCalibrationOutput:
+    """The calibrated camera and its report, travelling together (reference ``calibrate_intrinsics.py:76-86``)."""
+
+    camera: object
+    report: IntrinsicCalibrationReport
 
 
 def _gather_views(image_points, cam_ids, frames, by_object):
@@ -206,26 +235,61 @@ def calibrate_intrinsics(image_points, cam_id: int, image_size: tuple[int, int],
     return report.result
 
 
+def run_intrinsic_calibration(camera, image_points, selection_result: IntrinsicCoverageReport | None = None, *, float32_io: bool = True,
+                              _solver=None, _selector=None) -> IntrinsicCalibrationOutput:
+    """The complete workflow for one camera (the reference's function, ``calibrate_intrinsics.py:233-308``): frame selection unless
+    ``selection_result`` brings one, the solve on the selected frames, then the calibrated camera — a copy of ``camera`` with
+    ``matrix``, ``distortions``, ``error`` and ``grid_count`` set — and the report.  ``ValueError`` when no frame is selected or the
+    calibration fails.  ``_solver`` / ``_selector`` replace the two device calls."""
+    cam_id = camera.cam_id
+    if selection_result is None:
+        selection_result = select_calibration_frames(image_points, cam_id, camera.size, float32_io=float32_io, _solver=_selector)
+    if not selection_result.selected_frames:
+        raise ValueError(f"No frames selected for calibration on cam_id {cam_id}")
+    selected_frames = selection_result.selected_frames
+    result = calibrate_intrinsics(image_points, cam_id, camera.size, selected_frames, fisheye=bool(camera.fisheye), float32_io=float32_io,
+                                  _solver=_solver)
+    calibrated = deepcopy(camera)
+    calibrated.matrix = result.camera_matrix.copy()
+    calibrated.distortions = result.distortions.copy()
+    calibrated.error = result.reprojection_error
+    calibrated.grid_count = result.frames_used
+    report = IntrinsicCalibrationReport(
+        rmse=result.reprojection_error, frames_used=result.frames_used, coverage_fraction=selection_result.coverage_fraction,
+        edge_coverage_fraction=selection_result.edge_coverage_fraction, corner_coverage_fraction=selection_result.corner_coverage_fraction,
+        orientation_sufficient=selection_result.orientation_sufficient, orientation_count=selection_result.orientation_count,
+        selected_frames=tuple(selected_frames))
+    logger.info(f"Calibration complete for cam_id {cam_id}: rmse={report.rmse:.3f}px, frames={report.frames_used}, coverage={report.coverage_fraction:.0%}")
+    return IntrinsicCalibrationOutput(camera=calibrated, report=report)
+
+
 def calibrate_camera_array_intrinsics(image_points, camera_array, frames=None, *, only_missing: bool = False, float32_io: bool = True,
-                                      max_iter: int = 0, _solver=None):
+                                      max_iter: int = 0, target_frame_count: int = 30, min_corners_per_frame: int = 6, min_orientations: int = 4,
+                                      grid_size: int = 5, _solver=None, _selector=None):
     """Calibrate every non-ignored camera of ``camera_array`` (``only_missing``: only those without a matrix or distortion
     coefficients) in one device call.  A view is one object in one frame, (cam_id, sync_index, object_id) as in the pose
     bootstrap: sessions may hold several rigid objects, each with its own ``obj_loc`` frame.  ``frames=None``: every view with at
     least four corners; ``{cam_id: [sync_index, ...]}``
-    selects frames per camera (a camera not named gets none).  Returns ``(CameraArray, {cam_id: CameraIntrinsicsReport})``: a copy
+    selects frames per camera (a camera not named gets none); ``"select"`` runs :func:`caliscope_amd.frame_selector.select_rig` over the
+    same cameras first (keywords ``target_frame_count``, ``min_corners_per_frame``, ``min_orientations``, ``grid_size``; ``_selector``
+    replaces its device call), solves from the frames it chose and sets ``coverage`` in every report.  Returns ``(CameraArray, {cam_id: CameraIntrinsicsReport})``: a copy
     of the array in which every camera that solved carries ``matrix``, ``distortions``, ``error`` and ``grid_count``; a camera
     that did not is left as it was.  The input array is not touched."""
     out = deepcopy(camera_array)
-    cams = []
-    for cam_id, cam in sorted(out.cameras.items()):
-        if cam.ignore or (only_missing and cam.matrix is not None and cam.distortions is not None):
-            continue
-        if cam.size is None:
-            raise ValueError(f"Camera {cam_id} has no resolution data: intrinsic calibration starts from the image size.")
-        cams.append((cam_id, cam.size, bool(cam.fisheye)))
+    cams = [(cam_id, cam.size, bool(cam.fisheye)) for cam_id, cam in rig_cameras(out, only_missing)]
     if not cams:
         return out, {}
+    coverage = None
+    if isinstance(frames, str):
+        if frames != "select":
+            raise ValueError(f"frames must be None, a dict {{cam_id: sync_index values}} or \"select\", got {frames!r}")
+        coverage, _, _ = select_rig(image_points, [(c, size) for c, size, _ in cams], target_frame_count=target_frame_count,
+                                    min_corners_per_frame=min_corners_per_frame, min_orientations=min_orientations, grid_size=grid_size,
+                                    float32_io=float32_io, by_object=True, _solver=_selector)
+        frames = {c: rep.selected_frames for c, rep in coverage.items()}
     reports = _solve(image_points, cams, frames, float32_io, max_iter, _solver)
+    if coverage is not None:
+        reports = {c: replace(rep, coverage=coverage[c]) for c, rep in reports.items()}
     for cam_id, rep in reports.items():
         if rep.result is not None:
             cam = out.cameras[cam_id]
@@ -236,5 +300,6 @@ def calibrate_camera_array_intrinsics(image_points, camera_array, frames=None, *
     return out, reports
 
 
-__all__ = ["IntrinsicCalibrationResult", "CameraIntrinsicsReport", "DeviceIntrinsics", "calibrate_intrinsics",
-           "calibrate_camera_array_intrinsics", "MIN_CORNERS_PER_FRAME"]
+__all__ = ["IntrinsicCalibrationResult", "CameraIntrinsicsReport", "IntrinsicCalibrationReport", "IntrinsicCalibrationOutput",
+           "IntrinsicCoverageReport", "DeviceIntrinsics", "calibrate_intrinsics", "calibrate_camera_array_intrinsics",
+           "run_intrinsic_calibration", "select_calibration_frames", "MIN_CORNERS_PER_FRAME"]

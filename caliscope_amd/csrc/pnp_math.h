@@ -293,6 +293,15 @@ CBA_HD bool pnp_translation(const double* obj, const double* uv, int n, int f32,
   return pnp_finite(t[0]) && pnp_finite(t[1]) && pnp_finite(t[2]);
 }
 
+// The two DLT rows of one correspondence (x, y) -> (u, v) of a homography with h33 = 1, added to the packed 8 x 8 normal equations
+// A and their right-hand side h (pnp_planar_init; the start of the homography fit of frame_select_math.h).
+CBA_HD void homog_dlt_add(double* A, double* h, double x, double y, double u, double v) {
+  const double ru[8] = {x, y, 1.0, 0.0, 0.0, 0.0, -u * x, -u * y};
+  const double rv[8] = {0.0, 0.0, 0.0, x, y, 1.0, -v * x, -v * y};
+  normal_add<8>(A, h, ru, u);
+  normal_add<8>(A, h, rv, v);
+}
+
 // Planar initial rotations (IPPE) from the homography of the centred board; false when the homography is degenerate.
 CBA_HD bool pnp_planar_init(const double* obj, const double* uv, int n, int f32, const double* cen, const double* im_c, double s_o,
                             double s_i, double* R1, double* R2) {
@@ -307,10 +316,7 @@ CBA_HD bool pnp_planar_init(const double* obj, const double* uv, int n, int f32,
     pnp_load(obj, uv, i, f32, X, u);
     const double x = (X[0] - cen[0]) * io, y = (X[1] - cen[1]) * io;
     const double uu = (u[0] - im_c[0]) * ii, vv = (u[1] - im_c[1]) * ii;
-    const double ru[8] = {x, y, 1.0, 0.0, 0.0, 0.0, -uu * x, -uu * y};
-    const double rv[8] = {0.0, 0.0, 0.0, x, y, 1.0, -vv * x, -vv * y};
-    normal_add<8>(A, h, ru, uu);
-    normal_add<8>(A, h, rv, vv);
+    homog_dlt_add(A, h, x, y, uu, vv);
   }
   if (!chol_solve<8>(A, h)) return false;
   // H = Ti^-1 Hn So with So = diag(1/s_o, 1/s_o, 1), Ti^-1 = [s_i 0 cx; 0 s_i cy; 0 0 1]: H22 = 1

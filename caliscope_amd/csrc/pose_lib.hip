@@ -37,6 +37,20 @@
 //                     pose and the A_v^-1 terms live in a global work array (INTR_WORK doubles per view; each thread touches only
 //                     the rows of its own views, so no barrier guards them).  No atomics: bit-identical from run to run.
 //
+// The frame selection of the intrinsic calibration (arithmetic: frame_select_math.h) is one call of two launches; the per-frame
+// features stay on the device between them:
+//
+//   k_frame_features  one thread per frame, frames handed out sorted by corner count as k_pose_pnp's views: cell mask, pose features,
+//                     then the homography of the frame's subrange (8 x 8 normal equations and the Levenberg-Marquardt polish in
+//                     registers) and the orientation features read off it.
+//   k_frame_select    one SELECT_BLOCK workgroup per camera, fsel_select: threads stride over the camera's frames; every anchor bin
+//                     and every greedy round is one value per frame and one workgroup argmax over (value, -frame): shuffles inside
+//                     a wave, then LDS across the waves, every thread reads the winner.  The running distance to the nearest
+//                     selected frame lives in a device array of n_frames doubles; a frame's entry is only ever touched by the one
+//                     thread that strides over it.  No atomics, fixed order: bit-identical from run to run.
+//                     k_frame_features: 236 VGPRs, ScratchSize 0 (a trial step evaluates the cost alone, so one normal matrix and
+//                     its damped copy are live); k_frame_select: 49 VGPRs, ScratchSize 0.
+//
 // No host synchronisation inside a call beyond the final copy-back.  The epipolar workgroup kernels keep one LDS reduction buffer
 // of EPI_LIN_NSUM x REFINE_BLOCK doubles (46 KiB), k_intrinsics one of INTR_NSUM_MAX x REFINE_BLOCK doubles (55 KiB).  The largest
 // per-thread matrices of the bootstrap kernels are the 9 x 8 Householder factor (k_epi_hyp) and the 11 x 11 DLT normal matrix
@@ -54,6 +68,7 @@
 #include "../../include/caliscope_pose.h"
 #include "device_call.h"
 #include "epipolar_math.h"
+#include "frame_select_math.h"
 #include "intrinsic_math.h"
 
 using namespace cba;
@@ -589,6 +604,125 @@ k_intrinsics(const int* __restrict__ cam_model, const double* __restrict__ cam_s
   }
 }
 
+// ---- frame selection ---------------------------------------------------------------------------------------------------------
+
+constexpr int FEAT_BLOCK = 64;     // one wave, as POSE_BLOCK: frames differ in cost
+constexpr int SELECT_BLOCK = 256;
+
+__global__ void __launch_bounds__(FEAT_BLOCK)
+k_frame_features(long n_frames, const long* __restrict__ order, const long* __restrict__ frame_start, const int* __restrict__ frame_cam,
+                 const double* __restrict__ cam_size, const long* __restrict__ homog_start, const int* __restrict__ homog_count,
+                 const double* __restrict__ obs_xy, const double* __restrict__ obs_obj, int grid, int f32,
+                 unsigned long long* __restrict__ mask_out, double* __restrict__ feat_out, double* __restrict__ orient_out,
+                 int* __restrict__ status_out, double* __restrict__ rmse_out) {
+  const long q = (long)blockIdx.x * FEAT_BLOCK + threadIdx.x;
+  if (q >= n_frames) return;
+  const long f = order[q];
+  const long a = frame_start[f];
+  const int n = (int)(frame_start[f + 1] - a);
+  const int c = frame_cam[f];
+  const double w = cam_size[2 * c], h = cam_size[2 * c + 1];
+  mask_out[f] = fsel_coverage(obs_xy + 2 * a, n, w, h, grid);
+  double feat[5];
+  fsel_pose_features(obs_xy + 2 * a, n, w, h, feat);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) feat_out[5 * f + k] = feat[k];
+  const long ha = homog_start ? homog_start[f] : a;
+  const int hn = homog_start ? homog_count[f] : n;
+  double o[3], r;
+  const int st = fsel_orientation(obs_obj + 2 * ha, obs_xy + 2 * ha, hn, f32, o, &r);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) orient_out[3 * f + k] = o[k];
+  status_out[f] = st;
+  rmse_out[f] = r;
+}
+
+// workgroup argmax over (value, -frame): every thread gets the winner (-1: no candidate) and its value
+__device__ __forceinline__ int wg_argmax(double v, int f, double* sv, int* si, double* best) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double v2 = __shfl_down(v, o, 64);
+    const int f2 = __shfl_down(f, o, 64);
+    if (fsel_better(v2, f2, v, f)) { v = v2; f = f2; }
+  }
+  const int tid = threadIdx.x;
+  if ((tid & 63) == 0) { sv[tid >> 6] = v; si[tid >> 6] = f; }
+  __syncthreads();
+  double bv = sv[0];
+  int bf = si[0];
+#pragma unroll
+  for (int k = 1; k < SELECT_BLOCK / 64; ++k)
+    if (fsel_better(sv[k], si[k], bv, bf)) { bv = sv[k]; bf = si[k]; }
+  __syncthreads();
+  *best = bv;
+  return bf;
+}
+
+// The ops of fsel_select on the device: the workgroup's threads stride over the camera's frames (all arrays start at the camera's
+// first frame).
+struct FrameSelDev {
+  int nf; const long* fstart; int min_corners;
+  const unsigned long long* mask; const double* feat; const double* orient;
+  uint64_t edge, corner;
+  double* dist; int* sel; double* sv; int* si;
+  __device__ bool eligible(int f) const { return fstart[f + 1] - fstart[f] >= (long)min_corners; }
+  __device__ uint64_t mask_of(int f) const { return mask[f]; }
+  __device__ void take(int k, int f) { if (threadIdx.x == 0) sel[k] = f; }
+  __device__ int best_in_bin(int b) {
+    double bv = 0.0, best;
+    int bf = -1;
+    for (int f = threadIdx.x; f < nf; f += SELECT_BLOCK)
+      if (eligible(f) && fsel_bin(orient + 3 * f) == b && fsel_better(orient[3 * f + 1], f, bv, bf)) { bv = orient[3 * f + 1]; bf = f; }
+    return wg_argmax(bv, bf, sv, si, &best);
+  }
+  __device__ void start(const int* anchors, int na) {
+    for (int f = threadIdx.x; f < nf; f += SELECT_BLOCK) dist[f] = fsel_start_dist(feat, f, eligible(f), anchors, na);
+  }
+  __device__ int best_score(int last, uint64_t covered, bool have, double* score) {
+    double bv = 0.0;
+    int bf = -1;
+    for (int f = threadIdx.x; f < nf; f += SELECT_BLOCK) {
+      double m = dist[f], s;
+      const bool cand = fsel_round_item(feat, f, last, mask[f], covered, edge, corner, have, &m, &s);
+      if (last >= 0) dist[f] = m;
+      if (cand && fsel_better(s, f, bv, bf)) { bv = s; bf = f; }
+    }
+    return wg_argmax(bv, bf, sv, si, score);
+  }
+};
+
+__global__ void __launch_bounds__(SELECT_BLOCK)
+k_frame_select(const long* __restrict__ cam_frame_start, const long* __restrict__ frame_start, const unsigned long long* __restrict__ mask,
+               const double* __restrict__ feat, const double* __restrict__ orient, int grid, int min_corners, int target,
+               double* __restrict__ dist, int* __restrict__ selected_out, int* __restrict__ n_selected_out, int* __restrict__ n_anchors_out,
+               int* __restrict__ bin_mask_out, int* __restrict__ eligible_out) {
+  __shared__ double sv[SELECT_BLOCK / 64];
+  __shared__ int si[SELECT_BLOCK / 64];
+  __shared__ int cnt[SELECT_BLOCK / 64];
+  const int c = blockIdx.x;
+  const long f0 = cam_frame_start[c];
+  const int nf = (int)(cam_frame_start[c + 1] - f0);
+  FrameSelDev ops{nf, frame_start + f0, min_corners, mask + f0, feat + 5 * f0, orient + 3 * f0, fsel_edge_mask(grid), fsel_corner_mask(grid),
+                  dist + f0, selected_out + (long)c * target, sv, si};
+  int n_el = 0;
+  for (int f = threadIdx.x; f < nf; f += SELECT_BLOCK) n_el += ops.eligible(f) ? 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n_el += __shfl_down(n_el, o, 64);
+  if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = n_el;
+  __syncthreads();
+  int na, bins;
+  const int n_sel = fsel_select(ops, target, &na, &bins);
+  if (threadIdx.x == 0) {
+    int tot = 0;
+#pragma unroll
+    for (int k = 0; k < SELECT_BLOCK / 64; ++k) tot += cnt[k];
+    n_selected_out[c] = n_sel;
+    n_anchors_out[c] = na;
+    bin_mask_out[c] = bins;
+    eligible_out[c] = tot;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -913,6 +1047,106 @@ int cba_pose_intrinsics_batch(const cba_intrinsics_desc* d, int32_t device, doub
   if (e == hipSuccess && n_views > 0) e = hipMemcpy(pose_out, dpose, (size_t)n_views * 12 * sizeof(double), hipMemcpyDeviceToHost);
   if (e == hipSuccess && n_views > 0) e = hipMemcpy(view_rmse_out, dvr, (size_t)n_views * sizeof(double), hipMemcpyDeviceToHost);
   if (e == hipSuccess && n_views > 0) e = hipMemcpy(view_status_out, dvst, (size_t)n_views * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  return CBA_OK;
+}
+
+int cba_pose_select_frames(const cba_frame_select_desc* d, int32_t device, uint64_t* cell_mask_out, double* pose_feat_out, double* orient_out,
+                           int32_t* homog_status_out, double* homog_rmse_out, int32_t* selected_out, int32_t* n_selected_out,
+                           int32_t* n_anchors_out, int32_t* bin_mask_out, int32_t* eligible_out) {
+  const char* what = "cba_pose_select_frames";
+  if (!d) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
+  if (d->n_cams < 0 || d->n_frames < 0 || d->target_count < 1 || d->min_corners < 0 || (!d->homog_start != !d->homog_count))
+    return err(CBA_ERR_INVALID, std::string(what) + ": bad descriptor");
+  if (d->grid_size < 1 || d->grid_size > FSEL_MAX_GRID)
+    return err(CBA_ERR_UNSUPPORTED, std::string(what) + ": grid_size " + std::to_string(d->grid_size) + " outside 1.." + std::to_string(FSEL_MAX_GRID) +
+                                        " (the cell mask has 64 bits)");
+  const int32_t n_cams = d->n_cams, target = d->target_count;
+  const int64_t n_frames = d->n_frames;
+  if (n_cams > 0 && (!d->cam_frame_start || !d->cam_size || !selected_out || !n_selected_out || !n_anchors_out || !bin_mask_out || !eligible_out))
+    return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
+  if (n_frames > 0 && (n_cams == 0 || !d->frame_start || !d->obs_xy || !d->obs_obj || !cell_mask_out || !pose_feat_out || !orient_out ||
+                       !homog_status_out || !homog_rmse_out))
+    return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
+  if (n_cams == 0) return CBA_OK;
+  // bounds of everything the kernels index, checked on the host before anything reaches the device
+  if (d->cam_frame_start[0] != 0) return err(CBA_ERR_INVALID, std::string(what) + ": cam_frame_start[0] != 0");
+  for (int32_t c = 0; c < n_cams; ++c) {
+    if (d->cam_frame_start[c + 1] < d->cam_frame_start[c]) return err(CBA_ERR_INVALID, std::string(what) + ": cam_frame_start decreases at camera " + std::to_string(c));
+    if (d->cam_frame_start[c + 1] - d->cam_frame_start[c] > 0x7fffffff) return err(CBA_ERR_INVALID, std::string(what) + ": too many frames of camera " + std::to_string(c));
+    const double w = d->cam_size[2 * c], h = d->cam_size[2 * c + 1];
+    if (!(w > 0.0) || !(h > 0.0) || !pnp_finite(w) || !pnp_finite(h)) return err(CBA_ERR_INVALID, std::string(what) + ": camera " + std::to_string(c) + " has no image size");
+  }
+  if (d->cam_frame_start[n_cams] != n_frames) return err(CBA_ERR_INVALID, std::string(what) + ": cam_frame_start does not end at n_frames");
+  if ((uint64_t)n_cams * (uint64_t)target > (uint64_t)1 << 40) return err(CBA_ERR_INVALID, std::string(what) + ": n_cams * target_count too large");
+  std::fill(selected_out, selected_out + (size_t)n_cams * target, -1);
+  if (n_frames == 0) {
+    for (int32_t c = 0; c < n_cams; ++c) n_selected_out[c] = n_anchors_out[c] = bin_mask_out[c] = eligible_out[c] = 0;
+    return CBA_OK;
+  }
+  if (d->frame_start[0] != 0) return err(CBA_ERR_INVALID, std::string(what) + ": frame_start[0] != 0");
+  for (int64_t f = 0; f < n_frames; ++f) {
+    const int64_t a = d->frame_start[f], b = d->frame_start[f + 1];
+    if (b < a) return err(CBA_ERR_INVALID, std::string(what) + ": frame_start decreases at frame " + std::to_string(f));
+    if (b - a > (int64_t)1 << 30) return err(CBA_ERR_INVALID, std::string(what) + ": frame too large");
+    if (d->homog_start && (d->homog_count[f] < 0 || d->homog_start[f] < a || d->homog_start[f] > b || d->homog_count[f] > b - d->homog_start[f]))
+      return err(CBA_ERR_INVALID, std::string(what) + ": homography subrange outside frame " + std::to_string(f));
+  }
+  int rc = select_device(device, what);
+  if (rc) return rc;
+  const int64_t n_obs = d->frame_start[n_frames];
+  // frames by corner count (stable), and the camera of every frame
+  std::vector<int64_t> order(n_frames);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {
+    return d->frame_start[x + 1] - d->frame_start[x] < d->frame_start[y + 1] - d->frame_start[y];
+  });
+  std::vector<int32_t> frame_cam(n_frames);
+  for (int32_t c = 0; c < n_cams; ++c) std::fill(frame_cam.begin() + d->cam_frame_start[c], frame_cam.begin() + d->cam_frame_start[c + 1], c);
+  Buffers buf;
+  void *dord = nullptr, *dfs = nullptr, *dfc = nullptr, *dcfs = nullptr, *dsize = nullptr, *dhs = nullptr, *dhc = nullptr, *dxy = nullptr, *dobj = nullptr,
+       *dmask = nullptr, *dfeat = nullptr, *dori = nullptr, *dhst = nullptr, *dhr = nullptr, *ddist = nullptr, *dsel = nullptr, *dns = nullptr,
+       *dna = nullptr, *dbm = nullptr, *del = nullptr;
+  rc = buf.up(order.data(), (size_t)n_frames * sizeof(int64_t), &dord);
+  if (!rc) rc = buf.up(d->frame_start, (size_t)(n_frames + 1) * sizeof(int64_t), &dfs);
+  if (!rc) rc = buf.up(frame_cam.data(), (size_t)n_frames * sizeof(int32_t), &dfc);
+  if (!rc) rc = buf.up(d->cam_frame_start, (size_t)(n_cams + 1) * sizeof(int64_t), &dcfs);
+  if (!rc) rc = buf.up(d->cam_size, (size_t)n_cams * 2 * sizeof(double), &dsize);
+  if (!rc && d->homog_start) rc = buf.up(d->homog_start, (size_t)n_frames * sizeof(int64_t), &dhs);
+  if (!rc && d->homog_start) rc = buf.up(d->homog_count, (size_t)n_frames * sizeof(int32_t), &dhc);
+  if (!rc) rc = buf.up(d->obs_xy, (size_t)n_obs * 2 * sizeof(double), &dxy);
+  if (!rc) rc = buf.up(d->obs_obj, (size_t)n_obs * 2 * sizeof(double), &dobj);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * sizeof(uint64_t), &dmask);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * 5 * sizeof(double), &dfeat);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * 3 * sizeof(double), &dori);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * sizeof(int32_t), &dhst);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * sizeof(double), &dhr);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * sizeof(double), &ddist);
+  if (!rc) rc = buf.up(selected_out, (size_t)n_cams * target * sizeof(int32_t), &dsel);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &dns);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &dna);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &dbm);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &del);
+  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "cell masks are passed as unsigned long long");
+  hipLaunchKernelGGL(k_frame_features, dim3((unsigned)((n_frames + FEAT_BLOCK - 1) / FEAT_BLOCK)), dim3(FEAT_BLOCK), 0, 0, (long)n_frames,
+                     (const long*)dord, (const long*)dfs, (const int*)dfc, (const double*)dsize, (const long*)dhs, (const int*)dhc, (const double*)dxy,
+                     (const double*)dobj, (int)d->grid_size, d->float32_io ? 1 : 0, (unsigned long long*)dmask, (double*)dfeat, (double*)dori,
+                     (int*)dhst, (double*)dhr);
+  hipLaunchKernelGGL(k_frame_select, dim3((unsigned)n_cams), dim3(SELECT_BLOCK), 0, 0, (const long*)dcfs, (const long*)dfs,
+                     (const unsigned long long*)dmask, (const double*)dfeat, (const double*)dori, (int)d->grid_size, (int)d->min_corners, (int)target,
+                     (double*)ddist, (int*)dsel, (int*)dns, (int*)dna, (int*)dbm, (int*)del);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(cell_mask_out, dmask, (size_t)n_frames * sizeof(uint64_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(pose_feat_out, dfeat, (size_t)n_frames * 5 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(orient_out, dori, (size_t)n_frames * 3 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(homog_status_out, dhst, (size_t)n_frames * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(homog_rmse_out, dhr, (size_t)n_frames * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(selected_out, dsel, (size_t)n_cams * target * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(n_selected_out, dns, (size_t)n_cams * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(n_anchors_out, dna, (size_t)n_cams * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(bin_mask_out, dbm, (size_t)n_cams * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(eligible_out, del, (size_t)n_cams * sizeof(int32_t), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
   return CBA_OK;
 }

@@ -140,6 +140,40 @@ typedef struct {
 int cba_pose_intrinsics_batch(const cba_intrinsics_desc* d, int32_t device, double* intr_out, double* rmse_out, int32_t* status_out,
                               int32_t* iters_out, double* pose_out, double* view_rmse_out, int32_t* view_status_out);
 
+/* Frame selection and coverage report for the intrinsic calibration of every camera of a rig (caliscope_amd/frame_selector.py; the
+ * reference's core/frame_selector.py).  Frames in CSR form over the rows, cameras in CSR form over the frames: the frames of a
+ * camera are contiguous and ascending in sync_index, and a frame number in the outputs counts from the camera's first frame.
+ * Statuses of a frame's homography: */
+enum cba_frame_homog_status { CBA_FSEL_OK = 0, CBA_FSEL_TOO_FEW = 1, CBA_FSEL_FAILED = 2 };
+
+typedef struct {
+  int32_t n_cams;
+  const int64_t* cam_frame_start; /* [n_cams + 1], non-decreasing, [0] = 0, [n_cams] = n_frames */
+  const double* cam_size;         /* [n_cams][2] image width, height in pixels */
+  int64_t n_frames;
+  const int64_t* frame_start;     /* [n_frames + 1], non-decreasing, [0] = 0 */
+  const int64_t* homog_start;     /* optional [n_frames]: first row of the rows the frame's homography is fitted to, */
+  const int32_t* homog_count;     /* [n_frames] and their number, inside the frame; both null: the whole frame */
+  const double* obs_xy;           /* [n_obs][2] pixels */
+  const double* obs_obj;          /* [n_obs][2] board x, y */
+  int32_t grid_size;              /* coverage grid, 1..8 (the cell mask has 64 bits: bit row * grid_size + col); beyond: CBA_ERR_UNSUPPORTED */
+  int32_t min_corners;            /* rows a frame needs to be eligible */
+  int32_t target_count;           /* frames to select per camera, >= 1 */
+  int32_t float32_io;             /* homography inputs rounded to float32, board coordinates normalised in float (the reference) */
+} cba_frame_select_desc;
+
+/* Two launches.  Per frame: cell_mask_out[n_frames]; pose_feat_out[n_frames][5] centroid x y, spread x y (each / image size),
+ * aspect; orient_out[n_frames][3] tilt direction [0, 2 pi), tilt magnitude, in-plane rotation [0, 2 pi) from the least-squares
+ * homography of the pixel transfer error (three zeros unless the status is OK); homog_status_out; homog_rmse_out: transfer RMSE in
+ * pixels.  Per camera: selected_out[n_cams][target_count] frame numbers in selection order (anchors of the occupied tilt bins
+ * first, then the greedy coverage phase), -1 beyond n_selected_out; n_anchors_out: occupied bins; bin_mask_out: their bits;
+ * eligible_out: frames with at least min_corners rows.  Ties go to the lowest frame; every reduction runs in a fixed order: the
+ * result does not change from run to run.  A decreasing CSR array or a subrange outside its frame is CBA_ERR_INVALID, the message
+ * names the position.  n_frames == 0 or n_cams == 0 succeeds without a launch. */
+int cba_pose_select_frames(const cba_frame_select_desc* d, int32_t device, uint64_t* cell_mask_out, double* pose_feat_out, double* orient_out,
+                           int32_t* homog_status_out, double* homog_rmse_out, int32_t* selected_out, int32_t* n_selected_out,
+                           int32_t* n_anchors_out, int32_t* bin_mask_out, int32_t* eligible_out);
+
 #ifdef __cplusplus
 }
 #endif
