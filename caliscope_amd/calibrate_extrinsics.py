@@ -226,6 +226,7 @@ def calibrate_extrinsics(
     progress: Callable[[int, str], None] | None = None,
     estimate_poses: bool | str = False,
     estimate_intrinsics: bool = False,
+    device_filter: bool = False,
     _engine_factory=None,
     _triangulate=None,
     _pnp=None,
@@ -240,7 +241,9 @@ def calibrate_extrinsics(
     calibrated from the session's board views on the device (``caliscope_amd/calibrate_intrinsics.py``, all of them in one call)
     instead of receiving blind defaults, which also makes fisheye cameras without intrinsics usable; they are not listed in
     ``synthesized_cam_ids``.  A camera whose calibration does not solve, or ends at an implausible minimum (reprojection RMSE above
-    0.5 % of the image size, focal length outside 0.1 ... 10 image sizes), falls back to the blind defaults and is listed."""
+    0.5 % of the image size, focal length outside 0.1 ... 10 image sizes), falls back to the blind defaults and is listed.
+    ``device_filter=True``: the outlier filter between the passes is ``CaptureVolume.filter_outliers`` (errors, thresholds and keep mask
+    in one device call) instead of ``filter_by_percentile_error``; the same observations survive."""
     from copy import deepcopy
 
     from caliscope_amd.exceptions import CalibrationError
@@ -316,7 +319,8 @@ def calibrate_extrinsics(
                                          _triangulate=_triangulate, _pnp=_pnp, _epi=_epi)
     check_cancelled()
     run = refine_calibration(volume, refine_intrinsics=refine_intrinsics, filter_percentile=filter_percentile,
-                             cancellation_token=cancellation_token, progress=progress, _engine_factory=_engine_factory, _guard=False)
+                             cancellation_token=cancellation_token, progress=progress, device_filter=device_filter,
+                             _engine_factory=_engine_factory, _guard=False)
     estimates = _intrinsic_estimates(run.capture_volume, anchors)
     return CalibrationRun(run.capture_volume, estimates, frozenset(synthesized), tuple(dropped), run.intrinsic_refinement_gated)
 
@@ -328,10 +332,12 @@ def refine_calibration(
     filter_percentile: float = 2.5,
     cancellation_token=None,
     progress: Callable[[int, str], None] | None = None,
+    device_filter: bool = False,
     _engine_factory=None,
     _guard: bool = True,
 ) -> CalibrationRun:
-    """Stages 5-9 of ``calibrate_extrinsics`` on a bootstrapped volume (``_guard=False``: the caller has run the static-marker guard)."""
+    """Stages 5-9 of ``calibrate_extrinsics`` on a bootstrapped volume (``_guard=False``: the caller has run the static-marker guard;
+    ``device_filter=True``: stage 7 is ``filter_outliers``, one device call, instead of ``filter_by_percentile_error``)."""
 
     def check_cancelled():
         if cancellation_token is not None and getattr(cancellation_token, "is_cancelled", False):
@@ -370,7 +376,7 @@ def refine_calibration(
     check_cancelled()
 
     report(75, "Filtering outliers")
-    cv = cv.filter_by_percentile_error(filter_percentile, **kw)
+    cv = cv.filter_outliers(filter_percentile) if device_filter else cv.filter_by_percentile_error(filter_percentile, **kw)
     check_cancelled()
 
     report(90, "Re-optimizing")
