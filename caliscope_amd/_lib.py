@@ -68,6 +68,7 @@ class Info(C.Structure):
         ("max_obs_per_point", C.c_int32), ("device_bytes", C.c_int64),
         ("schur_groups", C.c_int32), ("schur_tiles", C.c_int32), ("schur_grid", C.c_int32), ("n_heavy_points", C.c_int32),
         ("schur_stream_len", C.c_int64), ("schur_pairs", C.c_int64), ("plan_error", C.c_int32), ("build_camg", C.c_int32),
+        ("spec_jv_skipped", C.c_int64),
     ]
 
 
@@ -135,6 +136,9 @@ SIGNATURES = {
     "cba_step": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(StepInfo)]),
     "cba_refresh_step_scalars": (C.c_int, [C.c_void_p, C.POINTER(NewtonInfo)]),
     "cba_step_supported": (C.c_int, [C.c_void_p]),
+    "cba_set_tolerances": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "cba_hint_last_trial": (C.c_int, [C.c_void_p]),
+    "cba_gradient_norm": (C.c_int, [C.c_void_p, c_double_p]),
     "cba_set_camera_scaling": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.POINTER(Linearization)]),
     "cba_set_bounds": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "cba_step_camera_state": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),

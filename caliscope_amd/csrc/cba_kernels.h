@@ -270,7 +270,21 @@ struct PubArgs {
   // bounded fused iteration: the camera blocks of x, g, the Jacobi scale and the damped step travel with the packet (the host driver keeps scipy's
   // select_step and the later trials of the iteration; four vectors of <= 1152 doubles instead of three host round trips for them)
   const double* cam_src[4]; double* cam_dst; int ncp;
+  // termination decided here too (spec_word != nullptr: cba_set_tolerances was called, unbounded solve): when the host driver's test (trf::termination on
+  // the same scalars) will end the solve at this trial point, the J.g pass of the speculative linearisation behind this launch has no reader; the word
+  // tells that k_jv launch to return at once, and slot n_scal - 1 of the packet tells the host.  cost_x: the cost at x (NaN: this iteration's own
+  // build evaluated x, 0.5 scal[8]).
+  int* spec_word; double ftol, xtol, cost_x;
 };
+// 1: the host will stop at this trial point (ta: its rho sum, tb: the squared step norm; both just summed by the packet workgroup)
+__device__ __forceinline__ int pub_solve_ends(const PubArgs& pub, double ta, double tb) {
+  const double cost_new = 0.5 * ta;
+  const double cost = isnan(pub.cost_x) ? 0.5 * pub.scal[8] : pub.cost_x;
+  if (pub.scal[42] != 0.0 || (pub.flags[0] | pub.flags[1] | pub.flags[2] | pub.flags[3]) != 0 || !isfinite(cost_new) || !isfinite(cost)) return 0;  // need_host, a failed pivot, a non-finite residual
+  const double actual = cost - cost_new;
+  const double ratio = trf::reduction_ratio(actual, pub.scal[45]);
+  return trf::termination(actual, cost, sqrt(tb), sqrt(pub.scal[2]), ratio, pub.ftol, pub.xtol) != trf::TERMINATION_NONE ? 1 : 0;
+}
 __global__ void __launch_bounds__(64 * REDUCE_RY)
 k_reduce_rows_pub(const double* __restrict__ partial, int nrow, int width, double* __restrict__ out, double* __restrict__ grad_out,
                   const int* __restrict__ cam_off, const int* __restrict__ cam_np, int stride, int tri, PubArgs pub) {
@@ -285,15 +299,18 @@ k_reduce_rows_pub(const double* __restrict__ partial, int nrow, int width, doubl
   a = wave_sum(a); b = wave_sum(b);
   if (threadIdx.x == 0) { sh_w[0][threadIdx.y] = a; sh_w[1][threadIdx.y] = b; }
   __syncthreads();
-  __shared__ double sh_tot[2];
+  __shared__ double sh_tot[3];
   if (t == 0) {
     double ta = 0.0, tb = 0.0;
     for (int i = 0; i < REDUCE_RY; ++i) { ta += sh_w[0][i]; tb += sh_w[1][i]; }
     pub.scal[pub.slot_a] = ta; pub.scal[pub.slot_b] = tb;
     sh_tot[0] = ta; sh_tot[1] = tb;
+    int ends = 0;
+    if (pub.spec_word) { ends = pub_solve_ends(pub, ta, tb); *pub.spec_word = ends; }  // (written every time: a word left set would silence the next solve's pass)
+    sh_tot[2] = (double)ends;
   }
   __syncthreads();
-  if (t < pub.n_scal) pub.host_scal[t] = (t == pub.slot_a) ? sh_tot[0] : (t == pub.slot_b) ? sh_tot[1] : own;
+  if (t < pub.n_scal) pub.host_scal[t] = (t == pub.slot_a) ? sh_tot[0] : (t == pub.slot_b) ? sh_tot[1] : (t == pub.n_scal - 1) ? sh_tot[2] : own;
   if (t < 4) { pub.host_flags[t] = pub.flags[t]; pub.flags[t] = 0; }
   if (pub.cam_dst)
     for (int e = t; e < 4 * pub.ncp; e += 64 * REDUCE_RY) pub.cam_dst[e] = pub.cam_src[e / pub.ncp][e % pub.ncp];
@@ -934,14 +951,41 @@ __global__ void k_combine(const double* __restrict__ g, const double* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
+// The one number a driver reads of a linearisation it stops at: max |g| over the rows k_scale_lin left (max_rows), straight to the host's mailbox
+// (slot MAIL_GNORM, then the sequence word MAIL_GNORM_SEQ: cba_gradient_norm polls it) — no launch of its own, no host round trip.  One workgroup.
+constexpr int MAIL_GNORM = 60, MAIL_GNORM_SEQ = 61;
+struct SpecSkip {
+  const int* word;          // != nullptr: the speculative J.g pass; *word != 0 (k_reduce_rows_pub): the solve ends at this point, return at once ...
+  const double* max_rows;   // ... after workgroup 0 has published max |g|
+  int n_rows;
+  double* mail; unsigned long long seq;
+};
+__device__ __forceinline__ void publish_gnorm(const SpecSkip& sk) {
+  __shared__ double sh_gn[BLOCK / WAVE];
+  double m = 0.0;
+  for (int b = threadIdx.x; b < sk.n_rows; b += BLOCK) m = fmax(m, sk.max_rows[b]);
+  m = block_max(m, sh_gn);
+  if (threadIdx.x == 0) {
+    sk.mail[MAIL_GNORM] = m;
+    __threadfence_system();
+    reinterpret_cast<volatile unsigned long long*>(sk.mail)[MAIL_GNORM_SEQ] = sk.seq;
+  }
+}
+// the same behind a trial the caller has announced as its last (no J.g pass is enqueued there)
+__global__ void __launch_bounds__(BLOCK) k_gnorm_pub(SpecSkip sk) { publish_gnorm(sk); }
+
 // J.v for one or two vectors: partial[b][0..2] = sum |Jv1|^2, <Jv1,Jv2>, |Jv2|^2
 template <int NC, int NV, bool CAMG = false>
 __global__ void __launch_bounds__(BLOCK)
 k_jv(const double* __restrict__ obs_u, const double* __restrict__ obs_v, const int* __restrict__ obs_cam,
      const int* __restrict__ obs_pt, long n_obs, const double* __restrict__ xvec, VecLayout lay,
      const double* __restrict__ tab, const int* __restrict__ cam_off, int n_cams, int loss, double f_scale,
-     const double* __restrict__ v1, const double* __restrict__ v2, double* __restrict__ partial) {
+     const double* __restrict__ v1, const double* __restrict__ v2, double* __restrict__ partial, SpecSkip skip = SpecSkip{}) {
   CBA_STAMP(ST_JV);
+  if (skip.word && *skip.word) {  // speculative pass of a trial point at which the solve ends (k_reduce_rows_pub): nobody reads the rows
+    if (blockIdx.x == 0) publish_gnorm(skip);
+    return;
+  }
   extern __shared__ __attribute__((aligned(16))) double sh[];
   double* sh_tab = sh;
   double* sh_v = sh_tab + (CAMG ? 0 : n_cams * CAMTAB_LDS);  // NV * ncp_pad

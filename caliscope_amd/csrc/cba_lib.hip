@@ -161,6 +161,18 @@ struct cba_problem {
   double* sinv2 = nullptr;
   bool spec_enqueued = false, spec_valid = false;
   int spec_rows_jv = 0;
+  // The J.g pass of that linearisation is the part nobody reads when the solve ends at the trial point (cba_solve then needs max |g| only:
+  // cba_gradient_norm).  With the tolerances known (cba_set_tolerances) the packet workgroup runs the driver's termination test and the pass returns at
+  // entry (spec_word, device); a trial the caller has announced as its last (cba_hint_last_trial) is not followed by the pass at all.  CBA_SPEC_SKIP=0: off.
+  bool spec_skip = true, tol_set = false, last_trial_hint = false;
+  double ftol = 0.0, xtol = 0.0;
+  int* spec_word = nullptr;        // flags + 4
+  bool spec_jv_enqueued = false;   // the speculative linearisation behind the last cba_step has its J.g pass ...
+  bool spec_jv_dropped = false;    // ... which the device skipped (packet slot 48)
+  bool spec_scale_ready = false;   // the accepted trial came with its speculative scale pass: partial1 holds the rows of max |g| at the current x
+  long spec_jv_skipped = 0;        // cba_info
+  unsigned long long gnorm_seq = 0;  // sequence word of the max |g| the last cba_step's speculation publishes by itself when the solve ends at its trial
+  bool gnorm_mailed = false;         // ... and it does: the accepted trial's pass was skipped on the device, or replaced by k_gnorm_pub
   bool lf_pending = false;  // the reductions of the linearisation and the damping are left to the next k_tprep (LinFin lf)
   LinFin lf{};
   bool have_x0 = false;
@@ -1247,7 +1259,8 @@ static int alloc_solver_buffers(cba_problem* p) {
   TRYS(dev_alloc(p, &p->Xinv, (size_t)((ncp + NB - 1) / NB + 1) * NB * NB));
   TRYS(dev_zeros(p, &p->Tinv, (size_t)ncp * p->ldw));
   TRYS(dev_alloc(p, &p->rhs, (size_t)p->lay.ncp_pad));
-  TRYS(dev_zeros(p, &p->scal, 64)); TRYS(dev_zeros(p, &p->flags, 4)); TRYS(dev_alloc(p, &p->xbuf, 128));
+  TRYS(dev_zeros(p, &p->scal, 64)); TRYS(dev_zeros(p, &p->flags, 8)); TRYS(dev_alloc(p, &p->xbuf, 128));
+  p->spec_word = p->flags + 4;  // (flags[0..3] travel with every packet)
   TRYS(dev_alloc(p, &p->fz, 8)); TRYS(dev_zeros(p, &p->V2, (size_t)6 * p->lay.Ppad)); TRYS(dev_zeros(p, &p->g2, (size_t)tot));
   TRYS(dev_alloc(p, &p->U2, (size_t)p->C * ustride + 128));
   return CBA_OK;
@@ -1298,6 +1311,7 @@ int cba_create(const cba_problem_desc* d, const cba_options* opt, cba_problem** 
   p->C = d->n_cams; p->P = d->n_points; p->N = d->n_obs;
   p->loss = d->loss; p->f_scale = d->f_scale;
   if (const char* e = std::getenv("CBA_REG_FINALIZE")) p->fuse_reg_finalize = e[0] != '0';
+  if (const char* e = std::getenv("CBA_SPEC_SKIP")) p->spec_skip = e[0] != '0';
 #ifdef CBA_PROFILING
   p->schur_clock = std::getenv("CBA_SCHUR_CLOCK") != nullptr;
   p->want_chol_trace = std::getenv("CBA_CHOL_TRACE") != nullptr;
@@ -1415,7 +1429,7 @@ int cba_set_loss(cba_problem* p, int32_t loss, double f_scale) {
   if (loss != CBA_LOSS_LINEAR && !(f_scale > 0.0)) return fail(CBA_ERR_INVALID, "cba_set_loss: f_scale must be positive");
   p->loss = loss; p->f_scale = f_scale;
   p->have_build = false;  // blocks and gradient of the current point belong to the old loss
-  p->spec_valid = false; p->spec_enqueued = false;
+  p->spec_valid = false; p->spec_enqueued = false; p->spec_scale_ready = false;
   return CBA_OK;
 }
 
@@ -1433,6 +1447,7 @@ int cba_get_info(cba_problem* p, cba_info* o) {
     o->build_camg = (camg ? 1 : 0) | (p->tab_global ? 2 : 0) | (cs ? 4 : 0) | (uglob ? 8 : 0) | (p->backsub_rec ? 16 : 0) |
                     (p->con.n_con && p->con.small ? 32 : 0);
   }
+  o->spec_jv_skipped = p->spec_jv_skipped;
   return CBA_OK;
 }
 
@@ -1598,7 +1613,7 @@ template <int NC>
 static int run_build(cba_problem* p) { return run_build_into<NC>(p, p->x, p->tab, p->V, p->g, p->Upacked, 8, nullptr, false, false, 3); }
 
 template <int NC>
-static int run_jv(cba_problem* p, int nv, int* rows_out = nullptr, const double* xvec = nullptr, const double* tab = nullptr) {
+static int run_jv(cba_problem* p, int nv, int* rows_out = nullptr, const double* xvec = nullptr, const double* tab = nullptr, const SpecSkip& skip = SpecSkip{}) {
   ScopedTimer t(p, T_JV);
   if (!xvec) { xvec = p->x; tab = p->tab; }  // (the speculative linearisation evaluates the trial point: x_new, tab_new)
   const int grid = nv == 1 ? p->jv_grid : (int)std::min<long>((p->N + BLOCK - 1) / BLOCK, 1024);
@@ -1607,7 +1622,7 @@ static int run_jv(cba_problem* p, int nv, int* rows_out = nullptr, const double*
     return fail(CBA_ERR_UNSUPPORTED, "run_jv: %d rows of k_jv and %d of k_con_jv exceed the %d rows of partial4", grid, con_rows, PARTIAL4_ROWS);
   auto launch_jv = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds_jv(p, nv), p->stream, p->obs_u, p->obs_v, p->obs_cam, p->obs_pt,
-                       p->N, xvec, p->lay, tab, p->cam_off, p->C, p->loss, p->f_scale, p->v1, p->v2, p->partial4);
+                       p->N, xvec, p->lay, tab, p->cam_off, p->C, p->loss, p->f_scale, p->v1, p->v2, p->partial4, skip);
   };
   if (nv == 1) { if (p->tab_global) launch_jv(k_jv<NC, 1, true>); else launch_jv(k_jv<NC, 1>); }
   else { if (p->tab_global) launch_jv(k_jv<NC, 2, true>); else launch_jv(k_jv<NC, 2>); }
@@ -1627,6 +1642,7 @@ static int run_jv(cba_problem* p, int nv, int* rows_out = nullptr, const double*
 template <int NC>
 static int run_lin_chain(cba_problem* p, bool scalars = true, bool compact = false, double radius = 0.0, bool defer_finish = false) {
   RoctxRange range("cba:linearize");
+  p->spec_scale_ready = false; p->gnorm_mailed = false;
   if (!p->have_build) {
     int rcb = run_build<NC>(p);
     if (rcb) return rcb;
@@ -2063,8 +2079,13 @@ static int step_enqueue(cba_problem* p, double radius, bool compact, unsigned lo
   // block's from k_step_cam, or k_trial_update's) leaves with the launch that reduces the trial build's camera blocks
   const unsigned long long seq = compact ? ++p->publish_seq : 0;
   const bool bnd = compact && p->bounds_on;
-  const PubArgs pub{p->scal, 48, p->flags, p->d_hscal, p->d_hflags, seq, p->partial1, p->grid, 24, p->partial4, ft ? p->grid + 1 : vg, 28,
-                    {p->x, p->g, p->sinv_state_c, p->s}, bnd ? p->d_hbcam : (double*)nullptr, p->ncp};
+  // (the termination test of the packet workgroup: unbounded solves whose tolerances are known; slot 48 reports it)
+  const bool last_trial = p->last_trial_hint;
+  p->last_trial_hint = false;
+  const bool spec_test = compact && p->spec_skip && p->tol_set && !p->bounds_on && !last_trial;
+  const PubArgs pub{p->scal, 49, p->flags, p->d_hscal, p->d_hflags, seq, p->partial1, p->grid, 24, p->partial4, ft ? p->grid + 1 : vg, 28,
+                    {p->x, p->g, p->sinv_state_c, p->s}, bnd ? p->d_hbcam : (double*)nullptr, p->ncp,
+                    spec_test ? p->spec_word : (int*)nullptr, p->ftol, p->xtol, p->cost_pending ? NAN : p->cost_x};
   rc = run_build_into<NC>(p, p->x_new, p->tab_new, p->V2, p->g2, p->U2, 24, p->scal + 42, true, compact, 0, ft ? &tsrc : nullptr,
                           compact ? &pub : nullptr);  // (the build is skipped when need_host; the reduction and the packet are not)
   if (rc) return rc;
@@ -2072,7 +2093,7 @@ static int step_enqueue(cba_problem* p, double radius, bool compact, unsigned lo
   *seq_out = seq;
   // speculative linearisation of the trial point, enqueued BEHIND the publish: the device works on it while the host reads the packet,
   // decides and enqueues the next iteration (k_publish -> host -> first kernel of the next cba_step used to be an idle gap per iteration)
-  p->spec_enqueued = false;
+  p->spec_enqueued = false; p->spec_jv_enqueued = false;
   {
     {
       ScopedTimer t(p, T_SCALE_SCALARS);
@@ -2082,9 +2103,19 @@ static int step_enqueue(cba_problem* p, double radius, bool compact, unsigned lo
                            (const double*)nullptr, p->x_new, p->g2, p->v1, p->partial4b, p->partial1, (const double*)p->sinv, ba2);
       };
       if (bnd) launch_sl2(k_scale_lin<NC, true>); else launch_sl2(k_scale_lin<NC, false>);
+    }
+    // max |g| of the trial point goes to the host's mailbox by itself where the solve ends there (workgroup 0 of the skipped pass, or a
+    // one-workgroup launch in the place of a pass that is not enqueued): cba_gradient_norm finds it waiting
+    const SpecSkip skip{spec_test ? p->spec_word : (const int*)nullptr, p->partial1, vg, p->d_hscal, seq};
+    p->gnorm_seq = seq;
+    if (!(p->spec_skip && last_trial)) {
       int rows_jv = 0;
-      rc = run_jv<NC>(p, 1, &rows_jv, p->x_new, p->tab_new);
+      rc = run_jv<NC>(p, 1, &rows_jv, p->x_new, p->tab_new, skip);
       p->spec_rows_jv = rows_jv;
+      p->spec_jv_enqueued = true;
+    } else {  // (the caller stops after this trial whatever it brings: max |g| is all it will ask for)
+      ScopedTimer t(p, T_SCALE_SCALARS);
+      hipLaunchKernelGGL(k_gnorm_pub, dim3(1), dim3(BLOCK), 0, p->stream, skip);
     }
     if (rc) return rc;
     p->spec_enqueued = true;
@@ -2117,6 +2148,8 @@ static int run_step(cba_problem* p, double radius, cba_step_info* out) {
     rc = sync_scalars(p, 48);
   }
   if (rc) return rc;
+  p->spec_jv_dropped = compact && p->h_scal[48] != 0.0;
+  if (p->spec_jv_dropped) ++p->spec_jv_skipped;
   const int bad_residual = p->h_flags[0];
   read_linearization(p, &out->lin);
   read_newton(p, &out->newton);
@@ -2140,6 +2173,57 @@ static int run_step(cba_problem* p, double radius, cba_step_info* out) {
   out->trial.step_norm = std::sqrt(p->h_scal[28]);
   out->trial.reserved = 0;
   p->trial_cost = c;
+  return CBA_OK;
+}
+
+// max |g| at the current x without the J.g pass (cba_gradient_norm)
+template <int NC>
+static int run_gradient_norm(cba_problem* p, double* out) {
+  // bounded and sharded solves, fixed-order sums, or the shortcut switched off: the whole linearisation, as before
+  if (!p->spec_skip || p->sharded() || p->bounds_on || p->cam_scaled || p->eval_only) {
+    cba_linearization lin;
+    const int rc = run_linearize<NC>(p, &lin);
+    if (rc) return rc;
+    p->linearized = true; p->stepped = false;
+    *out = lin.g_norm_inf;
+    return CBA_OK;
+  }
+  if (p->spec_scale_ready && p->gnorm_mailed) {  // on its way already (publish_gnorm): nothing to launch
+    volatile unsigned long long* word = reinterpret_cast<volatile unsigned long long*>(p->h_scal) + MAIL_GNORM_SEQ;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0; *word != p->gnorm_seq; ++spins) {
+      if ((spins & 0xfff) == 0xfff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
+        HIPCHK(hipStreamSynchronize(p->stream));  // something is wrong or very slow: let the runtime report it
+        if (*word != p->gnorm_seq) return fail(CBA_ERR_HIP, "the gradient norm of the accepted trial did not arrive");
+        break;
+      }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    *out = p->h_scal[MAIL_GNORM];
+    return CBA_OK;
+  }
+  const int vg = vec_grid(p->lay.total());
+  if (!p->spec_scale_ready) {  // the scale pass alone (run_lin_chain's, without J.g and the sums that need it)
+    if (!p->have_build) {
+      const int rcb = run_build<NC>(p);
+      if (rcb) return rcb;
+      p->cost_pending = true; p->have_build = true;
+    }
+    p->spec_valid = false;
+    ScopedTimer t(p, T_SCALE_SCALARS);
+    hipLaunchKernelGGL((k_scale_lin<NC, false>), dim3(vg), dim3(BLOCK), 0, p->stream, p->Upacked, p->V, p->param_cam, p->param_loc, p->lay, p->first_scale ? 1 : 0,
+                       p->sinv, p->con.n_con ? (const double*)p->con.cdiag : (const double*)nullptr, p->x, p->g, p->v1, p->partial4b, p->partial1,
+                       (const double*)nullptr, BoundArgs{});
+    p->first_scale = false;
+    p->spec_scale_ready = true;  // (asked again at the same point: the rows are still there)
+  }
+  {
+    ScopedTimer t(p, T_SCALE_SCALARS);
+    hipLaunchKernelGGL(k_reduce_narrow<true>, dim3(1), dim3(BLOCK), 0, p->stream, p->partial1, vg, 1, p->scal + 4);
+  }
+  const int rc = sync_scalars(p, 16);
+  if (rc) return rc;
+  *out = p->h_scal[4];
   return CBA_OK;
 }
 
@@ -2258,6 +2342,7 @@ static int begin_common(cba_problem* p, double* cost_out, bool evaluate) {
   // keep their x0 entries in BOTH buffers), scale 1, bound scaling and flags cleared, the camera table of x0: one launch (k_begin)
   p->cam_scaled = false; p->cam_state_saved = false;
   p->have_build = false; p->trial_built = false; p->cost_pending = false; p->lf_pending = false;
+  p->spec_scale_ready = false; p->gnorm_mailed = false; p->tol_set = false; p->last_trial_hint = false;
   {
     ScopedTimer t(p, T_CAM_PREP);
     double* trial_buf = (!p->eval_only && fused_trial(p, true)) ? p->x_new : nullptr;
@@ -2488,19 +2573,48 @@ int cba_accept(cba_problem* p) {
   if (!p->have_trial) return fail(CBA_ERR_INVALID, "cba_accept: no trial point");
   std::swap(p->x, p->x_new);
   std::swap(p->tab, p->tab_new);
-  p->spec_valid = false;
+  p->spec_valid = false; p->spec_scale_ready = false; p->gnorm_mailed = false;
   if (p->trial_built) {  // the trial point came with its own build (cba_step): it becomes the linearisation point as it is
     std::swap(p->V, p->V2); std::swap(p->g, p->g2); std::swap(p->Upacked, p->U2);
     p->cost_x = p->trial_cost;
     if (p->spec_enqueued) {  // ... and so does its speculative linearisation
-      std::swap(p->sinv, p->sinv2); p->spec_valid = true;
+      std::swap(p->sinv, p->sinv2);
       if (p->bounds_on) { std::swap(p->sinv_state_c, p->sinv_state_c2); std::swap(p->cam_diag, p->cam_diag2); }
+      // without its J.g pass (skipped on the device, or never enqueued) it is not complete: a caller that goes on linearises this point as usual
+      // (the scale pass again, on a Jacobi state that already holds its result, and J.g); one that stops reads max |g| from the scale pass's rows
+      p->spec_valid = p->spec_jv_enqueued && !p->spec_jv_dropped;
+      p->spec_scale_ready = true;
+      p->gnorm_mailed = !p->spec_valid;
     }
   }
   p->spec_enqueued = false;
   p->have_build = p->trial_built;
   p->trial_built = false;
   p->have_trial = false; p->linearized = false; p->stepped = false;
+  return CBA_OK;
+}
+
+int cba_set_tolerances(cba_problem* p, double ftol, double xtol) {
+  if (!p) return fail(CBA_ERR_INVALID, "cba_set_tolerances: null argument");
+  if (!(ftol >= 0.0) || !(xtol >= 0.0)) return fail(CBA_ERR_INVALID, "cba_set_tolerances: the tolerances must be >= 0");
+  p->ftol = ftol; p->xtol = xtol; p->tol_set = true;
+  return CBA_OK;
+}
+
+int cba_hint_last_trial(cba_problem* p) {
+  if (!p) return fail(CBA_ERR_INVALID, "cba_hint_last_trial: null argument");
+  p->last_trial_hint = true;
+  return CBA_OK;
+}
+
+int cba_gradient_norm(cba_problem* p, double* g_norm_inf) {
+  if (!p || !g_norm_inf) return fail(CBA_ERR_INVALID, "cba_gradient_norm: null argument");
+  if (p->eval_only) return fail(CBA_ERR_INVALID, "cba_gradient_norm: the problem was created with evaluation_only");
+  if (!p->begun) return fail(CBA_ERR_INVALID, "cba_gradient_norm: call cba_begin first");
+  HIPCHK(hipSetDevice(p->device));
+  const int rc = DISPATCH_NC(p, run_gradient_norm<6>(p, g_norm_inf), run_gradient_norm<9>(p, g_norm_inf));
+  if (rc) return rc;
+  HIPCHK(hipGetLastError());
   return CBA_OK;
 }
 

@@ -26,15 +26,7 @@ namespace {
 constexpr double SUBSPACE_EXPLICIT_BELOW = 1e-6;
 
 using trf::solve_subspace_2d;
-
-int termination(double dF, double F, double dx_norm, double x_norm, double ratio, double ftol, double xtol) {
-  const bool f_ok = dF < ftol * F && ratio > 0.25;
-  const bool x_ok = dx_norm < xtol * (xtol + x_norm);
-  if (f_ok && x_ok) return 4;
-  if (f_ok) return 2;
-  if (x_ok) return 3;
-  return -100;  // none
-}
+using trf::termination;  // (shared with the packet workgroup of the fused iteration, which runs the same test: cba_set_tolerances)
 
 
 // ---- bounded camera block (scipy trf_bounds, trf.py:205-398; helpers of common.py) -------------------------------
@@ -104,6 +96,17 @@ struct CallTrace {
 
 }  // namespace
 
+// An engine without the speculative linearisation (the dense CPU build of the tests) has nothing to skip: the three entries that steer it fall
+// back to these, and the gradient norm of the last point is the full linearisation's.  The device library defines its own (cba_lib.hip).
+extern "C" __attribute__((weak)) int cba_set_tolerances(cba_problem*, double, double) { return CBA_OK; }
+extern "C" __attribute__((weak)) int cba_hint_last_trial(cba_problem*) { return CBA_OK; }
+extern "C" __attribute__((weak)) int cba_gradient_norm(cba_problem* p, double* g_norm_inf) {
+  cba_linearization lin;
+  const int rc = cba_linearize(p, &lin);
+  if (!rc && g_norm_inf) *g_norm_inf = lin.g_norm_inf;
+  return rc;
+}
+
 extern "C" int cba_solve(cba_problem* p, const double* x0, const cba_solve_options* opt_in, double* x_out, cba_result* out) {
   if (!p || !out) return cba_set_error(CBA_ERR_INVALID, "cba_solve: null argument");
   cba_solve_options opt;
@@ -166,12 +169,14 @@ extern "C" int cba_solve(cba_problem* p, const double* x0, const cba_solve_optio
   } else {
     (void)cba_set_bounds(p, nullptr, nullptr);
   }
+  if (!bounded && (rc = cba_set_tolerances(p, opt.ftol, opt.xtol))) return rc;  // the device ends the speculation of a trial point the test below stops at
   bool fused = (!bounded || bounds_on_device) && cba_step_supported(p);
   bool fuse_next = fused;
   int n_outside = 0;  // bounded fused steps whose first trial point left the box
   cba_linearization lin;
   cba_step_info si;
   bool lin_valid = false;    // `lin` describes the current x
+  bool accepted = false;     // the last thing that happened to x was cba_accept
   double radius = NAN;  // set from ||x0 * scale_inv (/ sqrt(v))|| on the first pass
   int status = -100;
   double g_norm = NAN, step_norm = NAN, actual = NAN;
@@ -182,8 +187,12 @@ extern "C" int cba_solve(cba_problem* p, const double* x0, const cba_solve_optio
     bool have_step = false;  // `si` holds this iteration's damped step and first trial
     if (!lin_valid) {
       if (status == -100 && fuse_next && nfev < max_nfev) {
+        if (nfev + 1 >= max_nfev && (rc = cba_hint_last_trial(p))) return rc;  // the loop ends after this step's trial whatever it brings
         if ((rc = calls.run("step", [&] { return cba_step(p, std::isnan(radius) ? -1.0 : radius, &si); }))) return rc;
         lin = si.lin; have_step = true;
+      } else if (!bounded && accepted && (status != -100 || nfev >= max_nfev)) {
+        // the loop ends below: of the linearisation of the accepted point only max |g| is read (optimality, and status 1 in the place of 2 .. 4)
+        if ((rc = calls.run("gradient_norm", [&] { return cba_gradient_norm(p, &lin.g_norm_inf); }))) return rc;
       } else if (bounded) {
         fuse_next = false;  // (THIS iteration runs on the primitives — the two routes keep the same scaling state; the first trial decides below
                             // whether the next one is fused again, and after two trial points on a bound the solve stays here: n_outside)
@@ -389,10 +398,7 @@ extern "C" int cba_solve(cba_problem* p, const double* x0, const cba_solve_optio
       // speculate again only after an accepted first trial of a well-conditioned subspace (a collinear step needs the
       // explicit J.v model, which cba_step leaves to the host)
       if (was_first) fuse_next = fused && actual > 0 && w_sq > 1e-2 * st.p_sq;  // (cba_step needs w_sq > 1e-3 p_sq: hysteresis)
-      double ratio;
-      if (predicted > 0) ratio = actual / predicted;
-      else if (predicted == 0 && actual == 0) ratio = 1.0;
-      else ratio = 0.0;
+      const double ratio = trf::reduction_ratio(actual, predicted);
       double radius_new = radius;
       if (ratio < 0.25) radius_new = 0.25 * step_h_norm;
       else if (ratio > 0.75 && step_h_norm > 0.95 * radius) radius_new = 2.0 * radius;
@@ -403,6 +409,7 @@ extern "C" int cba_solve(cba_problem* p, const double* x0, const cba_solve_optio
     }
     if (actual > 0) {
       if ((rc = calls.run("accept", [&] { return cba_accept(p); }))) return rc;
+      accepted = true;
       cost = cost_new;
       lin_valid = false;  // linearised at the top of the next pass (by cba_step when fused)
       ++njev;

@@ -1,6 +1,7 @@
 // Scalar pieces of the trust-region loop shared by the host driver (cba_solve.cpp) and the device-side step of the
-// fused iteration (cba_kernels.h): the 1-D model minimum behind the regularisation rule and the 2-D subspace
-// trust-region solve (scipy common.py:171-219).  Real arithmetic only, so the same code runs on both sides.
+// fused iteration (cba_kernels.h): the 1-D model minimum behind the regularisation rule, the 2-D subspace
+// trust-region solve (scipy common.py:171-219) and the termination test of an evaluated trial point (common.py:
+// check_termination).  Real arithmetic only, so the same code runs on both sides.
 #pragma once
 #include <math.h>
 
@@ -160,6 +161,26 @@ TRF_HD inline void subspace_model(double H_gg, double gh_sq, double lam, double 
   *b00 = H_gg / gh_sq;
   *b01 = (H_gp - c * H_gg) / (gh_norm * w_norm);
   *b11 = (H_pp - 2.0 * c * H_gp + c * c * H_gg) / w_sq;
+}
+
+// actual / predicted reduction of a trial point (trf.py:513-516 through common.py update_tr_radius)
+TRF_HD inline double reduction_ratio(double actual, double predicted) {
+  if (predicted > 0.0) return actual / predicted;
+  if (predicted == 0.0 && actual == 0.0) return 1.0;
+  return 0.0;
+}
+
+// scipy's check_termination (common.py): 2 ftol, 3 xtol, 4 both, TERMINATION_NONE otherwise.  The host driver decides with it whether the solve
+// ends at a trial point; the packet workgroup of a fused iteration runs it on the same scalars to tell the speculative J.g pass behind it that
+// nobody will read its result (k_reduce_rows_pub).
+constexpr int TERMINATION_NONE = -100;
+TRF_HD inline int termination(double dF, double F, double dx_norm, double x_norm, double ratio, double ftol, double xtol) {
+  const bool f_ok = dF < ftol * F && ratio > 0.25;
+  const bool x_ok = dx_norm < xtol * (xtol + x_norm);
+  if (f_ok && x_ok) return 4;
+  if (f_ok) return 2;
+  if (x_ok) return 3;
+  return TERMINATION_NONE;
 }
 
 }  // namespace trf

@@ -192,6 +192,21 @@ int cba_step(cba_problem* p, double radius, cba_step_info* out);
 int cba_refresh_step_scalars(cba_problem* p, cba_newton_info* out);
 int cba_step_supported(cba_problem* p);
 
+/* Behind its packet cba_step linearises the trial point speculatively (scale pass, then the J.g pass) so that an accepted trial is ready for the next
+ * cba_step.  When the caller STOPS at that trial point it reads one number of all that, max |g|, and the J.g pass (a pass over the observations) was
+ * for nothing.  Three calls let a driver avoid it; each is optional and none changes a result:
+ *   cba_set_tolerances   ftol, xtol of the driver's termination test (scipy's check_termination: csrc/trf_math.h, the code the driver itself runs).
+ *                        The device then runs the test on the trial's scalars and the J.g pass behind a trial that passes it returns at once.
+ *                        Unbounded single-rank solves; holds until the next cba_begin / cba_restart.  A handle that never had it called never skips.
+ *   cba_hint_last_trial  the trial of the NEXT cba_step is the last evaluation the caller's budget allows: no J.g pass is enqueued behind it.
+ *   cba_gradient_norm    ||J^T f||_inf at the current x after cba_accept, in the place of the cba_linearize a driver would call just to read
+ *                        g_norm_inf before it returns: the max over the speculative scale pass's rows when the accepted trial brought one, else the
+ *                        scale pass alone; never J.g.  (Bounded or sharded handles and CBA_SPEC_SKIP=0: the full linearisation.)
+ * cba_info.spec_jv_skipped counts the passes the device skipped. */
+int cba_set_tolerances(cba_problem* p, double ftol, double xtol);
+int cba_hint_last_trial(cba_problem* p);
+int cba_gradient_norm(cba_problem* p, double* g_norm_inf);
+
 /* ---- bounded camera parameters (scipy trf_bounds, trf.py:205-398) ------------------------------------
  * With finite bounds (free intrinsics: s, k1, k2 of BundleParameterization.bounds()) scipy rescales every bounded
  * variable by the Coleman-Li vector v (distance to the bound the gradient points at) and adds the diagonal
@@ -342,6 +357,7 @@ typedef struct {
                                bit 5: the constraint rows run the small-component kernels (k_con_schur_small / k_con_backsub_small: every
                                component has at most 64 rows and its dense blocks fit 120 KB of LDS, no heavy points; CBA_CON_SMALL=0 turns them
                                off); 0 without constraint rows. */
+  int64_t spec_jv_skipped;  /* speculative J.g passes the device skipped because the solve ended at their trial point (cba_set_tolerances) */
 } cba_info;
 int cba_get_info(cba_problem* p, cba_info* out);
 
