@@ -1,0 +1,14 @@
+"""caliscope_amd: multi-camera calibration and reconstruction on the MI355X.  The sub-modules are imported by name; the two entry points
+of the per-recording stage are also reachable from the package (loaded on first use, so that importing the package stays as cheap)."""
+
+_EXPORTS = {"reconstruct_trajectories": "caliscope_amd.reconstruction", "reconstruct_xyz": "caliscope_amd.reconstruction"}
+
+__all__ = sorted(_EXPORTS)
+
+
+def __getattr__(name):
+    if name in _EXPORTS:
+        import importlib
+
+        return getattr(importlib.import_module(_EXPORTS[name]), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,170 @@
+// cba_reconstruct_trajectories of libcaliscope_ba.so (C ABI: include/caliscope_trajectory.h): the 2-D tracks of a whole recording
+// to filled, triangulated, filled and smoothed 3-D trajectories on one dense grid.  What a thread does, and the checks, are
+// trajectory_math.h (shared with tests/native/trajectory_harness.cpp); this file holds the kernels and the entry point.
+//
+//   k_traj_fill2d       one thread per uploaded row (sorted by camera, trajectory, frame): the row's cell of xy[c][s][2] / ft[c][s],
+//                       and the first min(hole, xy_gap) cells of the hole between it and the next row of its track.  Holes of
+//                       different rows are disjoint and no row lies in a hole (the checks refuse duplicates), so nothing is
+//                       written twice.  Both grids are NaN (all bits set) before it runs.
+//   k_traj_frame_time   one thread per frame: mean of the times of the frame in a fixed order.
+//   k_traj_triangulate  one thread per slot s = f * n_traj + j; neighbouring threads read neighbouring cells of every camera's grid.
+//   k_traj_fill3d       one thread per slot, in place (see traj_fill3d_cell for why that is safe).
+//   k_traj_filtfilt     one thread per (trajectory, coordinate); thread t reads xyz[f][t] and its scratch column scratch[e][t], so
+//                       a wave's loads and stores are contiguous.
+//
+// Null stream throughout: the launches of a call run in the order they were issued.  Nothing is added with atomics.
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "trajectory_math.h"
+#include "device_call.h"
+
+using namespace cba;
+
+namespace {
+
+__global__ void __launch_bounds__(TRAJ_BLOCK)
+k_traj_fill2d(int64_t n_rows, int64_t n_traj, int64_t n_slots, const int32_t* __restrict__ row_cam, const int64_t* __restrict__ row_slot,
+              const double* __restrict__ row_xy, const double* __restrict__ row_time, int max_gap, double* __restrict__ xy, double* __restrict__ ft) {
+  const int64_t i = (int64_t)blockIdx.x * TRAJ_BLOCK + threadIdx.x;
+  if (i >= n_rows) return;
+  traj_fill2d_row(n_rows, n_traj, n_slots, i, row_cam, row_slot, row_xy, row_time, max_gap, xy, ft);
+}
+
+__global__ void __launch_bounds__(TRAJ_BLOCK)
+k_traj_frame_time(int32_t n_cams, int64_t n_frames, int64_t n_traj, int64_t n_slots, const double* __restrict__ ft, double* __restrict__ frame_time) {
+  const int64_t f = (int64_t)blockIdx.x * TRAJ_BLOCK + threadIdx.x;
+  if (f >= n_frames) return;
+  frame_time[f] = traj_frame_mean(n_cams, n_traj, n_slots, f, ft);
+}
+
+__global__ void __launch_bounds__(TRAJ_BLOCK)
+k_traj_triangulate(int32_t n_cams, int64_t n_traj, int64_t n_slots, const uint8_t* __restrict__ cam_posed, const int32_t* __restrict__ cam_model,
+                   const double* __restrict__ cam_intr, const double* __restrict__ cam_P, const double* __restrict__ xy,
+                   const double* __restrict__ frame_time, int f32, double* __restrict__ xyz, uint8_t* __restrict__ valid, double* __restrict__ time) {
+  const int64_t s = (int64_t)blockIdx.x * TRAJ_BLOCK + threadIdx.x;
+  if (s >= n_slots) return;
+  double p[3];
+  const int views = traj_triangulate_slot(n_cams, n_slots, s, cam_posed, cam_model, cam_intr, cam_P, xy, f32, p);
+  xyz[3 * s] = p[0];
+  xyz[3 * s + 1] = p[1];
+  xyz[3 * s + 2] = p[2];
+  valid[s] = views >= 2 ? 1 : 0;
+  time[s] = views >= 2 ? frame_time[s / n_traj] : traj_nan();
+}
+
+__global__ void __launch_bounds__(TRAJ_BLOCK)
+k_traj_fill3d(int64_t n_frames, int64_t n_traj, int64_t n_slots, int max_gap, uint8_t* valid, double* xyz, double* time) {
+  const int64_t s = (int64_t)blockIdx.x * TRAJ_BLOCK + threadIdx.x;
+  if (s >= n_slots) return;
+  traj_fill3d_cell(n_frames, n_traj, s, max_gap, valid, xyz, time);
+}
+
+__global__ void __launch_bounds__(TRAJ_BLOCK)
+k_traj_filtfilt(int64_t n_frames, int64_t n_traj, int order, const double* __restrict__ b, const double* __restrict__ a, const double* __restrict__ zi,
+                const uint8_t* __restrict__ valid, double* xyz, double* scratch) {
+  const int64_t t = (int64_t)blockIdx.x * TRAJ_BLOCK + threadIdx.x;
+  if (t >= 3 * n_traj) return;
+  traj_filtfilt_thread(n_frames, n_traj, t, order, b, a, zi, valid, xyz, scratch);
+}
+
+unsigned blocks(int64_t n) { return (unsigned)((n + TRAJ_BLOCK - 1) / TRAJ_BLOCK); }
+
+}  // namespace
+
+extern "C" int cba_reconstruct_trajectories(const cba_traj_desc* d, int32_t device, cba_traj_out* out) {
+  const char* what = "cba_reconstruct_trajectories";
+  if (!d || !out) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
+  // everything that does not need the device first: the sizes, the filter, every index the kernels use
+  std::string msg;
+  int rc = traj_validate(d, (double)d->memory_limit, msg);  // (memory_limit 0: the free memory is asked for below)
+  if (rc) return err(rc, msg);
+  const int32_t n_cams = d->n_cams;
+  const int64_t n_frames = d->n_frames, n_traj = d->n_traj, n_rows = d->n_rows, n_slots = n_frames * n_traj;
+  if (n_rows == 0) {
+    const double nan = traj_nan();
+    for (int64_t s = 0; s < n_slots; ++s) {
+      if (out->xyz) out->xyz[3 * s] = out->xyz[3 * s + 1] = out->xyz[3 * s + 2] = nan;
+      if (out->valid) out->valid[s] = 0;
+      if (out->slot_time) out->slot_time[s] = nan;
+    }
+    for (int64_t f = 0; f < n_frames; ++f)
+      if (out->frame_time) out->frame_time[f] = nan;
+    for (int64_t i = 0; i < (int64_t)n_cams * n_slots; ++i) {
+      if (out->xy_filled) out->xy_filled[2 * i] = out->xy_filled[2 * i + 1] = nan;
+      if (out->ft_filled) out->ft_filled[i] = nan;
+    }
+    return CBA_OK;
+  }
+  rc = select_device(device, what);
+  if (rc) return rc;
+  double memory = (double)d->memory_limit;
+  if (d->memory_limit <= 0) {
+    size_t free_bytes = 0, total_bytes = 0;
+    if (hipMemGetInfo(&free_bytes, &total_bytes) != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": hipMemGetInfo failed");
+    memory = (double)free_bytes;
+  }
+  if (traj_device_bytes(d) > memory) {
+    rc = traj_validate(d, memory, msg);  // (puts the message together)
+    return err(rc ? rc : CBA_ERR_UNSUPPORTED, msg);
+  }
+  if (n_slots > (int64_t)0x7fffffff * TRAJ_BLOCK || n_rows > (int64_t)0x7fffffff * TRAJ_BLOCK)
+    return err(CBA_ERR_UNSUPPORTED, std::string(what) + ": more workgroups than one launch takes");
+
+  Buffers buf;
+  void *dposed = nullptr, *dmodel = nullptr, *dintr = nullptr, *dP = nullptr, *drcam = nullptr, *drslot = nullptr, *drxy = nullptr, *drt = nullptr;
+  void *dxy = nullptr, *dft = nullptr, *dframe = nullptr, *dxyz = nullptr, *dvalid = nullptr, *dtime = nullptr;
+  void *db = nullptr, *da = nullptr, *dzi = nullptr, *dscratch = nullptr;
+  const size_t cells = (size_t)n_cams * (size_t)n_slots;
+  rc = buf.up(d->cam_posed, (size_t)n_cams, &dposed);
+  if (!rc) rc = buf.up(d->cam_model, (size_t)n_cams * sizeof(int32_t), &dmodel);
+  if (!rc) rc = buf.up(d->cam_intr, (size_t)n_cams * 9 * sizeof(double), &dintr);
+  if (!rc) rc = buf.up(d->cam_P, (size_t)n_cams * 12 * sizeof(double), &dP);
+  if (!rc) rc = buf.up(d->row_cam, (size_t)n_rows * sizeof(int32_t), &drcam);
+  if (!rc) rc = buf.up(d->row_slot, (size_t)n_rows * sizeof(int64_t), &drslot);
+  if (!rc) rc = buf.up(d->row_xy, (size_t)n_rows * 2 * sizeof(double), &drxy);
+  if (!rc) rc = buf.up(d->row_time, (size_t)n_rows * sizeof(double), &drt);
+  if (!rc) rc = buf.up(nullptr, cells * 2 * sizeof(double), &dxy);
+  if (!rc) rc = buf.up(nullptr, cells * sizeof(double), &dft);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * sizeof(double), &dframe);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_slots * 3 * sizeof(double), &dxyz);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_slots, &dvalid);
+  if (!rc) rc = buf.up(nullptr, (size_t)n_slots * sizeof(double), &dtime);
+  const int order = d->filter_b ? d->filter_order : 0;
+  const size_t scratch_bytes = (size_t)(n_frames + 2 * traj_pad(order)) * (size_t)n_traj * 3 * sizeof(double);
+  if (!rc && d->filter_b) rc = buf.up(d->filter_b, (size_t)(order + 1) * sizeof(double), &db);
+  if (!rc && d->filter_b) rc = buf.up(d->filter_a, (size_t)(order + 1) * sizeof(double), &da);
+  if (!rc && d->filter_b) rc = buf.up(d->filter_zi, (size_t)order * sizeof(double), &dzi);
+  if (!rc && d->filter_b) rc = buf.up(nullptr, scratch_bytes, &dscratch);
+  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
+
+  // all bits set is a NaN: "no row here"
+  hipError_t e = hipMemsetAsync(dxy, 0xff, cells * 2 * sizeof(double), 0);
+  if (e == hipSuccess) e = hipMemsetAsync(dft, 0xff, cells * sizeof(double), 0);
+  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  hipLaunchKernelGGL(k_traj_fill2d, dim3(blocks(n_rows)), dim3(TRAJ_BLOCK), 0, 0, n_rows, n_traj, n_slots, (const int32_t*)drcam, (const int64_t*)drslot,
+                     (const double*)drxy, (const double*)drt, (int)d->xy_gap, (double*)dxy, (double*)dft);
+  hipLaunchKernelGGL(k_traj_frame_time, dim3(blocks(n_frames)), dim3(TRAJ_BLOCK), 0, 0, n_cams, n_frames, n_traj, n_slots, (const double*)dft,
+                     (double*)dframe);
+  hipLaunchKernelGGL(k_traj_triangulate, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), 0, 0, n_cams, n_traj, n_slots, (const uint8_t*)dposed,
+                     (const int32_t*)dmodel, (const double*)dintr, (const double*)dP, (const double*)dxy, (const double*)dframe, d->float32_io ? 1 : 0,
+                     (double*)dxyz, (uint8_t*)dvalid, (double*)dtime);
+  if (d->xyz_gap > 0)
+    hipLaunchKernelGGL(k_traj_fill3d, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), 0, 0, n_frames, n_traj, n_slots, (int)d->xyz_gap, (uint8_t*)dvalid,
+                       (double*)dxyz, (double*)dtime);
+  if (d->filter_b)
+    hipLaunchKernelGGL(k_traj_filtfilt, dim3(blocks(3 * n_traj)), dim3(TRAJ_BLOCK), 0, 0, n_frames, n_traj, order, (const double*)db, (const double*)da,
+                       (const double*)dzi, (const uint8_t*)dvalid, (double*)dxyz, (double*)dscratch);
+  e = hipGetLastError();
+  if (e == hipSuccess && out->xyz) e = hipMemcpy(out->xyz, dxyz, (size_t)n_slots * 3 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out->valid) e = hipMemcpy(out->valid, dvalid, (size_t)n_slots, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out->slot_time) e = hipMemcpy(out->slot_time, dtime, (size_t)n_slots * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out->frame_time) e = hipMemcpy(out->frame_time, dframe, (size_t)n_frames * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out->xy_filled) e = hipMemcpy(out->xy_filled, dxy, cells * 2 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out->ft_filled) e = hipMemcpy(out->ft_filled, dft, cells * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  return CBA_OK;
+}
