@@ -11,6 +11,8 @@ import ctypes as C
 import os
 from pathlib import Path
 
+import numpy as np
+
 from caliscope_amd.exceptions import BackendError
 
 LIB_NAME = "libcaliscope_ba.so"
@@ -19,6 +21,16 @@ LIB_PATH = Path(__file__).resolve().parent / LIB_NAME
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
 c_int64_p = C.POINTER(C.c_int64)
+c_uint8_p = C.POINTER(C.c_uint8)
+c_uint64_p = C.POINTER(C.c_uint64)
+_POINTER_OF = {np.dtype(t): p for t, p in ((np.float64, c_double_p), (np.int32, c_int32_p), (np.int64, c_int64_p), (np.uint8, c_uint8_p),
+                                           (np.uint64, c_uint64_p))}
+
+
+def ptr(a):
+    """The pointer to the elements of a contiguous array, typed by its dtype (so that ctypes refuses an array of the wrong one);
+    None stays None."""
+    return None if a is None else a.ctypes.data_as(_POINTER_OF[a.dtype])
 
 
 class ProblemDesc(C.Structure):
@@ -170,6 +182,23 @@ SIGNATURES = {
 }
 
 _lib = None
+_bound: set[int] = set()  # id() of the signature tables (module-level dictionaries) typed so far on the one library load() keeps
+
+
+def bind(lib: C.CDLL, signatures: dict) -> C.CDLL:
+    """Type the functions of a signature table (``SIGNATURES``, or the table of a module whose calls are declared outside
+    include/caliscope_ba.h: ``POSE_SIGNATURES`` and the like) on ``lib``, once per table; returns ``lib``.  ``lib`` is the one library
+    ``load()`` keeps and a table a module-level dictionary that is never rebuilt: a table is remembered by ``id()`` alone."""
+    if id(signatures) not in _bound:
+        for name, (res, args) in signatures.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as exc:
+                raise BackendError(f"{lib._name} does not export {name} (stale build?)") from exc
+            fn.restype = res
+            fn.argtypes = args
+        _bound.add(id(signatures))
+    return lib
 
 
 def load() -> C.CDLL:
@@ -187,14 +216,8 @@ def load() -> C.CDLL:
         lib = C.CDLL(str(path))
     except OSError as exc:  # missing ROCm runtime etc.
         raise BackendError(f"could not load {path}: {exc}") from exc
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise BackendError(f"{path} does not export {name} (stale build?)") from exc
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
+    _bound.clear()  # (a new library object: nothing is typed on it yet)
+    _lib = bind(lib, SIGNATURES)
     return lib
 
 

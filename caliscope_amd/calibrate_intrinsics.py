@@ -33,7 +33,6 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from caliscope_amd import _lib
-from caliscope_amd.exceptions import BackendError
 from caliscope_amd.frame_selector import IntrinsicCoverageReport, rig_cameras, select_calibration_frames, select_rig
 
 logger = logging.getLogger(__name__)
@@ -57,21 +56,6 @@ INTRINSICS_SIGNATURES = {
 }
 
 
-def _load():
-    lib = _lib.load()
-    for name, (res, args) in INTRINSICS_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise BackendError(f"{_lib.LIB_PATH} does not export {name} (stale build?)") from exc
-        fn.restype, fn.argtypes = res, args
-    return lib
-
-
-def _ptr(a, ctype=C.c_double):
-    return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
-
-
 class DeviceIntrinsics:
     """The device call ``cba_pose_intrinsics_batch`` on ``device_id``."""
 
@@ -81,7 +65,7 @@ class DeviceIntrinsics:
     def intrinsics_batch(self, cam_model, cam_size, cam_start, view_start, view_cam, obs_xy, obs_obj, float32_io=True, max_iter=0):
         """Returns ``(intr[n_cams, 9], rmse[n_cams], status[n_cams], iters[n_cams], pose[n_views, 12], view_rmse[n_views],
         view_status[n_views])``; ``cam_start`` may be None (default start values)."""
-        lib = _load()
+        lib = _lib.bind(_lib.load(), INTRINSICS_SIGNATURES)
         cam_model = np.ascontiguousarray(cam_model, dtype=np.int32)
         cam_size = np.ascontiguousarray(cam_size, dtype=np.float64).reshape(-1, 2)
         cam_start = None if cam_start is None else np.ascontiguousarray(cam_start, dtype=np.float64).reshape(-1, 9)
@@ -96,11 +80,11 @@ class DeviceIntrinsics:
         intr, rmse = np.zeros((n_cams, 9)), np.zeros(n_cams)
         status, iters = np.zeros(n_cams, dtype=np.int32), np.zeros(n_cams, dtype=np.int32)
         pose, view_rmse, view_status = np.zeros((n_views, 12)), np.zeros(n_views), np.zeros(n_views, dtype=np.int32)
-        desc = IntrinsicsDesc(n_cams=n_cams, cam_model=_ptr(cam_model, C.c_int32), cam_size=_ptr(cam_size), cam_start=_ptr(cam_start),
-                              n_views=n_views, view_start=_ptr(view_start, C.c_int64), view_cam=_ptr(view_cam, C.c_int32), obs_xy=_ptr(obs_xy),
-                              obs_obj=_ptr(obs_obj), float32_io=1 if float32_io else 0, max_iter=int(max_iter))
-        rc = lib.cba_pose_intrinsics_batch(C.byref(desc), self.device_id, _ptr(intr), _ptr(rmse), _ptr(status, C.c_int32), _ptr(iters, C.c_int32),
-                                           _ptr(pose), _ptr(view_rmse), _ptr(view_status, C.c_int32))
+        desc = IntrinsicsDesc(n_cams=n_cams, cam_model=_lib.ptr(cam_model), cam_size=_lib.ptr(cam_size), cam_start=_lib.ptr(cam_start),
+                              n_views=n_views, view_start=_lib.ptr(view_start), view_cam=_lib.ptr(view_cam), obs_xy=_lib.ptr(obs_xy),
+                              obs_obj=_lib.ptr(obs_obj), float32_io=1 if float32_io else 0, max_iter=int(max_iter))
+        rc = lib.cba_pose_intrinsics_batch(C.byref(desc), self.device_id, _lib.ptr(intr), _lib.ptr(rmse), _lib.ptr(status), _lib.ptr(iters),
+                                           _lib.ptr(pose), _lib.ptr(view_rmse), _lib.ptr(view_status))
         _lib.check(lib, rc, "cba_pose_intrinsics_batch")
         return intr, rmse, status, iters, pose, view_rmse, view_status
 

@@ -95,17 +95,6 @@ COVERAGE_SIGNATURES = {
 }
 
 
-def _load():
-    lib = _lib.load()
-    for name, (res, args) in COVERAGE_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise BackendError(f"{_lib.LIB_PATH} does not export {name} (stale build?)") from exc
-        fn.restype, fn.argtypes = res, args
-    return lib
-
-
 def check_coverage_arguments(obs_key, obs_cam, n_cams, n_keys, slab_words):
     """The arrays of a ``coverage_counts`` call in the layout of ``cba_coverage_desc`` (``ValueError`` for mismatched lengths or a
     negative size; the range of every key and camera index is the library's check)."""
@@ -129,11 +118,11 @@ class DeviceCoverageCounts:
         (``obs_key``, ``obs_cam``); camera -1 is skipped.  ``slab_words``: 64-bit words of the key range per pass (0: the library's
         default); the result does not depend on it."""
         obs_key, obs_cam, n_cams, n_keys, slab_words = check_coverage_arguments(obs_key, obs_cam, n_cams, n_keys, slab_words)
-        lib = _load()
+        lib = _lib.bind(_lib.load(), COVERAGE_SIGNATURES)
         counts = np.zeros((n_cams, n_cams), dtype=np.int64)
-        desc = CoverageDesc(n_cams=n_cams, n_keys=n_keys, n_obs=len(obs_key), obs_key=obs_key.ctypes.data_as(_lib.c_int64_p),
-                            obs_cam=obs_cam.ctypes.data_as(_lib.c_int32_p), slab_words=slab_words)
-        _lib.check(lib, lib.cba_coverage_counts(C.byref(desc), self.device_id, counts.ctypes.data_as(_lib.c_int64_p)), "cba_coverage_counts")
+        desc = CoverageDesc(n_cams=n_cams, n_keys=n_keys, n_obs=len(obs_key), obs_key=_lib.ptr(obs_key),
+                            obs_cam=_lib.ptr(obs_cam), slab_words=slab_words)
+        _lib.check(lib, lib.cba_coverage_counts(C.byref(desc), self.device_id, _lib.ptr(counts)), "cba_coverage_counts")
         return counts
 
 

@@ -13,6 +13,7 @@
 // One upload per input array; memset, mark and gram per slab on the null stream; one copy-back; no host synchronisation in between.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 
 #include "../../include/caliscope_coverage.h"
@@ -93,13 +94,16 @@ extern "C" int cba_coverage_counts(const cba_coverage_desc* d, int32_t device, i
   rc = select_device(device, what);
   if (rc) return rc;
   Buffers buf;
-  void *dkey = nullptr, *dcam = nullptr, *dbits = nullptr, *dcounts = nullptr;
+  const int64_t* dkey = buf.in(d->obs_key, n_obs);
+  const int32_t* dcam = buf.in(d->obs_cam, n_obs);
+  uint64_t* dbits = buf.make<uint64_t>(n_cams, plan.stride);
+  int64_t* dcounts = buf.make<int64_t>(n_counts);
+  if (buf.status()) return buf.result(what);
+  // the 64-bit atomics are declared on unsigned long long: the same words as uint64_t / int64_t under another name
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "bit words and counts are passed as unsigned long long");
+  unsigned long long* dbits_atomic = (unsigned long long*)dbits;
+  unsigned long long* dcounts_atomic = (unsigned long long*)dcounts;
   const size_t bits_bytes = (size_t)n_cams * (size_t)plan.stride * sizeof(uint64_t);
-  rc = buf.up(d->obs_key, (size_t)n_obs * sizeof(int64_t), &dkey);
-  if (!rc) rc = buf.up(d->obs_cam, (size_t)n_obs * sizeof(int32_t), &dcam);
-  if (!rc) rc = buf.up(nullptr, bits_bytes, &dbits);
-  if (!rc) rc = buf.up(nullptr, n_counts * sizeof(int64_t), &dcounts);
-  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
   hipError_t e = hipMemsetAsync(dcounts, 0, n_counts * sizeof(int64_t), 0);
   const dim3 mark_grid((unsigned)((n_obs + COV_MARK_BLOCK - 1) / COV_MARK_BLOCK));
   const dim3 gram_grid((unsigned)plan.n_tile_pairs, (unsigned)plan.n_chunks);
@@ -108,17 +112,15 @@ extern "C" int cba_coverage_counts(const cba_coverage_desc* d, int32_t device, i
     const int64_t w1 = w0 + plan.slab_words < plan.n_words ? w0 + plan.slab_words : plan.n_words;
     e = hipMemsetAsync(dbits, 0, bits_bytes, 0);
     if (e != hipSuccess) break;
-    hipLaunchKernelGGL(k_cov_mark, mark_grid, dim3(COV_MARK_BLOCK), 0, 0, n_obs, (const int64_t*)dkey, (const int32_t*)dcam, w0, w1, plan.stride,
-                       (unsigned long long*)dbits);
-    hipLaunchKernelGGL(k_cov_gram, gram_grid, dim3(COV_BLOCK), 0, 0, n_cams, plan.n_tiles, plan.stride, plan.chunk_words, (const uint64_t*)dbits,
-                       (unsigned long long*)dcounts);
+    hipLaunchKernelGGL(k_cov_mark, mark_grid, dim3(COV_MARK_BLOCK), 0, 0, n_obs, dkey, dcam, w0, w1, plan.stride, dbits_atomic);
+    hipLaunchKernelGGL(k_cov_gram, gram_grid, dim3(COV_BLOCK), 0, 0, n_cams, plan.n_tiles, plan.stride, plan.chunk_words, dbits, dcounts_atomic);
     e = hipGetLastError();
   }
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_cov_mirror, dim3((unsigned)((n_counts + 255) / 256)), dim3(256), 0, 0, n_cams, (int64_t*)dcounts);
+    hipLaunchKernelGGL(k_cov_mirror, dim3((unsigned)((n_counts + 255) / 256)), dim3(256), 0, 0, n_cams, dcounts);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpy(counts_out, dcounts, n_counts * sizeof(int64_t), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  return CBA_OK;
+  buf.check(e);
+  buf.out(counts_out, dcounts, n_counts);
+  return buf.result(what);
 }

@@ -63,6 +63,7 @@
 #include <algorithm>
 #include <numeric>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/caliscope_pose.h"
@@ -72,6 +73,10 @@
 #include "intrinsic_math.h"
 
 using namespace cba;
+
+// The kernels take CSR offsets and counts as long, the C ABI as int64_t.  Where the two are one type the buffers of a call go to the
+// launches as they are; anywhere else this file must not compile.
+static_assert(std::is_same<long, int64_t>::value, "CSR offsets are passed as long");
 
 namespace {
 
@@ -753,32 +758,27 @@ int cba_pose_pnp_batch(const cba_pose_pnp_desc* d, int32_t device, double* pose_
     return d->view_start[x + 1] - d->view_start[x] < d->view_start[y + 1] - d->view_start[y];
   });
   Buffers buf;
-  void *dord = nullptr, *dvs = nullptr, *dvc = nullptr, *dmodel = nullptr, *dintr = nullptr, *dxy = nullptr, *dobj = nullptr, *dund = nullptr,
-       *dpose = nullptr, *drmse = nullptr, *dst = nullptr;
-  rc = buf.up(order.data(), (size_t)n_views * sizeof(int64_t), &dord);
-  if (!rc) rc = buf.up(d->view_start, (size_t)(n_views + 1) * sizeof(int64_t), &dvs);
-  if (!rc) rc = buf.up(d->view_cam, (size_t)n_views * sizeof(int32_t), &dvc);
-  if (!rc) rc = buf.up(d->cam_model, (size_t)d->n_cams * sizeof(int32_t), &dmodel);
-  if (!rc) rc = buf.up(d->cam_intr, (size_t)d->n_cams * 9 * sizeof(double), &dintr);
-  if (!rc) rc = buf.up(d->obs_xy, (size_t)n_obs * 2 * sizeof(double), &dxy);
-  if (!rc) rc = buf.up(d->obs_obj, (size_t)n_obs * 3 * sizeof(double), &dobj);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_obs * 2 * sizeof(double), &dund);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_views * 12 * sizeof(double), &dpose);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_views * sizeof(double), &drmse);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_views * sizeof(int32_t), &dst);
-  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
-  static_assert(sizeof(long) == sizeof(int64_t), "CSR offsets are passed as long");
+  const int64_t* dord = buf.in(order.data(), n_views);
+  const int64_t* dvs = buf.in(d->view_start, n_views + 1);
+  const int32_t* dvc = buf.in(d->view_cam, n_views);
+  const int32_t* dmodel = buf.in(d->cam_model, d->n_cams);
+  const double* dintr = buf.in(d->cam_intr, d->n_cams, 9);
+  const double* dxy = buf.in(d->obs_xy, n_obs, 2);
+  const double* dobj = buf.in(d->obs_obj, n_obs, 3);
+  double* dund = buf.make<double>(n_obs, 2);
+  double* dpose = buf.make<double>(n_views, 12);
+  double* drmse = buf.make<double>(n_views);
+  int32_t* dst = buf.make<int32_t>(n_views);
+  if (buf.status()) return buf.result(what);
   const int grid = (int)((n_views + POSE_BLOCK - 1) / POSE_BLOCK);
-  hipLaunchKernelGGL(k_pose_pnp, dim3(grid), dim3(POSE_BLOCK), 0, 0, (long)n_views, (const long*)dord, (const long*)dvs, (const int*)dvc,
-                     (const int*)dmodel, (const double*)dintr, (const double*)dxy, (const double*)dobj, (int)d->min_points,
-                     d->float32_io ? 1 : 0, (double*)dund, (double*)dpose, (double*)drmse, (int*)dst);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(pose_out, dpose, (size_t)n_views * 12 * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(rmse_out, drmse, (size_t)n_views * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(status_out, dst, (size_t)n_views * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && undistorted_out) e = hipMemcpy(undistorted_out, dund, (size_t)n_obs * 2 * sizeof(double), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  return CBA_OK;
+  hipLaunchKernelGGL(k_pose_pnp, dim3(grid), dim3(POSE_BLOCK), 0, 0, (long)n_views, dord, dvs, dvc, dmodel, dintr, dxy, dobj, (int)d->min_points,
+                     d->float32_io ? 1 : 0, dund, dpose, drmse, dst);
+  buf.check(hipGetLastError());
+  buf.out(pose_out, dpose, n_views, 12);
+  buf.out(rmse_out, drmse, n_views);
+  buf.out(status_out, dst, n_views);
+  buf.out(undistorted_out, dund, n_obs, 2);
+  return buf.result(what);
 }
 
 int cba_pose_pair_rmse(const cba_pose_pair_desc* d, int32_t device, double* rmse_out, int64_t* count_out) {
@@ -795,21 +795,18 @@ int cba_pose_pair_rmse(const cba_pose_pair_desc* d, int32_t device, double* rmse
   if (rc) return rc;
   const int64_t n_pairs = d->n_pairs, n_obs = d->pair_start[n_pairs];
   Buffers buf;
-  void *dpose = nullptr, *dps = nullptr, *da = nullptr, *db = nullptr, *drmse = nullptr, *dcount = nullptr;
-  rc = buf.up(d->pair_pose, (size_t)n_pairs * 12 * sizeof(double), &dpose);
-  if (!rc) rc = buf.up(d->pair_start, (size_t)(n_pairs + 1) * sizeof(int64_t), &dps);
-  if (!rc) rc = buf.up(d->obs_a, (size_t)n_obs * 2 * sizeof(double), &da);
-  if (!rc) rc = buf.up(d->obs_b, (size_t)n_obs * 2 * sizeof(double), &db);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * sizeof(double), &drmse);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * sizeof(int64_t), &dcount);
-  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
-  hipLaunchKernelGGL(k_pose_pair_rmse, dim3((unsigned)n_pairs), dim3(PAIR_BLOCK), 0, 0, (const double*)dpose, (const long*)dps,
-                     (const double*)da, (const double*)db, (double*)drmse, (long*)dcount);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(rmse_out, drmse, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(count_out, dcount, (size_t)n_pairs * sizeof(int64_t), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  return CBA_OK;
+  const double* dpose = buf.in(d->pair_pose, n_pairs, 12);
+  const int64_t* dps = buf.in(d->pair_start, n_pairs + 1);
+  const double* da = buf.in(d->obs_a, n_obs, 2);
+  const double* db = buf.in(d->obs_b, n_obs, 2);
+  double* drmse = buf.make<double>(n_pairs);
+  int64_t* dcount = buf.make<int64_t>(n_pairs);
+  if (buf.status()) return buf.result(what);
+  hipLaunchKernelGGL(k_pose_pair_rmse, dim3((unsigned)n_pairs), dim3(PAIR_BLOCK), 0, 0, dpose, dps, da, db, drmse, dcount);
+  buf.check(hipGetLastError());
+  buf.out(rmse_out, drmse, n_pairs);
+  buf.out(count_out, dcount, n_pairs);
+  return buf.result(what);
 }
 
 int cba_pose_essential_batch(const cba_pose_essential_desc* d, int32_t device, double* pose_out, int32_t* status_out, int64_t* n_inliers_out,
@@ -845,60 +842,55 @@ int cba_pose_essential_batch(const cba_pose_essential_desc* d, int32_t device, d
   int64_t max_n = 0;
   for (int64_t p = 0; p < n_pairs; ++p) max_n = std::max<int64_t>(max_n, d->pair_start[p + 1] - d->pair_start[p]);
   Buffers buf;
-  void *dmodel = nullptr, *dintr = nullptr, *dxy = nullptr, *dcam = nullptr, *dund = nullptr, *dps = nullptr, *dca = nullptr, *dcb = nullptr,
-       *dthr = nullptr, *dhyp = nullptr, *dcount = nullptr, *dpose = nullptr, *dst = nullptr, *dninl = nullptr, *dnchr = nullptr,
-       *dcond = nullptr, *dwin = nullptr, *dflag = nullptr, *dxyz = nullptr;
-  rc = buf.up(d->cam_model, (size_t)d->n_cams * sizeof(int32_t), &dmodel);
-  if (!rc) rc = buf.up(d->cam_intr, (size_t)d->n_cams * 9 * sizeof(double), &dintr);
-  if (!rc) rc = buf.up(d->obs_xy, (size_t)n_obs * 2 * sizeof(double), &dxy);
-  if (!rc) rc = buf.up(d->obs_cam, (size_t)n_obs * sizeof(int32_t), &dcam);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_obs * 2 * sizeof(double), &dund);
-  if (!rc) rc = buf.up(d->pair_start, (size_t)(n_pairs + 1) * sizeof(int64_t), &dps);
-  if (!rc) rc = buf.up(d->corr_a, (size_t)n_corr * sizeof(int64_t), &dca);
-  if (!rc) rc = buf.up(d->corr_b, (size_t)n_corr * sizeof(int64_t), &dcb);
-  if (!rc) rc = buf.up(d->threshold, (size_t)n_pairs * sizeof(double), &dthr);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * n_hyp * 9 * sizeof(double), &dhyp);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * n_hyp * sizeof(unsigned), &dcount);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * 12 * sizeof(double), &dpose);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * sizeof(int32_t), &dst);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * sizeof(int64_t), &dninl);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * sizeof(int64_t), &dnchr);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * sizeof(double), &dcond);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_pairs * sizeof(int32_t), &dwin);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_corr, &dflag);
-  if (!rc && xyz_out) rc = buf.up(nullptr, (size_t)n_corr * 3 * sizeof(double), &dxyz);
-  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
-  hipError_t e = hipSuccess;
-  if (n_pairs > 0) e = hipMemset(dcount, 0, (size_t)n_pairs * n_hyp * sizeof(unsigned));
-  if (e == hipSuccess && n_obs > 0)
-    hipLaunchKernelGGL(k_epi_undistort, dim3((unsigned)((n_obs + SCORE_BLOCK - 1) / SCORE_BLOCK)), dim3(SCORE_BLOCK), 0, 0, (long)n_obs,
-                       (const int*)dcam, (const int*)dmodel, (const double*)dintr, (const double*)dxy, d->float32_io ? 1 : 0, (double*)dund);
-  if (e == hipSuccess && n_pairs > 0) {
+  const int32_t* dmodel = buf.in(d->cam_model, d->n_cams);
+  const double* dintr = buf.in(d->cam_intr, d->n_cams, 9);
+  const double* dxy = buf.in(d->obs_xy, n_obs, 2);
+  const int32_t* dcam = buf.in(d->obs_cam, n_obs);
+  double* dund = buf.make<double>(n_obs, 2);
+  const int64_t* dps = buf.in(d->pair_start, n_pairs + 1);
+  const int64_t* dca = buf.in(d->corr_a, n_corr);
+  const int64_t* dcb = buf.in(d->corr_b, n_corr);
+  const double* dthr = buf.in(d->threshold, n_pairs);
+  double* dhyp = buf.make<double>(n_pairs, n_hyp, 9);
+  unsigned* dcount = buf.make<unsigned>(n_pairs, n_hyp);
+  double* dpose = buf.make<double>(n_pairs, 12);
+  int32_t* dst = buf.make<int32_t>(n_pairs);
+  int64_t* dninl = buf.make<int64_t>(n_pairs);
+  int64_t* dnchr = buf.make<int64_t>(n_pairs);
+  double* dcond = buf.make<double>(n_pairs);
+  int32_t* dwin = buf.make<int32_t>(n_pairs);
+  uint8_t* dflag = buf.make<uint8_t>(n_corr);
+  double* dxyz = xyz_out ? buf.make<double>(n_corr, 3) : nullptr;  // null: k_epi_refine writes no points
+  if (buf.status()) return buf.result(what);
+  if (n_pairs > 0) buf.check(hipMemset(dcount, 0, (size_t)n_pairs * n_hyp * sizeof(unsigned)));
+  if (buf.status()) return buf.result(what);
+  if (n_obs > 0)
+    hipLaunchKernelGGL(k_epi_undistort, dim3((unsigned)((n_obs + SCORE_BLOCK - 1) / SCORE_BLOCK)), dim3(SCORE_BLOCK), 0, 0, (long)n_obs, dcam, dmodel, dintr, dxy,
+                       d->float32_io ? 1 : 0, dund);
+  if (n_pairs > 0) {
     const long nq = (long)n_pairs * n_hyp;
+    const double* no_f64 = nullptr;
     hipLaunchKernelGGL(k_epi_hyp, dim3((unsigned)((nq + HYP_BLOCK - 1) / HYP_BLOCK)), dim3(HYP_BLOCK), 0, 0, (long)n_pairs, n_hyp,
-                       (unsigned long long)d->seed, (const long*)dps, (const long*)dca, (const long*)dcb, (const double*)dund, (double*)dhyp);
+                       (unsigned long long)d->seed, dps, dca, dcb, dund, dhyp);
     const long tiles = std::max<long>(1, (long)((max_n + SCORE_BLOCK * SCORE_PER_LANE - 1) / (SCORE_BLOCK * SCORE_PER_LANE)));
     hipLaunchKernelGGL(k_score<true>, dim3((unsigned)tiles, (unsigned)std::min<int64_t>(n_pairs, 65535)), dim3(SCORE_BLOCK), 0, 0, (long)n_pairs,
-                       n_hyp, (const long*)dps, (const long*)dca, (const long*)dcb, (const double*)dund, (const double*)nullptr,
-                       (const double*)nullptr, (const double*)dthr, (const double*)dhyp, (unsigned*)dcount);
-    hipLaunchKernelGGL(k_epi_refine, dim3((unsigned)n_pairs), dim3(REFINE_BLOCK), 0, 0, (long)n_pairs, n_hyp, (const long*)dps, (const long*)dca,
-                       (const long*)dcb, (const double*)dund, (const double*)dthr, (const double*)dhyp, (const unsigned*)dcount, (double*)dpose,
-                       (int*)dst, (long*)dninl, (long*)dnchr, (double*)dcond, (int*)dwin, (unsigned char*)dflag, (double*)dxyz);
+                       n_hyp, dps, dca, dcb, dund, no_f64, no_f64, dthr, dhyp, dcount);
+    hipLaunchKernelGGL(k_epi_refine, dim3((unsigned)n_pairs), dim3(REFINE_BLOCK), 0, 0, (long)n_pairs, n_hyp, dps, dca, dcb, dund, dthr,
+                       dhyp, dcount, dpose, dst, dninl, dnchr, dcond, dwin, dflag, dxyz);
   }
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess && n_pairs > 0) {
-    e = hipMemcpy(pose_out, dpose, (size_t)n_pairs * 12 * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(status_out, dst, (size_t)n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(n_inliers_out, dninl, (size_t)n_pairs * sizeof(int64_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(n_cheiral_out, dnchr, (size_t)n_pairs * sizeof(int64_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(conditioning_out, dcond, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && winner_out) e = hipMemcpy(winner_out, dwin, (size_t)n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && n_corr > 0) e = hipMemcpy(corr_flag_out, dflag, (size_t)n_corr, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && xyz_out && n_corr > 0) e = hipMemcpy(xyz_out, dxyz, (size_t)n_corr * 3 * sizeof(double), hipMemcpyDeviceToHost);
+  buf.check(hipGetLastError());
+  if (n_pairs > 0) {
+    buf.out(pose_out, dpose, n_pairs, 12);
+    buf.out(status_out, dst, n_pairs);
+    buf.out(n_inliers_out, dninl, n_pairs);
+    buf.out(n_cheiral_out, dnchr, n_pairs);
+    buf.out(conditioning_out, dcond, n_pairs);
+    buf.out(winner_out, dwin, n_pairs);
+    buf.out(corr_flag_out, dflag, n_corr);
+    buf.out(xyz_out, dxyz, n_corr, 3);
   }
-  if (e == hipSuccess && undistorted_out && n_obs > 0) e = hipMemcpy(undistorted_out, dund, (size_t)n_obs * 2 * sizeof(double), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  return CBA_OK;
+  buf.out(undistorted_out, dund, n_obs, 2);
+  return buf.result(what);
 }
 
 int cba_pose_resect_batch(const cba_pose_resect_desc* d, int32_t device, double* pose_out, int32_t* status_out, int64_t* n_inliers_out,
@@ -922,41 +914,37 @@ int cba_pose_resect_batch(const cba_pose_resect_desc* d, int32_t device, double*
   int64_t max_n = 0;
   for (int64_t j = 0; j < n_jobs; ++j) max_n = std::max<int64_t>(max_n, d->job_start[j + 1] - d->job_start[j]);
   Buffers buf;
-  void *djs = nullptr, *dobj = nullptr, *duv = nullptr, *dthr = nullptr, *dhyp = nullptr, *dcount = nullptr, *dpose = nullptr, *dst = nullptr,
-       *dninl = nullptr, *dwin = nullptr, *derr = nullptr;
-  rc = buf.up(d->job_start, (size_t)(n_jobs + 1) * sizeof(int64_t), &djs);
-  if (!rc) rc = buf.up(d->obj, (size_t)n * 3 * sizeof(double), &dobj);
-  if (!rc) rc = buf.up(d->uv, (size_t)n * 2 * sizeof(double), &duv);
-  if (!rc) rc = buf.up(d->threshold, (size_t)n_jobs * sizeof(double), &dthr);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_jobs * n_hyp * 12 * sizeof(double), &dhyp);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_jobs * n_hyp * sizeof(unsigned), &dcount);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_jobs * 12 * sizeof(double), &dpose);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_jobs * sizeof(int32_t), &dst);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_jobs * sizeof(int64_t), &dninl);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_jobs * sizeof(int32_t), &dwin);
-  if (!rc) rc = buf.up(nullptr, (size_t)n * sizeof(double), &derr);
-  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
-  hipError_t e = hipMemset(dcount, 0, (size_t)n_jobs * n_hyp * sizeof(unsigned));
-  if (e == hipSuccess) {
-    const long nq = (long)n_jobs * n_hyp;
-    hipLaunchKernelGGL(k_res_hyp, dim3((unsigned)((nq + HYP_BLOCK - 1) / HYP_BLOCK)), dim3(HYP_BLOCK), 0, 0, (long)n_jobs, n_hyp, (int)d->min_points,
-                       (unsigned long long)d->seed, (const long*)djs, (const double*)dobj, (const double*)duv, (double*)dhyp);
-    const long tiles = std::max<long>(1, (long)((max_n + SCORE_BLOCK * SCORE_PER_LANE - 1) / (SCORE_BLOCK * SCORE_PER_LANE)));
-    hipLaunchKernelGGL(k_score<false>, dim3((unsigned)tiles, (unsigned)std::min<int64_t>(n_jobs, 65535)), dim3(SCORE_BLOCK), 0, 0, (long)n_jobs,
-                       n_hyp, (const long*)djs, (const long*)nullptr, (const long*)nullptr, (const double*)nullptr, (const double*)dobj,
-                       (const double*)duv, (const double*)dthr, (const double*)dhyp, (unsigned*)dcount);
-    hipLaunchKernelGGL(k_res_refine, dim3((unsigned)n_jobs), dim3(REFINE_BLOCK), 0, 0, (long)n_jobs, n_hyp, (int)d->min_points, (const long*)djs,
-                       (const double*)dobj, (const double*)duv, (const double*)dthr, (const double*)dhyp, (const unsigned*)dcount, (double*)dpose,
-                       (int*)dst, (long*)dninl, (int*)dwin, (double*)derr);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(pose_out, dpose, (size_t)n_jobs * 12 * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(status_out, dst, (size_t)n_jobs * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(n_inliers_out, dninl, (size_t)n_jobs * sizeof(int64_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && winner_out) e = hipMemcpy(winner_out, dwin, (size_t)n_jobs * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && n > 0) e = hipMemcpy(err_out, derr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  return CBA_OK;
+  const int64_t* djs = buf.in(d->job_start, n_jobs + 1);
+  const double* dobj = buf.in(d->obj, n, 3);
+  const double* duv = buf.in(d->uv, n, 2);
+  const double* dthr = buf.in(d->threshold, n_jobs);
+  double* dhyp = buf.make<double>(n_jobs, n_hyp, 12);
+  unsigned* dcount = buf.make<unsigned>(n_jobs, n_hyp);
+  double* dpose = buf.make<double>(n_jobs, 12);
+  int32_t* dst = buf.make<int32_t>(n_jobs);
+  int64_t* dninl = buf.make<int64_t>(n_jobs);
+  int32_t* dwin = buf.make<int32_t>(n_jobs);
+  double* derr = buf.make<double>(n);
+  if (buf.status()) return buf.result(what);
+  buf.check(hipMemset(dcount, 0, (size_t)n_jobs * n_hyp * sizeof(unsigned)));
+  if (buf.status()) return buf.result(what);
+  const long nq = (long)n_jobs * n_hyp;
+  const long* no_i64 = nullptr;
+  const double* no_f64 = nullptr;
+  hipLaunchKernelGGL(k_res_hyp, dim3((unsigned)((nq + HYP_BLOCK - 1) / HYP_BLOCK)), dim3(HYP_BLOCK), 0, 0, (long)n_jobs, n_hyp, (int)d->min_points,
+                     (unsigned long long)d->seed, djs, dobj, duv, dhyp);
+  const long tiles = std::max<long>(1, (long)((max_n + SCORE_BLOCK * SCORE_PER_LANE - 1) / (SCORE_BLOCK * SCORE_PER_LANE)));
+  hipLaunchKernelGGL(k_score<false>, dim3((unsigned)tiles, (unsigned)std::min<int64_t>(n_jobs, 65535)), dim3(SCORE_BLOCK), 0, 0, (long)n_jobs, n_hyp, djs,
+                     no_i64, no_i64, no_f64, dobj, duv, dthr, dhyp, dcount);
+  hipLaunchKernelGGL(k_res_refine, dim3((unsigned)n_jobs), dim3(REFINE_BLOCK), 0, 0, (long)n_jobs, n_hyp, (int)d->min_points, djs, dobj, duv, dthr,
+                     dhyp, dcount, dpose, dst, dninl, dwin, derr);
+  buf.check(hipGetLastError());
+  buf.out(pose_out, dpose, n_jobs, 12);
+  buf.out(status_out, dst, n_jobs);
+  buf.out(n_inliers_out, dninl, n_jobs);
+  buf.out(winner_out, dwin, n_jobs);
+  buf.out(err_out, derr, n);
+  return buf.result(what);
 }
 
 int cba_pose_intrinsics_batch(const cba_intrinsics_desc* d, int32_t device, double* intr_out, double* rmse_out, int32_t* status_out,
@@ -1006,49 +994,43 @@ int cba_pose_intrinsics_batch(const cba_intrinsics_desc* d, int32_t device, doub
     cam_views[cam_view_start[c] + fill[c]++] = v;
   }
   Buffers buf;
-  void *dord = nullptr, *dvs = nullptr, *dvc = nullptr, *dmodel = nullptr, *dstart = nullptr, *dxy = nullptr, *dobj = nullptr, *dund = nullptr,
-       *dpnp = nullptr, *dprm = nullptr, *dpst = nullptr, *dcvs = nullptr, *dcv = nullptr, *dwork = nullptr, *dintr = nullptr, *drmse = nullptr,
-       *dst = nullptr, *dit = nullptr, *dpose = nullptr, *dvr = nullptr, *dvst = nullptr;
-  rc = buf.up(order.data(), (size_t)n_views * sizeof(int64_t), &dord);
-  if (!rc) rc = buf.up(d->view_start, (size_t)(n_views > 0 ? n_views + 1 : 0) * sizeof(int64_t), &dvs);
-  if (!rc) rc = buf.up(d->view_cam, (size_t)n_views * sizeof(int32_t), &dvc);
-  if (!rc) rc = buf.up(d->cam_model, (size_t)n_cams * sizeof(int32_t), &dmodel);
-  if (!rc) rc = buf.up(start.data(), (size_t)n_cams * 9 * sizeof(double), &dstart);
-  if (!rc) rc = buf.up(d->obs_xy, (size_t)n_obs * 2 * sizeof(double), &dxy);
-  if (!rc) rc = buf.up(d->obs_obj, (size_t)n_obs * 3 * sizeof(double), &dobj);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_obs * 2 * sizeof(double), &dund);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_views * 12 * sizeof(double), &dpnp);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_views * sizeof(double), &dprm);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_views * sizeof(int32_t), &dpst);
-  if (!rc) rc = buf.up(cam_view_start.data(), (size_t)(n_cams + 1) * sizeof(int64_t), &dcvs);
-  if (!rc) rc = buf.up(cam_views.data(), (size_t)n_views * sizeof(int64_t), &dcv);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_views * INTR_WORK * sizeof(double), &dwork);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * 9 * sizeof(double), &dintr);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(double), &drmse);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &dst);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &dit);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_views * 12 * sizeof(double), &dpose);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_views * sizeof(double), &dvr);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_views * sizeof(int32_t), &dvst);
-  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
+  const int64_t* dord = buf.in(order.data(), n_views);
+  const int64_t* dvs = buf.in(d->view_start, n_views > 0 ? n_views + 1 : 0);
+  const int32_t* dvc = buf.in(d->view_cam, n_views);
+  const int32_t* dmodel = buf.in(d->cam_model, n_cams);
+  const double* dstart = buf.in(start.data(), n_cams, 9);
+  const double* dxy = buf.in(d->obs_xy, n_obs, 2);
+  const double* dobj = buf.in(d->obs_obj, n_obs, 3);
+  double* dund = buf.make<double>(n_obs, 2);
+  double* dpnp = buf.make<double>(n_views, 12);
+  double* dprm = buf.make<double>(n_views);
+  int32_t* dpst = buf.make<int32_t>(n_views);
+  const int64_t* dcvs = buf.in(cam_view_start.data(), n_cams + 1);
+  const int64_t* dcv = buf.in(cam_views.data(), n_views);
+  double* dwork = buf.make<double>(n_views, INTR_WORK);
+  double* dintr = buf.make<double>(n_cams, 9);
+  double* drmse = buf.make<double>(n_cams);
+  int32_t* dst = buf.make<int32_t>(n_cams);
+  int32_t* dit = buf.make<int32_t>(n_cams);
+  double* dpose = buf.make<double>(n_views, 12);
+  double* dvr = buf.make<double>(n_views);
+  int32_t* dvst = buf.make<int32_t>(n_views);
+  if (buf.status()) return buf.result(what);
   const int f32 = d->float32_io ? 1 : 0;
   if (n_views > 0)
-    hipLaunchKernelGGL(k_pose_pnp, dim3((unsigned)((n_views + POSE_BLOCK - 1) / POSE_BLOCK)), dim3(POSE_BLOCK), 0, 0, (long)n_views, (const long*)dord,
-                       (const long*)dvs, (const int*)dvc, (const int*)dmodel, (const double*)dstart, (const double*)dxy, (const double*)dobj,
-                       (int)INTR_MIN_POINTS, f32, (double*)dund, (double*)dpnp, (double*)dprm, (int*)dpst);
-  hipLaunchKernelGGL(k_intrinsics, dim3((unsigned)n_cams), dim3(REFINE_BLOCK), 0, 0, (const int*)dmodel, (const double*)dstart, (const long*)dcvs,
-                     (const long*)dcv, (const long*)dvs, (const double*)dxy, (const double*)dobj, f32, (int)d->max_iter, (const double*)dpnp,
-                     (const int*)dpst, (double*)dwork, (double*)dintr, (double*)drmse, (int*)dst, (int*)dit, (double*)dpose, (double*)dvr, (int*)dvst);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(intr_out, dintr, (size_t)n_cams * 9 * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(rmse_out, drmse, (size_t)n_cams * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(status_out, dst, (size_t)n_cams * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && iters_out) e = hipMemcpy(iters_out, dit, (size_t)n_cams * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && n_views > 0) e = hipMemcpy(pose_out, dpose, (size_t)n_views * 12 * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && n_views > 0) e = hipMemcpy(view_rmse_out, dvr, (size_t)n_views * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && n_views > 0) e = hipMemcpy(view_status_out, dvst, (size_t)n_views * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  return CBA_OK;
+    hipLaunchKernelGGL(k_pose_pnp, dim3((unsigned)((n_views + POSE_BLOCK - 1) / POSE_BLOCK)), dim3(POSE_BLOCK), 0, 0, (long)n_views, dord, dvs, dvc, dmodel,
+                       dstart, dxy, dobj, (int)INTR_MIN_POINTS, f32, dund, dpnp, dprm, dpst);
+  hipLaunchKernelGGL(k_intrinsics, dim3((unsigned)n_cams), dim3(REFINE_BLOCK), 0, 0, dmodel, dstart, dcvs, dcv, dvs, dxy, dobj, f32, (int)d->max_iter,
+                     dpnp, dpst, dwork, dintr, drmse, dst, dit, dpose, dvr, dvst);
+  buf.check(hipGetLastError());
+  buf.out(intr_out, dintr, n_cams, 9);
+  buf.out(rmse_out, drmse, n_cams);
+  buf.out(status_out, dst, n_cams);
+  buf.out(iters_out, dit, n_cams);
+  buf.out(pose_out, dpose, n_views, 12);
+  buf.out(view_rmse_out, dvr, n_views);
+  buf.out(view_status_out, dvst, n_views);
+  return buf.result(what);
 }
 
 int cba_pose_select_frames(const cba_frame_select_desc* d, int32_t device, uint64_t* cell_mask_out, double* pose_feat_out, double* orient_out,
@@ -1104,51 +1086,45 @@ int cba_pose_select_frames(const cba_frame_select_desc* d, int32_t device, uint6
   std::vector<int32_t> frame_cam(n_frames);
   for (int32_t c = 0; c < n_cams; ++c) std::fill(frame_cam.begin() + d->cam_frame_start[c], frame_cam.begin() + d->cam_frame_start[c + 1], c);
   Buffers buf;
-  void *dord = nullptr, *dfs = nullptr, *dfc = nullptr, *dcfs = nullptr, *dsize = nullptr, *dhs = nullptr, *dhc = nullptr, *dxy = nullptr, *dobj = nullptr,
-       *dmask = nullptr, *dfeat = nullptr, *dori = nullptr, *dhst = nullptr, *dhr = nullptr, *ddist = nullptr, *dsel = nullptr, *dns = nullptr,
-       *dna = nullptr, *dbm = nullptr, *del = nullptr;
-  rc = buf.up(order.data(), (size_t)n_frames * sizeof(int64_t), &dord);
-  if (!rc) rc = buf.up(d->frame_start, (size_t)(n_frames + 1) * sizeof(int64_t), &dfs);
-  if (!rc) rc = buf.up(frame_cam.data(), (size_t)n_frames * sizeof(int32_t), &dfc);
-  if (!rc) rc = buf.up(d->cam_frame_start, (size_t)(n_cams + 1) * sizeof(int64_t), &dcfs);
-  if (!rc) rc = buf.up(d->cam_size, (size_t)n_cams * 2 * sizeof(double), &dsize);
-  if (!rc && d->homog_start) rc = buf.up(d->homog_start, (size_t)n_frames * sizeof(int64_t), &dhs);
-  if (!rc && d->homog_start) rc = buf.up(d->homog_count, (size_t)n_frames * sizeof(int32_t), &dhc);
-  if (!rc) rc = buf.up(d->obs_xy, (size_t)n_obs * 2 * sizeof(double), &dxy);
-  if (!rc) rc = buf.up(d->obs_obj, (size_t)n_obs * 2 * sizeof(double), &dobj);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * sizeof(uint64_t), &dmask);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * 5 * sizeof(double), &dfeat);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * 3 * sizeof(double), &dori);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * sizeof(int32_t), &dhst);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * sizeof(double), &dhr);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * sizeof(double), &ddist);
-  if (!rc) rc = buf.up(selected_out, (size_t)n_cams * target * sizeof(int32_t), &dsel);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &dns);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &dna);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &dbm);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &del);
-  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
+  const int64_t* dord = buf.in(order.data(), n_frames);
+  const int64_t* dfs = buf.in(d->frame_start, n_frames + 1);
+  const int32_t* dfc = buf.in(frame_cam.data(), n_frames);
+  const int64_t* dcfs = buf.in(d->cam_frame_start, n_cams + 1);
+  const double* dsize = buf.in(d->cam_size, n_cams, 2);
+  const int64_t* dhs = d->homog_start ? buf.in(d->homog_start, n_frames) : nullptr;  // null: the homography takes every corner of a frame
+  const int32_t* dhc = d->homog_start ? buf.in(d->homog_count, n_frames) : nullptr;
+  const double* dxy = buf.in(d->obs_xy, n_obs, 2);
+  const double* dobj = buf.in(d->obs_obj, n_obs, 2);
+  // the kernels take the cell masks as unsigned long long, the C ABI as uint64_t: the same words under another name
   static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "cell masks are passed as unsigned long long");
-  hipLaunchKernelGGL(k_frame_features, dim3((unsigned)((n_frames + FEAT_BLOCK - 1) / FEAT_BLOCK)), dim3(FEAT_BLOCK), 0, 0, (long)n_frames,
-                     (const long*)dord, (const long*)dfs, (const int*)dfc, (const double*)dsize, (const long*)dhs, (const int*)dhc, (const double*)dxy,
-                     (const double*)dobj, (int)d->grid_size, d->float32_io ? 1 : 0, (unsigned long long*)dmask, (double*)dfeat, (double*)dori,
-                     (int*)dhst, (double*)dhr);
-  hipLaunchKernelGGL(k_frame_select, dim3((unsigned)n_cams), dim3(SELECT_BLOCK), 0, 0, (const long*)dcfs, (const long*)dfs,
-                     (const unsigned long long*)dmask, (const double*)dfeat, (const double*)dori, (int)d->grid_size, (int)d->min_corners, (int)target,
-                     (double*)ddist, (int*)dsel, (int*)dns, (int*)dna, (int*)dbm, (int*)del);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(cell_mask_out, dmask, (size_t)n_frames * sizeof(uint64_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(pose_feat_out, dfeat, (size_t)n_frames * 5 * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(orient_out, dori, (size_t)n_frames * 3 * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(homog_status_out, dhst, (size_t)n_frames * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(homog_rmse_out, dhr, (size_t)n_frames * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(selected_out, dsel, (size_t)n_cams * target * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(n_selected_out, dns, (size_t)n_cams * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(n_anchors_out, dna, (size_t)n_cams * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(bin_mask_out, dbm, (size_t)n_cams * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(eligible_out, del, (size_t)n_cams * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  return CBA_OK;
+  unsigned long long* dmask = buf.make<unsigned long long>(n_frames);
+  double* dfeat = buf.make<double>(n_frames, 5);
+  double* dori = buf.make<double>(n_frames, 3);
+  int32_t* dhst = buf.make<int32_t>(n_frames);
+  double* dhr = buf.make<double>(n_frames);
+  double* ddist = buf.make<double>(n_frames);
+  int32_t* dsel = buf.in(selected_out, n_cams, target);
+  int32_t* dns = buf.make<int32_t>(n_cams);
+  int32_t* dna = buf.make<int32_t>(n_cams);
+  int32_t* dbm = buf.make<int32_t>(n_cams);
+  int32_t* del = buf.make<int32_t>(n_cams);
+  if (buf.status()) return buf.result(what);
+  hipLaunchKernelGGL(k_frame_features, dim3((unsigned)((n_frames + FEAT_BLOCK - 1) / FEAT_BLOCK)), dim3(FEAT_BLOCK), 0, 0, (long)n_frames, dord, dfs, dfc, dsize,
+                     dhs, dhc, dxy, dobj, (int)d->grid_size, d->float32_io ? 1 : 0, dmask, dfeat, dori, dhst, dhr);
+  hipLaunchKernelGGL(k_frame_select, dim3((unsigned)n_cams), dim3(SELECT_BLOCK), 0, 0, dcfs, dfs, dmask, dfeat,
+                     dori, (int)d->grid_size, (int)d->min_corners, (int)target, ddist, dsel, dns, dna, dbm, del);
+  buf.check(hipGetLastError());
+  buf.out((unsigned long long*)cell_mask_out, dmask, n_frames);
+  buf.out(pose_feat_out, dfeat, n_frames, 5);
+  buf.out(orient_out, dori, n_frames, 3);
+  buf.out(homog_status_out, dhst, n_frames);
+  buf.out(homog_rmse_out, dhr, n_frames);
+  buf.out(selected_out, dsel, n_cams, target);
+  buf.out(n_selected_out, dns, n_cams);
+  buf.out(n_anchors_out, dna, n_cams);
+  buf.out(bin_mask_out, dbm, n_cams);
+  buf.out(eligible_out, del, n_cams);
+  return buf.result(what);
 }
 
 }  // extern "C"

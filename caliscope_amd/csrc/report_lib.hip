@@ -20,6 +20,7 @@
 // select round (a few bytes per segment: the interpolation is host arithmetic), and the kept counts after a mask.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -228,7 +229,7 @@ hipError_t mask_round(int64_t n_obs, int32_t n_cams, const double* derr, const i
   hipError_t e = hipMemcpy(dthr, thr.data(), (size_t)n_cams * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemsetAsync(dkept, 0, (size_t)n_cams * sizeof(u64), 0);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_rep_mask, dim3((unsigned)((n_obs + REP_TILE - 1) / REP_TILE)), dim3(REP_BLOCK), 0, 0, n_obs, n_cams, derr, dcam, (const double*)dthr,
+  hipLaunchKernelGGL(k_rep_mask, dim3((unsigned)((n_obs + REP_TILE - 1) / REP_TILE)), dim3(REP_BLOCK), 0, 0, n_obs, n_cams, derr, dcam, dthr,
                      dkeep, dkept);
   e = hipGetLastError();
   kept.assign((size_t)n_cams, 0);
@@ -268,51 +269,47 @@ extern "C" int cba_reprojection_filter(const cba_report_desc* d, int32_t device,
   rc = select_device(device, what);
   if (rc) return rc;
   Buffers buf;
+  // what the chosen path does not read stays null: the kernels branch on that
   const bool project = d->err_in == nullptr;
-  void *dmodel = nullptr, *dconst = nullptr, *dpose = nullptr, *dtab = nullptr, *dpoints = nullptr, *dcam = nullptr, *dpt = nullptr, *duv = nullptr;
-  void *dgroup = nullptr, *derr_in = nullptr, *derr_xy = nullptr, *derr = nullptr, *dsums = nullptr;
-  rc = buf.up(d->obs_cam, (size_t)n_obs * sizeof(int32_t), &dcam);
-  if (!rc && project) rc = buf.up(d->cam_model, (size_t)n_cams * sizeof(int32_t), &dmodel);
-  if (!rc && project) rc = buf.up(d->cam_const, (size_t)n_cams * CAM_CONST_STRIDE * sizeof(double), &dconst);
-  if (!rc && project) rc = buf.up(d->cam_pose, (size_t)n_cams * 6 * sizeof(double), &dpose);
-  if (!rc && project) rc = buf.up(nullptr, (size_t)n_cams * CAMTAB_DOUBLES * sizeof(double), &dtab);
-  if (!rc && project) rc = buf.up(d->points, (size_t)d->n_points * 3 * sizeof(double), &dpoints);
-  if (!rc && project) rc = buf.up(d->obs_pt, (size_t)n_obs * sizeof(int32_t), &dpt);
-  if (!rc && project) rc = buf.up(d->obs_uv, (size_t)n_obs * 2 * sizeof(double), &duv);
-  if (!rc && project && out->err_xy) rc = buf.up(nullptr, (size_t)n_obs * 2 * sizeof(double), &derr_xy);
-  if (!rc && !project) rc = buf.up(d->err_in, (size_t)n_obs * sizeof(double), &derr_in);
-  if (!rc && d->obs_group) rc = buf.up(d->obs_group, (size_t)n_obs * sizeof(int32_t), &dgroup);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_obs * sizeof(double), &derr);
+  const int32_t* dcam = buf.in(d->obs_cam, n_obs);
+  const int32_t* dmodel = project ? buf.in(d->cam_model, n_cams) : nullptr;
+  const double* dconst = project ? buf.in(d->cam_const, n_cams, CAM_CONST_STRIDE) : nullptr;
+  const double* dpose = project ? buf.in(d->cam_pose, n_cams, 6) : nullptr;
+  double* dtab = project ? buf.make<double>(n_cams, CAMTAB_DOUBLES) : nullptr;
+  const double* dpoints = project ? buf.in(d->points, d->n_points, 3) : nullptr;
+  const int32_t* dpt = project ? buf.in(d->obs_pt, n_obs) : nullptr;
+  const double* duv = project ? buf.in(d->obs_uv, n_obs, 2) : nullptr;
+  double* derr_xy = project && out->err_xy ? buf.make<double>(n_obs, 2) : nullptr;
+  const double* derr_in = project ? nullptr : buf.in(d->err_in, n_obs);
+  const int32_t* dgroup = d->obs_group ? buf.in(d->obs_group, n_obs) : nullptr;
+  double* derr = buf.make<double>(n_obs);
   // the sums of the error kernel in one zeroed block of 8-byte words: camera sums, camera counts, group sums, group counts, overall, non-finite
   const size_t n_sums = 2 * (size_t)n_cams + 2 * (size_t)n_groups + 2;
-  if (!rc) rc = buf.up(nullptr, n_sums * 8, &dsums);
-  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
-  double* dcam_sum = (double*)dsums;
-  u64* dcam_cnt = (u64*)dsums + n_cams;
-  double* dgrp_sum = (double*)dsums + 2 * (size_t)n_cams;
-  u64* dgrp_cnt = (u64*)dsums + 2 * (size_t)n_cams + n_groups;
-  double* doverall = (double*)dsums + n_sums - 2;
-  u64* dbad = (u64*)dsums + n_sums - 1;
-  hipError_t e = hipMemsetAsync(dsums, 0, n_sums * 8, 0);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  u64* dsums = buf.make<u64>(n_sums);
+  if (buf.status()) return buf.result(what);
+  double* dsums_f64 = (double*)dsums;  // (the sums are doubles, the counts integers, in the same block)
+  double* dcam_sum = dsums_f64;
+  u64* dcam_cnt = dsums + n_cams;
+  double* dgrp_sum = dsums_f64 + 2 * (size_t)n_cams;
+  u64* dgrp_cnt = dsums + 2 * (size_t)n_cams + n_groups;
+  double* doverall = dsums_f64 + n_sums - 2;
+  u64* dbad = dsums + n_sums - 1;
+  buf.check(hipMemsetAsync(dsums, 0, n_sums * 8, 0));
+  if (buf.status()) return buf.result(what);
   const dim3 grid((unsigned)((n_obs + REP_TILE - 1) / REP_TILE));
-  if (project)
-    hipLaunchKernelGGL(k_rep_cam_prep, dim3((unsigned)((n_cams + REP_BLOCK - 1) / REP_BLOCK)), dim3(REP_BLOCK), 0, 0, n_cams, (const int32_t*)dmodel,
-                       (const double*)dconst, (const double*)dpose, (double*)dtab);
+  if (project) hipLaunchKernelGGL(k_rep_cam_prep, dim3((unsigned)((n_cams + REP_BLOCK - 1) / REP_BLOCK)), dim3(REP_BLOCK), 0, 0, n_cams, dmodel, dconst, dpose, dtab);
   if (project && n_cams <= REP_LDS_CAMS)
-    hipLaunchKernelGGL(k_rep_error<true>, grid, dim3(REP_BLOCK), 0, 0, n_obs, n_cams, n_groups, (const double*)dtab, (const double*)dpoints,
-                       (const int32_t*)dcam, (const int32_t*)dpt, (const double*)duv, (const int32_t*)dgroup, (const double*)derr_in, (double*)derr_xy,
-                       (double*)derr, dcam_sum, dcam_cnt, dgrp_sum, dgrp_cnt, doverall, dbad);
+    hipLaunchKernelGGL(k_rep_error<true>, grid, dim3(REP_BLOCK), 0, 0, n_obs, n_cams, n_groups, dtab, dpoints, dcam, dpt, duv, dgroup, derr_in,
+                       derr_xy, derr, dcam_sum, dcam_cnt, dgrp_sum, dgrp_cnt, doverall, dbad);
   else
-    hipLaunchKernelGGL(k_rep_error<false>, grid, dim3(REP_BLOCK), 0, 0, n_obs, n_cams, n_groups, (const double*)dtab, (const double*)dpoints,
-                       (const int32_t*)dcam, (const int32_t*)dpt, (const double*)duv, (const int32_t*)dgroup, (const double*)derr_in, (double*)derr_xy,
-                       (double*)derr, dcam_sum, dcam_cnt, dgrp_sum, dgrp_cnt, doverall, dbad);
-  e = hipGetLastError();
-  std::vector<uint64_t> sums(n_sums);
-  if (e == hipSuccess) e = hipMemcpy(sums.data(), dsums, n_sums * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out->err_xy && project) e = hipMemcpy(out->err_xy, derr_xy, (size_t)n_obs * 2 * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out->err) e = hipMemcpy(out->err, derr, (size_t)n_obs * sizeof(double), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    hipLaunchKernelGGL(k_rep_error<false>, grid, dim3(REP_BLOCK), 0, 0, n_obs, n_cams, n_groups, dtab, dpoints, dcam, dpt, duv, dgroup, derr_in,
+                       derr_xy, derr, dcam_sum, dcam_cnt, dgrp_sum, dgrp_cnt, doverall, dbad);
+  buf.check(hipGetLastError());
+  std::vector<u64> sums(n_sums);
+  buf.out(sums.data(), dsums, n_sums);
+  if (project) buf.out(out->err_xy, derr_xy, n_obs, 2);
+  buf.out(out->err, derr, n_obs);
+  if (buf.status()) return buf.result(what);
   for (int32_t c = 0; c < n_cams; ++c) {
     if (out->cam_sumsq) out->cam_sumsq[c] = rep_value(sums[(size_t)c]);
     if (out->cam_count) out->cam_count[c] = (int64_t)sums[(size_t)n_cams + c];
@@ -331,35 +328,33 @@ extern "C" int cba_reprojection_filter(const cba_report_desc* d, int32_t device,
   RepQueries q;
   if (d->mode == CBA_REPORT_PERCENTILE) q = rep_percentile_queries(cam_rows, n_obs, d->scope, d->value);
   const size_t max_q = std::max<size_t>((size_t)q.n(), (size_t)n_cams);  // the floor round has at most one query per camera
-  void *dqfirst = nullptr, *dprefix = nullptr, *drank = nullptr, *dhist = nullptr, *dthr = nullptr, *dkeep = nullptr, *dkept = nullptr;
-  rc = buf.up(nullptr, (size_t)n_cams * sizeof(int32_t), &dqfirst);
-  if (!rc) rc = buf.up(nullptr, max_q * sizeof(u64), &dprefix);
-  if (!rc) rc = buf.up(nullptr, max_q * sizeof(int64_t), &drank);
-  if (!rc) rc = buf.up(nullptr, max_q * REP_RADIX * sizeof(u64), &dhist);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(double), &dthr);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_obs, &dkeep);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_cams * sizeof(u64), &dkept);
-  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
+  int32_t* dqfirst = buf.make<int32_t>(n_cams);
+  u64* dprefix = buf.make<u64>(max_q);
+  int64_t* drank = buf.make<int64_t>(max_q);
+  u64* dhist = buf.make<u64>(max_q, REP_RADIX);
+  double* dthr = buf.make<double>(n_cams);
+  uint8_t* dkeep = buf.make<uint8_t>(n_obs);
+  u64* dkept = buf.make<u64>(n_cams);
+  if (buf.status()) return buf.result(what);
   std::vector<uint64_t> found;
   std::vector<int64_t> kept;
   if (d->mode == CBA_REPORT_PERCENTILE) {
-    e = select_round(q, n_obs, (const double*)derr, (const int32_t*)dcam, (int32_t*)dqfirst, (u64*)dprefix, (int64_t*)drank, (u64*)dhist, found);
-    if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    buf.check(select_round(q, n_obs, derr, dcam, dqfirst, dprefix, drank, dhist, found));
+    if (buf.status()) return buf.result(what);
     rep_percentile_thresholds(q, found, cam_rows, n_obs, d->scope, d->value, thr);
   }
-  e = mask_round(n_obs, n_cams, (const double*)derr, (const int32_t*)dcam, thr, (double*)dthr, (uint8_t*)dkeep, (u64*)dkept, kept);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  buf.check(mask_round(n_obs, n_cams, derr, dcam, thr, dthr, dkeep, dkept, kept));
+  if (buf.status()) return buf.result(what);
   const RepQueries fq = rep_floor_queries(cam_rows, kept, d->min_per_camera);
   if (fq.n() > 0) {
-    e = select_round(fq, n_obs, (const double*)derr, (const int32_t*)dcam, (int32_t*)dqfirst, (u64*)dprefix, (int64_t*)drank, (u64*)dhist, found);
-    if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    buf.check(select_round(fq, n_obs, derr, dcam, dqfirst, dprefix, drank, dhist, found));
+    if (buf.status()) return buf.result(what);
     for (int32_t k = 0; k < fq.n(); ++k) thr[(size_t)fq.seg[(size_t)k]] = rep_value(found[(size_t)k]);
     // (the mask of a camera whose threshold did not change comes out as before)
-    e = mask_round(n_obs, n_cams, (const double*)derr, (const int32_t*)dcam, thr, (double*)dthr, (uint8_t*)dkeep, (u64*)dkept, kept);
-    if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    buf.check(mask_round(n_obs, n_cams, derr, dcam, thr, dthr, dkeep, dkept, kept));
   }
-  if (out->keep) e = hipMemcpy(out->keep, dkeep, (size_t)n_obs, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  buf.out(out->keep, dkeep, n_obs);
+  if (buf.status()) return buf.result(what);
   for (int32_t c = 0; c < n_cams; ++c) {
     if (out->cam_threshold) out->cam_threshold[c] = thr[(size_t)c];
     if (out->cam_kept) out->cam_kept[c] = kept[(size_t)c];

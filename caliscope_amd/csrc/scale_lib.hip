@@ -120,30 +120,21 @@ extern "C" int cba_scale_launch(const cba_scale_desc* d, int32_t device, const i
   int rc = select_device(device, what);
   if (rc) return rc;
   Buffers buf;
-  void *dlist = nullptr, *dgs = nullptr, *dew = nullptr, *deo = nullptr, *dworld = nullptr, *dstats = nullptr;
-  rc = buf.up(list, (size_t)n_groups * sizeof(int64_t), &dlist);
-  if (!rc) rc = buf.up(d->group_start, (size_t)(n_groups + 1) * sizeof(int64_t), &dgs);
-  if (!rc) rc = buf.up(d->ent_world, (size_t)n_ent * sizeof(int64_t), &dew);
-  if (!rc) rc = buf.up(d->ent_obj, (size_t)n_ent * 3 * sizeof(double), &deo);
-  if (!rc) rc = buf.up(d->world_xyz, (size_t)d->n_world * 3 * sizeof(double), &dworld);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_groups * SCALE_NSTAT * sizeof(double), &dstats);
-  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
-  const int64_t* l = (const int64_t*)dlist;
+  const int64_t* l = buf.in(list, n_groups);
+  const int64_t* dgs = buf.in(d->group_start, n_groups + 1);
+  const int64_t* dew = buf.in(d->ent_world, n_ent);
+  const double* deo = buf.in(d->ent_obj, n_ent, 3);
+  const double* dworld = buf.in(d->world_xyz, d->n_world, 3);
+  double* dstats = buf.make<double>(n_groups, SCALE_NSTAT);
+  if (buf.status()) return buf.result(what);
   const int64_t n_small = counts[0], n_a = counts[1], n_b = counts[2], n_c = counts[3];
   if (n_small)
-    hipLaunchKernelGGL(k_scale_small, dim3((unsigned)((n_small + SCALE_SMALL_BLOCK - 1) / SCALE_SMALL_BLOCK)), dim3(SCALE_SMALL_BLOCK), 0, 0, n_small, l,
-                       (const int64_t*)dgs, (const int64_t*)dew, (const double*)deo, (const double*)dworld, (double*)dstats);
-  if (n_a)
-    hipLaunchKernelGGL(k_scale_group<SCALE_LDS_SMALL>, dim3((unsigned)n_a), dim3(SCALE_BLOCK), 0, 0, l + n_small, (const int64_t*)dgs,
-                       (const int64_t*)dew, (const double*)deo, (const double*)dworld, (double*)dstats);
-  if (n_b)
-    hipLaunchKernelGGL(k_scale_group<SCALE_LDS_LARGE>, dim3((unsigned)n_b), dim3(SCALE_BLOCK), 0, 0, l + n_small + n_a, (const int64_t*)dgs,
-                       (const int64_t*)dew, (const double*)deo, (const double*)dworld, (double*)dstats);
-  if (n_c)
-    hipLaunchKernelGGL(k_scale_group<0>, dim3((unsigned)n_c), dim3(SCALE_BLOCK), 0, 0, l + n_small + n_a + n_b, (const int64_t*)dgs,
-                       (const int64_t*)dew, (const double*)deo, (const double*)dworld, (double*)dstats);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(stats_out, dstats, (size_t)n_groups * SCALE_NSTAT * sizeof(double), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  return CBA_OK;
+    hipLaunchKernelGGL(k_scale_small, dim3((unsigned)((n_small + SCALE_SMALL_BLOCK - 1) / SCALE_SMALL_BLOCK)), dim3(SCALE_SMALL_BLOCK), 0, 0, n_small, l, dgs, dew,
+                       deo, dworld, dstats);
+  if (n_a) hipLaunchKernelGGL(k_scale_group<SCALE_LDS_SMALL>, dim3((unsigned)n_a), dim3(SCALE_BLOCK), 0, 0, l + n_small, dgs, dew, deo, dworld, dstats);
+  if (n_b) hipLaunchKernelGGL(k_scale_group<SCALE_LDS_LARGE>, dim3((unsigned)n_b), dim3(SCALE_BLOCK), 0, 0, l + n_small + n_a, dgs, dew, deo, dworld, dstats);
+  if (n_c) hipLaunchKernelGGL(k_scale_group<0>, dim3((unsigned)n_c), dim3(SCALE_BLOCK), 0, 0, l + n_small + n_a + n_b, dgs, dew, deo, dworld, dstats);
+  buf.check(hipGetLastError());
+  buf.out(stats_out, dstats, n_groups, SCALE_NSTAT);
+  return buf.result(what);
 }

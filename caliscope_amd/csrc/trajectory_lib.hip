@@ -114,57 +114,49 @@ extern "C" int cba_reconstruct_trajectories(const cba_traj_desc* d, int32_t devi
     return err(CBA_ERR_UNSUPPORTED, std::string(what) + ": more workgroups than one launch takes");
 
   Buffers buf;
-  void *dposed = nullptr, *dmodel = nullptr, *dintr = nullptr, *dP = nullptr, *drcam = nullptr, *drslot = nullptr, *drxy = nullptr, *drt = nullptr;
-  void *dxy = nullptr, *dft = nullptr, *dframe = nullptr, *dxyz = nullptr, *dvalid = nullptr, *dtime = nullptr;
-  void *db = nullptr, *da = nullptr, *dzi = nullptr, *dscratch = nullptr;
-  const size_t cells = (size_t)n_cams * (size_t)n_slots;
-  rc = buf.up(d->cam_posed, (size_t)n_cams, &dposed);
-  if (!rc) rc = buf.up(d->cam_model, (size_t)n_cams * sizeof(int32_t), &dmodel);
-  if (!rc) rc = buf.up(d->cam_intr, (size_t)n_cams * 9 * sizeof(double), &dintr);
-  if (!rc) rc = buf.up(d->cam_P, (size_t)n_cams * 12 * sizeof(double), &dP);
-  if (!rc) rc = buf.up(d->row_cam, (size_t)n_rows * sizeof(int32_t), &drcam);
-  if (!rc) rc = buf.up(d->row_slot, (size_t)n_rows * sizeof(int64_t), &drslot);
-  if (!rc) rc = buf.up(d->row_xy, (size_t)n_rows * 2 * sizeof(double), &drxy);
-  if (!rc) rc = buf.up(d->row_time, (size_t)n_rows * sizeof(double), &drt);
-  if (!rc) rc = buf.up(nullptr, cells * 2 * sizeof(double), &dxy);
-  if (!rc) rc = buf.up(nullptr, cells * sizeof(double), &dft);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_frames * sizeof(double), &dframe);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_slots * 3 * sizeof(double), &dxyz);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_slots, &dvalid);
-  if (!rc) rc = buf.up(nullptr, (size_t)n_slots * sizeof(double), &dtime);
+  const uint8_t* dposed = buf.in(d->cam_posed, n_cams);
+  const int32_t* dmodel = buf.in(d->cam_model, n_cams);
+  const double* dintr = buf.in(d->cam_intr, n_cams, 9);
+  const double* dP = buf.in(d->cam_P, n_cams, 12);
+  const int32_t* drcam = buf.in(d->row_cam, n_rows);
+  const int64_t* drslot = buf.in(d->row_slot, n_rows);
+  const double* drxy = buf.in(d->row_xy, n_rows, 2);
+  const double* drt = buf.in(d->row_time, n_rows);
+  double* dxy = buf.make<double>(n_cams, n_slots, 2);
+  double* dft = buf.make<double>(n_cams, n_slots);
+  double* dframe = buf.make<double>(n_frames);
+  double* dxyz = buf.make<double>(n_slots, 3);
+  uint8_t* dvalid = buf.make<uint8_t>(n_slots);
+  double* dtime = buf.make<double>(n_slots);
+  // without a filter its four buffers stay null
   const int order = d->filter_b ? d->filter_order : 0;
-  const size_t scratch_bytes = (size_t)(n_frames + 2 * traj_pad(order)) * (size_t)n_traj * 3 * sizeof(double);
-  if (!rc && d->filter_b) rc = buf.up(d->filter_b, (size_t)(order + 1) * sizeof(double), &db);
-  if (!rc && d->filter_b) rc = buf.up(d->filter_a, (size_t)(order + 1) * sizeof(double), &da);
-  if (!rc && d->filter_b) rc = buf.up(d->filter_zi, (size_t)order * sizeof(double), &dzi);
-  if (!rc && d->filter_b) rc = buf.up(nullptr, scratch_bytes, &dscratch);
-  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
+  const double* db = d->filter_b ? buf.in(d->filter_b, order + 1) : nullptr;
+  const double* da = d->filter_b ? buf.in(d->filter_a, order + 1) : nullptr;
+  const double* dzi = d->filter_b ? buf.in(d->filter_zi, order) : nullptr;
+  double* dscratch = d->filter_b ? buf.make<double>(n_frames + 2 * traj_pad(order), n_traj, 3) : nullptr;
+  if (buf.status()) return buf.result(what);
 
   // all bits set is a NaN: "no row here"
-  hipError_t e = hipMemsetAsync(dxy, 0xff, cells * 2 * sizeof(double), 0);
-  if (e == hipSuccess) e = hipMemsetAsync(dft, 0xff, cells * sizeof(double), 0);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  hipLaunchKernelGGL(k_traj_fill2d, dim3(blocks(n_rows)), dim3(TRAJ_BLOCK), 0, 0, n_rows, n_traj, n_slots, (const int32_t*)drcam, (const int64_t*)drslot,
-                     (const double*)drxy, (const double*)drt, (int)d->xy_gap, (double*)dxy, (double*)dft);
-  hipLaunchKernelGGL(k_traj_frame_time, dim3(blocks(n_frames)), dim3(TRAJ_BLOCK), 0, 0, n_cams, n_frames, n_traj, n_slots, (const double*)dft,
-                     (double*)dframe);
-  hipLaunchKernelGGL(k_traj_triangulate, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), 0, 0, n_cams, n_traj, n_slots, (const uint8_t*)dposed,
-                     (const int32_t*)dmodel, (const double*)dintr, (const double*)dP, (const double*)dxy, (const double*)dframe, d->float32_io ? 1 : 0,
-                     (double*)dxyz, (uint8_t*)dvalid, (double*)dtime);
+  const size_t cells = (size_t)n_cams * (size_t)n_slots;
+  buf.check(hipMemsetAsync(dxy, 0xff, cells * 2 * sizeof(double), 0));
+  if (!buf.status()) buf.check(hipMemsetAsync(dft, 0xff, cells * sizeof(double), 0));
+  if (buf.status()) return buf.result(what);
+  hipLaunchKernelGGL(k_traj_fill2d, dim3(blocks(n_rows)), dim3(TRAJ_BLOCK), 0, 0, n_rows, n_traj, n_slots, drcam, drslot, drxy, drt, (int)d->xy_gap, dxy, dft);
+  hipLaunchKernelGGL(k_traj_frame_time, dim3(blocks(n_frames)), dim3(TRAJ_BLOCK), 0, 0, n_cams, n_frames, n_traj, n_slots, dft, dframe);
+  hipLaunchKernelGGL(k_traj_triangulate, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), 0, 0, n_cams, n_traj, n_slots, dposed, dmodel, dintr, dP, dxy,
+                     dframe, d->float32_io ? 1 : 0, dxyz, dvalid, dtime);
   if (d->xyz_gap > 0)
-    hipLaunchKernelGGL(k_traj_fill3d, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), 0, 0, n_frames, n_traj, n_slots, (int)d->xyz_gap, (uint8_t*)dvalid,
-                       (double*)dxyz, (double*)dtime);
+    hipLaunchKernelGGL(k_traj_fill3d, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), 0, 0, n_frames, n_traj, n_slots, (int)d->xyz_gap, dvalid, dxyz, dtime);
   if (d->filter_b)
-    hipLaunchKernelGGL(k_traj_filtfilt, dim3(blocks(3 * n_traj)), dim3(TRAJ_BLOCK), 0, 0, n_frames, n_traj, order, (const double*)db, (const double*)da,
-                       (const double*)dzi, (const uint8_t*)dvalid, (double*)dxyz, (double*)dscratch);
-  e = hipGetLastError();
-  if (e == hipSuccess && out->xyz) e = hipMemcpy(out->xyz, dxyz, (size_t)n_slots * 3 * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out->valid) e = hipMemcpy(out->valid, dvalid, (size_t)n_slots, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out->slot_time) e = hipMemcpy(out->slot_time, dtime, (size_t)n_slots * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out->frame_time) e = hipMemcpy(out->frame_time, dframe, (size_t)n_frames * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out->xy_filled) e = hipMemcpy(out->xy_filled, dxy, cells * 2 * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out->ft_filled) e = hipMemcpy(out->ft_filled, dft, cells * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  return CBA_OK;
+    hipLaunchKernelGGL(k_traj_filtfilt, dim3(blocks(3 * n_traj)), dim3(TRAJ_BLOCK), 0, 0, n_frames, n_traj, order, db, da, dzi, dvalid, dxyz,
+                       dscratch);
+  buf.check(hipGetLastError());
+  buf.out(out->xyz, dxyz, n_slots, 3);
+  buf.out(out->valid, dvalid, n_slots);
+  buf.out(out->slot_time, dtime, n_slots);
+  buf.out(out->frame_time, dframe, n_frames);
+  buf.out(out->xy_filled, dxy, n_cams, n_slots, 2);
+  buf.out(out->ft_filled, dft, n_cams, n_slots);
+  if (!buf.status()) buf.check(hipDeviceSynchronize());
+  return buf.result(what);
 }

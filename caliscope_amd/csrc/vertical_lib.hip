@@ -97,23 +97,27 @@ k_vert_update(const int64_t* __restrict__ first_chunk, const int32_t* __restrict
   }
 }
 
+// The planes (float32 or float64: T), the work buffers and the passes of one call; the states come back in `state`.
 template <typename T>
-hipError_t run(const cba_vertical_desc* d, int64_t total_chunks, const int32_t* dcfit, const int64_t* dfirst, const int32_t* dh, const int32_t* dw,
-               const double* dfx, const double* dfy, const int64_t* doff, void* const* dplane, double* dsin, double* dpart, VertState* dstate) {
-  const T* up_x = (const T*)dplane[0];
-  const T* up_y = (const T*)dplane[1];
-  const T* up_conf = (const T*)dplane[2];
-  const T* lat = (const T*)dplane[3];
-  const T* lat_conf = (const T*)dplane[4];
+void run(Buffers& buf, const cba_vertical_desc* d, const void* const* planes, int64_t total_chunks, const int32_t* dcfit, const int64_t* dfirst,
+         const int32_t* dh, const int32_t* dw, const double* dfx, const double* dfy, const int64_t* doff, std::vector<VertState>& state) {
+  const T* plane[5];
+  for (int k = 0; k < 5; ++k) plane[k] = buf.in((const T*)planes[k], d->n_pixels);
+  const T *up_x = plane[0], *up_y = plane[1], *up_conf = plane[2], *lat = plane[3], *lat_conf = plane[4];
+  double* dsin = buf.make<double>(d->n_pixels);
+  double* dpart = buf.make<double>(total_chunks, VERT_NSUM);
+  VertState* dstate = buf.in(state.data(), d->n_fits);
+  if (buf.status()) return;
   hipLaunchKernelGGL(k_vert_sinlat<T>, dim3((unsigned)((d->n_pixels + VERT_BLOCK - 1) / VERT_BLOCK)), dim3(VERT_BLOCK), 0, 0, d->n_pixels, lat, dsin);
   hipError_t e = hipGetLastError();
   for (int32_t pass = 0; pass <= d->num_steps && e == hipSuccess; ++pass) {
     hipLaunchKernelGGL(k_vert_partial<T>, dim3((unsigned)total_chunks), dim3(VERT_BLOCK), 0, 0, dcfit, dfirst, dh, dw, dfx, dfy, doff, up_x, up_y, up_conf,
-                       (const double*)dsin, lat_conf, (const VertState*)dstate, dpart);
-    hipLaunchKernelGGL(k_vert_update, dim3((unsigned)d->n_fits), dim3(VERT_WAVE), 0, 0, dfirst, dh, dw, (const double*)dpart, dstate, pass, d->num_steps);
+                       dsin, lat_conf, dstate, dpart);
+    hipLaunchKernelGGL(k_vert_update, dim3((unsigned)d->n_fits), dim3(VERT_WAVE), 0, 0, dfirst, dh, dw, dpart, dstate, pass, d->num_steps);
     e = hipGetLastError();
   }
-  return e;
+  buf.check(e);
+  buf.out(state.data(), dstate, d->n_fits);
 }
 
 }  // namespace
@@ -149,28 +153,16 @@ extern "C" int cba_vertical_fit(const cba_vertical_desc* d, int32_t device, doub
   rc = select_device(device, what);
   if (rc) return rc;
   Buffers buf;
-  const size_t elem = d->is_f32 ? sizeof(float) : sizeof(double);
-  void *dcfit = nullptr, *dfirst = nullptr, *dh = nullptr, *dw = nullptr, *dfx = nullptr, *dfy = nullptr, *doff = nullptr, *dsin = nullptr, *dpart = nullptr,
-       *dstate = nullptr;
-  void* dplane[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  rc = buf.up(cfit.data(), (size_t)total * sizeof(int32_t), &dcfit);
-  if (!rc) rc = buf.up(first.data(), (size_t)n_fits * sizeof(int64_t), &dfirst);
-  if (!rc) rc = buf.up(d->height, (size_t)n_fits * sizeof(int32_t), &dh);
-  if (!rc) rc = buf.up(d->width, (size_t)n_fits * sizeof(int32_t), &dw);
-  if (!rc) rc = buf.up(d->focal_x, (size_t)n_fits * sizeof(double), &dfx);
-  if (!rc) rc = buf.up(d->focal_y, (size_t)n_fits * sizeof(double), &dfy);
-  if (!rc) rc = buf.up(d->offset, (size_t)n_fits * sizeof(int64_t), &doff);
-  for (int k = 0; k < 5 && !rc; ++k) rc = buf.up(planes[k], (size_t)d->n_pixels * elem, &dplane[k]);
-  if (!rc) rc = buf.up(nullptr, (size_t)d->n_pixels * sizeof(double), &dsin);
-  if (!rc) rc = buf.up(nullptr, (size_t)total * VERT_NSUM * sizeof(double), &dpart);
-  if (!rc) rc = buf.up(state.data(), (size_t)n_fits * sizeof(VertState), &dstate);
-  if (rc) return err(CBA_ERR_HIP, std::string(what) + ": device allocation / upload failed");
-  hipError_t e = d->is_f32 ? run<float>(d, total, (const int32_t*)dcfit, (const int64_t*)dfirst, (const int32_t*)dh, (const int32_t*)dw, (const double*)dfx,
-                                        (const double*)dfy, (const int64_t*)doff, dplane, (double*)dsin, (double*)dpart, (VertState*)dstate)
-                           : run<double>(d, total, (const int32_t*)dcfit, (const int64_t*)dfirst, (const int32_t*)dh, (const int32_t*)dw, (const double*)dfx,
-                                         (const double*)dfy, (const int64_t*)doff, dplane, (double*)dsin, (double*)dpart, (VertState*)dstate);
-  if (e == hipSuccess) e = hipMemcpy(state.data(), dstate, (size_t)n_fits * sizeof(VertState), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  const int32_t* dcfit = buf.in(cfit.data(), total);
+  const int64_t* dfirst = buf.in(first.data(), n_fits);
+  const int32_t* dh = buf.in(d->height, n_fits);
+  const int32_t* dw = buf.in(d->width, n_fits);
+  const double* dfx = buf.in(d->focal_x, n_fits);
+  const double* dfy = buf.in(d->focal_y, n_fits);
+  const int64_t* doff = buf.in(d->offset, n_fits);
+  if (d->is_f32) run<float>(buf, d, planes, total, dcfit, dfirst, dh, dw, dfx, dfy, doff, state);
+  else run<double>(buf, d, planes, total, dcfit, dfirst, dh, dw, dfx, dfy, doff, state);
+  if (buf.status()) return buf.result(what);
   for (int32_t f = 0; f < n_fits; ++f) {
     for (int k = 0; k < 8; ++k) fit_out[(size_t)f * 8 + k] = state[f].out[k];
     stop_step_out[f] = state[f].stop_step;

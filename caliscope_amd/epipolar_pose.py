@@ -37,7 +37,7 @@ import numpy as np
 from caliscope_amd import _lib
 from caliscope_amd.exceptions import CalibrationError
 from caliscope_amd.pose_network import (
-    DevicePnP, PairedPoseNetwork, StereoPair, _group_starts, _intrinsic_tables, _load, _pairs_within_groups, _ptr, common_observations,
+    DevicePnP, PairedPoseNetwork, StereoPair, _group_starts, _intrinsic_tables, _pairs_within_groups, common_observations,
     estimate_pnp_paired_pose_network,
 )
 
@@ -73,26 +73,12 @@ class ResectDesc(C.Structure):
     ]
 
 
-_u8_p = C.POINTER(C.c_uint8)
 EPI_SIGNATURES = {
     "cba_pose_essential_batch": (C.c_int, [C.POINTER(EssentialDesc), C.c_int32, _lib.c_double_p, _lib.c_int32_p, _lib.c_int64_p, _lib.c_int64_p,
-                                           _lib.c_double_p, _lib.c_int32_p, _u8_p, _lib.c_double_p, _lib.c_double_p]),
+                                           _lib.c_double_p, _lib.c_int32_p, _lib.c_uint8_p, _lib.c_double_p, _lib.c_double_p]),
     "cba_pose_resect_batch": (C.c_int, [C.POINTER(ResectDesc), C.c_int32, _lib.c_double_p, _lib.c_int32_p, _lib.c_int64_p, _lib.c_int32_p,
                                         _lib.c_double_p]),
 }
-
-
-def _load_epi():
-    lib = _load()
-    for name, (res, args) in EPI_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            from caliscope_amd.exceptions import BackendError
-
-            raise BackendError(f"{_lib.LIB_PATH} does not export {name} (stale build?)") from exc
-        fn.restype, fn.argtypes = res, args
-    return lib
 
 
 class DeviceEpipolar:
@@ -105,7 +91,7 @@ class DeviceEpipolar:
     def essential_batch(self, cam_model, cam_intr, obs_xy, obs_cam, pair_start, corr_a, corr_b, threshold, n_hyp, seed, float32_io=False):
         """Returns a dict: pose[n_pairs, 12], status, n_inliers, n_cheiral, conditioning, winner, flag[n_corr], xyz[n_corr, 3],
         undistorted[n_obs, 2]."""
-        lib = _load_epi()
+        lib = _lib.bind(_lib.load(), EPI_SIGNATURES)
         cam_model = np.ascontiguousarray(cam_model, dtype=np.int32)
         cam_intr = np.ascontiguousarray(cam_intr, dtype=np.float64)
         obs_xy = np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2)
@@ -119,19 +105,19 @@ class DeviceEpipolar:
         n_inl, n_chr = np.zeros(n_pairs, dtype=np.int64), np.zeros(n_pairs, dtype=np.int64)
         cond, winner = np.zeros(n_pairs), np.zeros(n_pairs, dtype=np.int32)
         flag, xyz, und = np.zeros(n_corr, dtype=np.uint8), np.zeros((n_corr, 3)), np.zeros_like(obs_xy)
-        desc = EssentialDesc(n_cams=len(cam_model), cam_model=_ptr(cam_model, C.c_int32), cam_intr=_ptr(cam_intr), n_obs=len(obs_xy),
-                             obs_xy=_ptr(obs_xy), obs_cam=_ptr(obs_cam, C.c_int32), n_pairs=n_pairs, pair_start=_ptr(pair_start, C.c_int64),
-                             corr_a=_ptr(corr_a, C.c_int64), corr_b=_ptr(corr_b, C.c_int64), threshold=_ptr(threshold), n_hyp=int(n_hyp),
+        desc = EssentialDesc(n_cams=len(cam_model), cam_model=_lib.ptr(cam_model), cam_intr=_lib.ptr(cam_intr), n_obs=len(obs_xy),
+                             obs_xy=_lib.ptr(obs_xy), obs_cam=_lib.ptr(obs_cam), n_pairs=n_pairs, pair_start=_lib.ptr(pair_start),
+                             corr_a=_lib.ptr(corr_a), corr_b=_lib.ptr(corr_b), threshold=_lib.ptr(threshold), n_hyp=int(n_hyp),
                              seed=int(seed), float32_io=1 if float32_io else 0)
-        rc = lib.cba_pose_essential_batch(C.byref(desc), self.device_id, _ptr(pose), _ptr(status, C.c_int32), _ptr(n_inl, C.c_int64),
-                                          _ptr(n_chr, C.c_int64), _ptr(cond), _ptr(winner, C.c_int32), _ptr(flag, C.c_uint8), _ptr(xyz), _ptr(und))
+        rc = lib.cba_pose_essential_batch(C.byref(desc), self.device_id, _lib.ptr(pose), _lib.ptr(status), _lib.ptr(n_inl),
+                                          _lib.ptr(n_chr), _lib.ptr(cond), _lib.ptr(winner), _lib.ptr(flag), _lib.ptr(xyz), _lib.ptr(und))
         _lib.check(lib, rc, "cba_pose_essential_batch")
         return dict(pose=pose, status=status, n_inliers=n_inl, n_cheiral=n_chr, conditioning=cond, winner=winner, flag=flag, xyz=xyz,
                     undistorted=und)
 
     def resect_batch(self, job_start, obj, uv, threshold, n_hyp, min_points, seed):
         """Returns a dict: pose[n_jobs, 12], status, n_inliers, winner, err[n]."""
-        lib = _load_epi()
+        lib = _lib.bind(_lib.load(), EPI_SIGNATURES)
         job_start = np.ascontiguousarray(job_start, dtype=np.int64)
         obj = np.ascontiguousarray(obj, dtype=np.float64).reshape(-1, 3)
         uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1, 2)
@@ -139,10 +125,10 @@ class DeviceEpipolar:
         n_jobs = len(job_start) - 1
         pose, status = np.zeros((n_jobs, 12)), np.zeros(n_jobs, dtype=np.int32)
         n_inl, winner, err = np.zeros(n_jobs, dtype=np.int64), np.zeros(n_jobs, dtype=np.int32), np.zeros(len(obj))
-        desc = ResectDesc(n_jobs=n_jobs, job_start=_ptr(job_start, C.c_int64), obj=_ptr(obj), uv=_ptr(uv), threshold=_ptr(threshold),
+        desc = ResectDesc(n_jobs=n_jobs, job_start=_lib.ptr(job_start), obj=_lib.ptr(obj), uv=_lib.ptr(uv), threshold=_lib.ptr(threshold),
                           n_hyp=int(n_hyp), min_points=int(min_points), seed=int(seed))
-        rc = lib.cba_pose_resect_batch(C.byref(desc), self.device_id, _ptr(pose), _ptr(status, C.c_int32), _ptr(n_inl, C.c_int64),
-                                       _ptr(winner, C.c_int32), _ptr(err))
+        rc = lib.cba_pose_resect_batch(C.byref(desc), self.device_id, _lib.ptr(pose), _lib.ptr(status), _lib.ptr(n_inl),
+                                       _lib.ptr(winner), _lib.ptr(err))
         _lib.check(lib, rc, "cba_pose_resect_batch")
         return dict(pose=pose, status=status, n_inliers=n_inl, winner=winner, err=err)
 

@@ -38,14 +38,12 @@ from types import SimpleNamespace
 import numpy as np
 
 from caliscope_amd import _lib
-from caliscope_amd.exceptions import BackendError
 
 logger = logging.getLogger(__name__)
 
 MAX_GRID_SIZE = 8  # the cell mask has 64 bits
 NUM_TILT_DIRECTION_BINS = 8
 HOMOG_OK, HOMOG_TOO_FEW, HOMOG_FAILED = 0, 1, 2
-c_uint64_p = C.POINTER(C.c_uint64)
 
 
 @dataclass(frozen=True)
@@ -137,24 +135,19 @@ class FrameSelectDesc(C.Structure):
 
 
 FRAME_SELECT_SIGNATURES = {
-    "cba_pose_select_frames": (C.c_int, [C.POINTER(FrameSelectDesc), C.c_int32, c_uint64_p, _lib.c_double_p, _lib.c_double_p, _lib.c_int32_p,
+    "cba_pose_select_frames": (C.c_int, [C.POINTER(FrameSelectDesc), C.c_int32, _lib.c_uint64_p, _lib.c_double_p, _lib.c_double_p, _lib.c_int32_p,
                                          _lib.c_double_p, _lib.c_int32_p, _lib.c_int32_p, _lib.c_int32_p, _lib.c_int32_p, _lib.c_int32_p]),
 }
 
 
+# Kept for tests/test_frame_selection_gpu.py alone, which calls the library directly through these two names (the module itself
+# uses _lib.bind / _lib.ptr): _ptr takes the element type that test passes and does not use it, the array's dtype decides.
 def _load():
-    lib = _lib.load()
-    for name, (res, args) in FRAME_SELECT_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise BackendError(f"{_lib.LIB_PATH} does not export {name} (stale build?)") from exc
-        fn.restype, fn.argtypes = res, args
-    return lib
+    return _lib.bind(_lib.load(), FRAME_SELECT_SIGNATURES)
 
 
-def _ptr(a, ctype=C.c_double):
-    return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
+def _ptr(a, ctype=None):
+    return _lib.ptr(a)
 
 
 class DeviceFrameSelection:
@@ -169,16 +162,16 @@ class DeviceFrameSelection:
         :class:`FrameSelection`."""
         a = check_selection_arguments(cam_frame_start, cam_size, frame_start, obs_xy, obs_obj, homog_start, homog_count, grid_size, min_corners,
                                       target_count)
-        lib = _load()
+        lib = _lib.bind(_lib.load(), FRAME_SELECT_SIGNATURES)
         out = FrameSelection.empty(a.n_cams, a.n_frames, a.target_count)
-        desc = FrameSelectDesc(n_cams=a.n_cams, cam_frame_start=_ptr(a.cam_frame_start, C.c_int64), cam_size=_ptr(a.cam_size), n_frames=a.n_frames,
-                               frame_start=_ptr(a.frame_start, C.c_int64), homog_start=_ptr(a.homog_start, C.c_int64),
-                               homog_count=_ptr(a.homog_count, C.c_int32), obs_xy=_ptr(a.obs_xy), obs_obj=_ptr(a.obs_obj), grid_size=a.grid_size,
+        desc = FrameSelectDesc(n_cams=a.n_cams, cam_frame_start=_lib.ptr(a.cam_frame_start), cam_size=_lib.ptr(a.cam_size), n_frames=a.n_frames,
+                               frame_start=_lib.ptr(a.frame_start), homog_start=_lib.ptr(a.homog_start),
+                               homog_count=_lib.ptr(a.homog_count), obs_xy=_lib.ptr(a.obs_xy), obs_obj=_lib.ptr(a.obs_obj), grid_size=a.grid_size,
                                min_corners=a.min_corners, target_count=a.target_count, float32_io=1 if float32_io else 0)
-        rc = lib.cba_pose_select_frames(C.byref(desc), self.device_id, _ptr(out.cell_mask, C.c_uint64), _ptr(out.pose_features), _ptr(out.orientation),
-                                        _ptr(out.homography_status, C.c_int32), _ptr(out.homography_rmse), _ptr(out.selected, C.c_int32),
-                                        _ptr(out.n_selected, C.c_int32), _ptr(out.n_anchors, C.c_int32), _ptr(out.bin_mask, C.c_int32),
-                                        _ptr(out.eligible, C.c_int32))
+        rc = lib.cba_pose_select_frames(C.byref(desc), self.device_id, _lib.ptr(out.cell_mask), _lib.ptr(out.pose_features), _lib.ptr(out.orientation),
+                                        _lib.ptr(out.homography_status), _lib.ptr(out.homography_rmse), _lib.ptr(out.selected),
+                                        _lib.ptr(out.n_selected), _lib.ptr(out.n_anchors), _lib.ptr(out.bin_mask),
+                                        _lib.ptr(out.eligible))
         _lib.check(lib, rc, "cba_pose_select_frames")
         return out
 

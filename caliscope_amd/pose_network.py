@@ -40,7 +40,6 @@ import numpy as np
 from scipy.spatial.transform import Rotation
 
 from caliscope_amd import _lib
-from caliscope_amd.exceptions import BackendError
 
 logger = logging.getLogger(__name__)
 
@@ -73,21 +72,6 @@ POSE_SIGNATURES = {
 }
 
 
-def _load():
-    lib = _lib.load()
-    for name, (res, args) in POSE_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise BackendError(f"{_lib.LIB_PATH} does not export {name} (stale build?)") from exc
-        fn.restype, fn.argtypes = res, args
-    return lib
-
-
-def _ptr(a, ctype=C.c_double):
-    return a.ctypes.data_as(C.POINTER(ctype))
-
-
 class DevicePnP:
     """The two device calls of the bootstrap (``cba_pose_pnp_batch``, ``cba_pose_pair_rmse``) on ``device_id``."""
 
@@ -96,7 +80,7 @@ class DevicePnP:
 
     def pnp_batch(self, view_start, view_cam, cam_model, cam_intr, obs_xy, obs_obj, min_points, float32_io):
         """Returns ``(pose[n_views, 12], rmse[n_views], status[n_views], undistorted[n_obs, 2])``."""
-        lib = _load()
+        lib = _lib.bind(_lib.load(), POSE_SIGNATURES)
         view_start = np.ascontiguousarray(view_start, dtype=np.int64)
         view_cam = np.ascontiguousarray(view_cam, dtype=np.int32)
         cam_model = np.ascontiguousarray(cam_model, dtype=np.int32)
@@ -106,24 +90,24 @@ class DevicePnP:
         n_views = len(view_start) - 1
         pose, rmse = np.zeros((n_views, 12)), np.zeros(n_views)
         status, und = np.zeros(n_views, dtype=np.int32), np.zeros_like(obs_xy)
-        desc = PnpDesc(n_cams=len(cam_model), cam_model=_ptr(cam_model, C.c_int32), cam_intr=_ptr(cam_intr), n_views=n_views,
-                       view_start=_ptr(view_start, C.c_int64), view_cam=_ptr(view_cam, C.c_int32), obs_xy=_ptr(obs_xy),
-                       obs_obj=_ptr(obs_obj), min_points=int(min_points), float32_io=1 if float32_io else 0)
-        rc = lib.cba_pose_pnp_batch(C.byref(desc), self.device_id, _ptr(pose), _ptr(rmse), _ptr(status, C.c_int32), _ptr(und))
+        desc = PnpDesc(n_cams=len(cam_model), cam_model=_lib.ptr(cam_model), cam_intr=_lib.ptr(cam_intr), n_views=n_views,
+                       view_start=_lib.ptr(view_start), view_cam=_lib.ptr(view_cam), obs_xy=_lib.ptr(obs_xy),
+                       obs_obj=_lib.ptr(obs_obj), min_points=int(min_points), float32_io=1 if float32_io else 0)
+        rc = lib.cba_pose_pnp_batch(C.byref(desc), self.device_id, _lib.ptr(pose), _lib.ptr(rmse), _lib.ptr(status), _lib.ptr(und))
         _lib.check(lib, rc, "cba_pose_pnp_batch")
         return pose, rmse, status, und
 
     def pair_rmse(self, pair_pose, pair_start, obs_a, obs_b):
         """Returns ``(rmse[n_pairs], count[n_pairs])``."""
-        lib = _load()
+        lib = _lib.bind(_lib.load(), POSE_SIGNATURES)
         pair_pose = np.ascontiguousarray(pair_pose, dtype=np.float64)
         pair_start = np.ascontiguousarray(pair_start, dtype=np.int64)
         obs_a = np.ascontiguousarray(obs_a, dtype=np.float64)
         obs_b = np.ascontiguousarray(obs_b, dtype=np.float64)
         n_pairs = len(pair_start) - 1
         rmse, count = np.zeros(n_pairs), np.zeros(n_pairs, dtype=np.int64)
-        desc = PairDesc(n_pairs=n_pairs, pair_pose=_ptr(pair_pose), pair_start=_ptr(pair_start, C.c_int64), obs_a=_ptr(obs_a), obs_b=_ptr(obs_b))
-        rc = lib.cba_pose_pair_rmse(C.byref(desc), self.device_id, _ptr(rmse), _ptr(count, C.c_int64))
+        desc = PairDesc(n_pairs=n_pairs, pair_pose=_lib.ptr(pair_pose), pair_start=_lib.ptr(pair_start), obs_a=_lib.ptr(obs_a), obs_b=_lib.ptr(obs_b))
+        rc = lib.cba_pose_pair_rmse(C.byref(desc), self.device_id, _lib.ptr(rmse), _lib.ptr(count))
         _lib.check(lib, rc, "cba_pose_pair_rmse")
         return rmse, count
 

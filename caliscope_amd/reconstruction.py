@@ -33,36 +33,24 @@ from caliscope_amd.exceptions import BackendError
 from caliscope_amd.point_data import WORLD_POINT_COLUMNS, ImagePoints, WorldPoints
 
 MAX_ORDER = 8
-c_uint8_p = C.POINTER(C.c_uint8)
 
 
 class TrajDesc(C.Structure):
     _fields_ = [("n_cams", C.c_int32), ("n_frames", C.c_int64), ("n_traj", C.c_int64), ("n_rows", C.c_int64),
-                ("cam_model", _lib.c_int32_p), ("cam_intr", _lib.c_double_p), ("cam_P", _lib.c_double_p), ("cam_posed", c_uint8_p),
+                ("cam_model", _lib.c_int32_p), ("cam_intr", _lib.c_double_p), ("cam_P", _lib.c_double_p), ("cam_posed", _lib.c_uint8_p),
                 ("row_cam", _lib.c_int32_p), ("row_slot", _lib.c_int64_p), ("row_xy", _lib.c_double_p), ("row_time", _lib.c_double_p),
                 ("xy_gap", C.c_int32), ("xyz_gap", C.c_int32), ("float32_io", C.c_int32), ("filter_order", C.c_int32),
                 ("filter_b", _lib.c_double_p), ("filter_a", _lib.c_double_p), ("filter_zi", _lib.c_double_p), ("memory_limit", C.c_int64)]
 
 
 class TrajOut(C.Structure):
-    _fields_ = [("xyz", _lib.c_double_p), ("valid", c_uint8_p), ("slot_time", _lib.c_double_p), ("frame_time", _lib.c_double_p),
+    _fields_ = [("xyz", _lib.c_double_p), ("valid", _lib.c_uint8_p), ("slot_time", _lib.c_double_p), ("frame_time", _lib.c_double_p),
                 ("xy_filled", _lib.c_double_p), ("ft_filled", _lib.c_double_p)]
 
 
 TRAJECTORY_SIGNATURES = {
     "cba_reconstruct_trajectories": (C.c_int, [C.POINTER(TrajDesc), C.c_int32, C.POINTER(TrajOut)]),
 }
-
-
-def _load():
-    lib = _lib.load()
-    for name, (res, args) in TRAJECTORY_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise BackendError(f"{_lib.LIB_PATH} does not export {name} (stale build?)") from exc
-        fn.restype, fn.argtypes = res, args
-    return lib
 
 
 @dataclass(frozen=True)
@@ -167,10 +155,6 @@ def filter_coefficients(smooth):
     return int(order), np.ascontiguousarray(b, dtype=np.float64), np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(lfilter_zi(b, a))
 
 
-def _ptr(a, ctype):
-    return a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None
-
-
 def run_trajectory_call(call, grid: TrajectoryGrid, xy_gap: int, xyz_gap: int, filt, float32_io: bool, memory_limit: int, want_grids: bool, what: str,
                         last_error) -> TrajectoryResult:
     """Fill ``cba_traj_desc`` / ``cba_traj_out``, run ``call(desc_ref, out_ref) -> code`` and collect the result (shared by the device
@@ -182,14 +166,14 @@ def run_trajectory_call(call, grid: TrajectoryGrid, xy_gap: int, xyz_gap: int, f
     xy_filled = np.empty((n_cams, n_slots, 2)) if want_grids else None
     ft_filled = np.empty((n_cams, n_slots)) if want_grids else None
     order, b, a, zi = filt if filt is not None else (0, None, None, None)
-    desc = TrajDesc(n_cams=n_cams, n_frames=grid.n_frames, n_traj=grid.n_traj, n_rows=len(grid.row_cam), cam_model=_ptr(grid.cam_model, C.c_int32),
-                    cam_intr=_ptr(grid.cam_intr, C.c_double), cam_P=_ptr(grid.cam_P, C.c_double), cam_posed=_ptr(grid.cam_posed, C.c_uint8),
-                    row_cam=_ptr(grid.row_cam, C.c_int32), row_slot=_ptr(grid.row_slot, C.c_int64), row_xy=_ptr(grid.row_xy, C.c_double),
-                    row_time=_ptr(grid.row_time, C.c_double), xy_gap=int(xy_gap), xyz_gap=int(xyz_gap), float32_io=1 if float32_io else 0,
-                    filter_order=order, filter_b=_ptr(b, C.c_double), filter_a=_ptr(a, C.c_double), filter_zi=_ptr(zi, C.c_double),
+    desc = TrajDesc(n_cams=n_cams, n_frames=grid.n_frames, n_traj=grid.n_traj, n_rows=len(grid.row_cam), cam_model=_lib.ptr(grid.cam_model),
+                    cam_intr=_lib.ptr(grid.cam_intr), cam_P=_lib.ptr(grid.cam_P), cam_posed=_lib.ptr(grid.cam_posed),
+                    row_cam=_lib.ptr(grid.row_cam), row_slot=_lib.ptr(grid.row_slot), row_xy=_lib.ptr(grid.row_xy),
+                    row_time=_lib.ptr(grid.row_time), xy_gap=int(xy_gap), xyz_gap=int(xyz_gap), float32_io=1 if float32_io else 0,
+                    filter_order=order, filter_b=_lib.ptr(b), filter_a=_lib.ptr(a), filter_zi=_lib.ptr(zi),
                     memory_limit=int(memory_limit))
-    out = TrajOut(xyz=_ptr(xyz, C.c_double), valid=_ptr(valid, C.c_uint8), slot_time=_ptr(slot_time, C.c_double), frame_time=_ptr(frame_time, C.c_double),
-                  xy_filled=_ptr(xy_filled, C.c_double), ft_filled=_ptr(ft_filled, C.c_double))
+    out = TrajOut(xyz=_lib.ptr(xyz), valid=_lib.ptr(valid), slot_time=_lib.ptr(slot_time), frame_time=_lib.ptr(frame_time),
+                  xy_filled=_lib.ptr(xy_filled), ft_filled=_lib.ptr(ft_filled))
     rc = call(C.byref(desc), C.byref(out))
     if rc in (-1, -4):
         raise ValueError(last_error())
@@ -207,7 +191,7 @@ class DeviceTrajectorySolver:
         self.memory_limit = memory_limit
 
     def reconstruct(self, grid: TrajectoryGrid, *, xy_gap=0, xyz_gap=0, filt=None, float32_io=True, want_grids=False) -> TrajectoryResult:
-        lib = _load()
+        lib = _lib.bind(_lib.load(), TRAJECTORY_SIGNATURES)
         return run_trajectory_call(lambda d, o: lib.cba_reconstruct_trajectories(d, self.device_id, o), grid, xy_gap, xyz_gap, filt, float32_io,
                                    self.memory_limit, want_grids, "cba_reconstruct_trajectories", lambda: _lib.last_error(lib))
 

@@ -30,8 +30,6 @@ from caliscope_amd.exceptions import BackendError
 MODES = {"stats": 0, "percentile": 1, "absolute": 2}
 SCOPES = {"per_camera": 0, "overall": 1}
 
-c_uint8_p = C.POINTER(C.c_uint8)
-
 
 class ReportDesc(C.Structure):
     _fields_ = [("n_cams", C.c_int32), ("n_points", C.c_int64), ("n_obs", C.c_int64), ("n_groups", C.c_int32),
@@ -43,24 +41,13 @@ class ReportDesc(C.Structure):
 class ReportOut(C.Structure):
     _fields_ = [("err_xy", _lib.c_double_p), ("err", _lib.c_double_p), ("cam_sumsq", _lib.c_double_p), ("cam_count", _lib.c_int64_p),
                 ("group_sumsq", _lib.c_double_p), ("group_count", _lib.c_int64_p), ("overall_sumsq", _lib.c_double_p),
-                ("n_nonfinite", _lib.c_int64_p), ("cam_threshold", _lib.c_double_p), ("keep", c_uint8_p), ("cam_kept", _lib.c_int64_p),
+                ("n_nonfinite", _lib.c_int64_p), ("cam_threshold", _lib.c_double_p), ("keep", _lib.c_uint8_p), ("cam_kept", _lib.c_int64_p),
                 ("n_floor_cams", _lib.c_int64_p)]
 
 
 REPORT_SIGNATURES = {
     "cba_reprojection_filter": (C.c_int, [C.POINTER(ReportDesc), C.c_int32, C.POINTER(ReportOut)]),
 }
-
-
-def _load():
-    lib = _lib.load()
-    for name, (res, args) in REPORT_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise BackendError(f"{_lib.LIB_PATH} does not export {name} (stale build?)") from exc
-        fn.restype, fn.argtypes = res, args
-    return lib
 
 
 @dataclass(frozen=True)
@@ -121,10 +108,6 @@ def check_reprojection_arguments(cam_model, cam_const, cam_pose, points, obs_cam
                 value=float(value), min_per_camera=int(min_per_camera))
 
 
-def _ptr(a, ctype):
-    return a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None
-
-
 def run_reprojection_call(call, args: dict, want_errors: bool, what: str, last_error) -> ReprojectionFilterResult:
     """Fill ``cba_report_desc`` / ``cba_report_out`` from checked arguments, run ``call(desc_ref, out_ref) -> code`` and collect the
     result (shared by the device binding and the test harness: same structures, same error type and message)."""
@@ -138,15 +121,15 @@ def run_reprojection_call(call, args: dict, want_errors: bool, what: str, last_e
     threshold = np.zeros(n_cams) if filtering else None
     keep = np.zeros(n_obs, dtype=np.uint8) if filtering else None
     kept = np.zeros(n_cams, dtype=np.int64) if filtering else None
-    desc = ReportDesc(n_cams=n_cams, n_points=len(args["points"]), n_obs=n_obs, n_groups=n_groups, cam_model=_ptr(args["cam_model"], C.c_int32),
-                      cam_const=_ptr(args["cam_const"], C.c_double), cam_pose=_ptr(args["cam_pose"], C.c_double), points=_ptr(args["points"], C.c_double),
-                      obs_cam=_ptr(args["obs_cam"], C.c_int32), obs_pt=_ptr(args["obs_pt"], C.c_int32), obs_uv=_ptr(args["obs_uv"], C.c_double),
-                      obs_group=_ptr(args["obs_group"], C.c_int32), err_in=_ptr(args["err_in"], C.c_double), mode=args["mode"], scope=args["scope"],
+    desc = ReportDesc(n_cams=n_cams, n_points=len(args["points"]), n_obs=n_obs, n_groups=n_groups, cam_model=_lib.ptr(args["cam_model"]),
+                      cam_const=_lib.ptr(args["cam_const"]), cam_pose=_lib.ptr(args["cam_pose"]), points=_lib.ptr(args["points"]),
+                      obs_cam=_lib.ptr(args["obs_cam"]), obs_pt=_lib.ptr(args["obs_pt"]), obs_uv=_lib.ptr(args["obs_uv"]),
+                      obs_group=_lib.ptr(args["obs_group"]), err_in=_lib.ptr(args["err_in"]), mode=args["mode"], scope=args["scope"],
                       value=args["value"], min_per_camera=args["min_per_camera"])
-    out = ReportOut(err_xy=_ptr(err_xy, C.c_double), err=_ptr(err, C.c_double), cam_sumsq=_ptr(cam_sumsq, C.c_double), cam_count=_ptr(cam_count, C.c_int64),
-                    group_sumsq=_ptr(group_sumsq, C.c_double), group_count=_ptr(group_count, C.c_int64), overall_sumsq=_ptr(overall, C.c_double),
-                    n_nonfinite=_ptr(n_bad, C.c_int64), cam_threshold=_ptr(threshold, C.c_double), keep=_ptr(keep, C.c_uint8),
-                    cam_kept=_ptr(kept, C.c_int64), n_floor_cams=_ptr(n_floor, C.c_int64))
+    out = ReportOut(err_xy=_lib.ptr(err_xy), err=_lib.ptr(err), cam_sumsq=_lib.ptr(cam_sumsq), cam_count=_lib.ptr(cam_count),
+                    group_sumsq=_lib.ptr(group_sumsq), group_count=_lib.ptr(group_count), overall_sumsq=_lib.ptr(overall),
+                    n_nonfinite=_lib.ptr(n_bad), cam_threshold=_lib.ptr(threshold), keep=_lib.ptr(keep),
+                    cam_kept=_lib.ptr(kept), n_floor_cams=_lib.ptr(n_floor))
     rc = call(C.byref(desc), C.byref(out))
     if rc != 0:
         raise BackendError(f"{what} failed (code {rc}): {last_error()}")
@@ -171,7 +154,7 @@ class DeviceReprojectionStats:
         kept), the keep mask of one call; see ``include/caliscope_report.h``."""
         args = check_reprojection_arguments(cam_model, cam_const, cam_pose, points, obs_cam, obs_pt, obs_uv, obs_group, n_groups,
                                             self.err_in if self.err_in is not None else err_in, mode, scope, value, min_per_camera)
-        lib = _load()
+        lib = _lib.bind(_lib.load(), REPORT_SIGNATURES)
         return run_reprojection_call(lambda d, o: lib.cba_reprojection_filter(d, self.device_id, o), args, want_errors, "cba_reprojection_filter",
                                      lambda: _lib.last_error(lib))
 

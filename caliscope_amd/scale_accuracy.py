@@ -141,10 +141,6 @@ class VolumetricScaleReport:
         return cls(frame_errors=())
 
 
-def _ptr(a, ctype=C.c_double):
-    return a.ctypes.data_as(C.POINTER(ctype))
-
-
 def _checked(world_xyz, group_start, ent_world, ent_obj):
     world_xyz = np.ascontiguousarray(world_xyz, dtype=np.float64).reshape(-1, 3)
     group_start = np.ascontiguousarray(group_start, dtype=np.int64)
@@ -168,9 +164,9 @@ class DeviceScaleErrors:
         world_xyz, group_start, ent_world, ent_obj = _checked(world_xyz, group_start, ent_world, ent_obj)
         n_groups = len(group_start) - 1
         stats = np.zeros((n_groups, SCALE_NSTAT))
-        desc = _lib.ScaleDesc(n_world=len(world_xyz), world_xyz=_ptr(world_xyz), n_groups=n_groups, group_start=_ptr(group_start, C.c_int64),
-                              ent_world=_ptr(ent_world, C.c_int64), ent_obj=_ptr(ent_obj))
-        _lib.check(lib, lib.cba_scale_errors(C.byref(desc), self.device_id, _ptr(stats)), "cba_scale_errors")
+        desc = _lib.ScaleDesc(n_world=len(world_xyz), world_xyz=_lib.ptr(world_xyz), n_groups=n_groups, group_start=_lib.ptr(group_start),
+                              ent_world=_lib.ptr(ent_world), ent_obj=_lib.ptr(ent_obj))
+        _lib.check(lib, lib.cba_scale_errors(C.byref(desc), self.device_id, _lib.ptr(stats)), "cba_scale_errors")
         return stats
 
 

@@ -102,17 +102,6 @@ VERTICAL_SIGNATURES = {
 }
 
 
-def _load():
-    lib = _lib.load()
-    for name, (res, args) in VERTICAL_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise BackendError(f"{_lib.LIB_PATH} does not export {name} (stale build?)") from exc
-        fn.restype, fn.argtypes = res, args
-    return lib
-
-
 def check_vertical_arguments(planes, height, width, focal_x, focal_y, offset, num_steps):
     """The arrays of a ``vertical_fit`` call in the layout of ``cba_vertical_desc``: five planes of one length and one dtype
     (float32 or float64; anything else is widened to float64), and the per-fit arrays.  ``ValueError`` for mismatched lengths, a
@@ -160,14 +149,12 @@ class DeviceVerticalFit:
         fits, stop, status = np.zeros((n, 8), dtype=np.float64), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
         if n == 0:
             return fits, stop, status
-        lib = _load()
-        desc = VerticalDesc(n_fits=n, num_steps=num_steps, n_pixels=len(planes[0]), height=height.ctypes.data_as(_lib.c_int32_p),
-                            width=width.ctypes.data_as(_lib.c_int32_p), focal_x=focal_x.ctypes.data_as(_lib.c_double_p),
-                            focal_y=focal_y.ctypes.data_as(_lib.c_double_p), offset=offset.ctypes.data_as(_lib.c_int64_p),
+        lib = _lib.bind(_lib.load(), VERTICAL_SIGNATURES)
+        desc = VerticalDesc(n_fits=n, num_steps=num_steps, n_pixels=len(planes[0]), height=_lib.ptr(height), width=_lib.ptr(width),
+                            focal_x=_lib.ptr(focal_x), focal_y=_lib.ptr(focal_y), offset=_lib.ptr(offset),
                             up_x=planes[0].ctypes.data, up_y=planes[1].ctypes.data, up_conf=planes[2].ctypes.data, lat=planes[3].ctypes.data,
                             lat_conf=planes[4].ctypes.data, is_f32=int(planes[0].dtype == np.float32))
-        _lib.check(lib, lib.cba_vertical_fit(C.byref(desc), self.device_id, fits.ctypes.data_as(_lib.c_double_p), stop.ctypes.data_as(_lib.c_int32_p),
-                                             status.ctypes.data_as(_lib.c_int32_p)), "cba_vertical_fit")
+        _lib.check(lib, lib.cba_vertical_fit(C.byref(desc), self.device_id, _lib.ptr(fits), _lib.ptr(stop), _lib.ptr(status)), "cba_vertical_fit")
         return fits, stop, status
 
 

@@ -3,40 +3,32 @@ caliscope_amd.coverage_analysis that runs on it, and the tables and the brute fo
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-import tempfile
-from pathlib import Path
+import functools
 
 import numpy as np
 
 from caliscope_amd.coverage_analysis import check_coverage_arguments
 from caliscope_amd.exceptions import BackendError
+from tests.native_build import CSRC, NATIVE, load_native
 
-ROOT = Path(__file__).resolve().parent.parent
 I32 = C.POINTER(C.c_int32)
 I64 = C.POINTER(C.c_int64)
-_LIB = None
 
 
+@functools.cache
 def harness():
     """Compile (once per process) and load the harness."""
-    global _LIB
-    if _LIB is None:
-        out = Path(tempfile.mkdtemp(prefix="coverage_harness_")) / "libcoverage_harness.so"
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", f"-I{ROOT / 'caliscope_amd' / 'csrc'}",
-                        str(ROOT / "tests" / "native" / "coverage_harness.cpp"), "-o", str(out)], check=True)
-        lib = C.CDLL(str(out))
-        lib.ch_last_error.restype = C.c_char_p
-        lib.ch_constants.restype = None
-        lib.ch_constants.argtypes = [I32]
-        lib.ch_plan.restype = None
-        lib.ch_plan.argtypes = [C.c_int32, C.c_int64, C.c_int64, I64]
-        lib.ch_tile_pair.restype = None
-        lib.ch_tile_pair.argtypes = [C.c_int64, C.c_int32, I32]
-        lib.ch_coverage_counts.restype = C.c_int
-        lib.ch_coverage_counts.argtypes = [C.c_int32, C.c_int64, C.c_int64, I64, I32, C.c_int64, I64]
-        _LIB = lib
-    return _LIB
+    lib = load_native(NATIVE / "coverage_harness.cpp", include=(CSRC,))
+    lib.ch_last_error.restype = C.c_char_p
+    lib.ch_constants.restype = None
+    lib.ch_constants.argtypes = [I32]
+    lib.ch_plan.restype = None
+    lib.ch_plan.argtypes = [C.c_int32, C.c_int64, C.c_int64, I64]
+    lib.ch_tile_pair.restype = None
+    lib.ch_tile_pair.argtypes = [C.c_int64, C.c_int32, I32]
+    lib.ch_coverage_counts.restype = C.c_int
+    lib.ch_coverage_counts.argtypes = [C.c_int32, C.c_int64, C.c_int64, I64, I32, C.c_int64, I64]
+    return lib
 
 
 def constants() -> dict:

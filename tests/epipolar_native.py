@@ -3,51 +3,43 @@ caliscope_amd.epipolar_pose that runs on it — the CPU side of the epipolar-boo
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-import tempfile
-from pathlib import Path
+import functools
 
 import numpy as np
 
+from tests.native_build import CSRC, NATIVE, load_native
 from tests.pnp_native import HarnessPnP
 
-ROOT = Path(__file__).resolve().parent.parent
 D = C.POINTER(C.c_double)
 I32 = C.POINTER(C.c_int32)
 I64 = C.POINTER(C.c_int64)
 U8 = C.POINTER(C.c_uint8)
-_LIB = None
 
 
 def _p(a, t=D):
     return a.ctypes.data_as(t)
 
 
+@functools.cache
 def harness():
     """Compile (once per process) and load the harness."""
-    global _LIB
-    if _LIB is None:
-        out = Path(tempfile.mkdtemp(prefix="epipolar_harness_")) / "libepipolar_harness.so"
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", f"-I{ROOT / 'caliscope_amd' / 'csrc'}",
-                        str(ROOT / "tests" / "native" / "epipolar_harness.cpp"), "-o", str(out)], check=True)
-        lib = C.CDLL(str(out))
-        lib.eh_sample.restype = None
-        lib.eh_sample.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int, I64]
-        lib.eh_sampson.restype = C.c_double
-        lib.eh_sampson.argtypes = [D, C.c_double, C.c_double, C.c_double, C.c_double]
-        lib.eh_decompose.restype = C.c_int
-        lib.eh_decompose.argtypes = [D, C.c_int64, D, D, I64]
-        lib.eh_essential_batch.restype = None
-        lib.eh_essential_batch.argtypes = [C.c_int32, I32, D, C.c_int64, D, I32, C.c_int64, I64, I64, I64, D, C.c_int32, C.c_uint64, C.c_int32,
-                                           D, I32, I64, I64, D, I32, U8, D, D]
-        lib.eh_resect_batch.restype = None
-        lib.eh_resect_batch.argtypes = [C.c_int64, I64, D, D, D, C.c_int32, C.c_int32, C.c_uint64, D, I32, I64, I32, D]
-        lib.eh_essential_counts.restype = None
-        lib.eh_essential_counts.argtypes = [D, I64, I64, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, I64, I64]
-        lib.eh_resect_counts.restype = None
-        lib.eh_resect_counts.argtypes = [D, D, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, I64, I64]
-        _LIB = lib
-    return _LIB
+    lib = load_native(NATIVE / "epipolar_harness.cpp", include=(CSRC,))
+    lib.eh_sample.restype = None
+    lib.eh_sample.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int, I64]
+    lib.eh_sampson.restype = C.c_double
+    lib.eh_sampson.argtypes = [D, C.c_double, C.c_double, C.c_double, C.c_double]
+    lib.eh_decompose.restype = C.c_int
+    lib.eh_decompose.argtypes = [D, C.c_int64, D, D, I64]
+    lib.eh_essential_batch.restype = None
+    lib.eh_essential_batch.argtypes = [C.c_int32, I32, D, C.c_int64, D, I32, C.c_int64, I64, I64, I64, D, C.c_int32, C.c_uint64, C.c_int32,
+                                       D, I32, I64, I64, D, I32, U8, D, D]
+    lib.eh_resect_batch.restype = None
+    lib.eh_resect_batch.argtypes = [C.c_int64, I64, D, D, D, C.c_int32, C.c_int32, C.c_uint64, D, I32, I64, I32, D]
+    lib.eh_essential_counts.restype = None
+    lib.eh_essential_counts.argtypes = [D, I64, I64, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, I64, I64]
+    lib.eh_resect_counts.restype = None
+    lib.eh_resect_counts.argtypes = [D, D, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, I64, I64]
+    return lib
 
 
 def essential_counts(und, corr_a, corr_b, s, n, thr, n_hyp, seed, job, items):

@@ -3,41 +3,33 @@ caliscope_amd.frame_selector that runs on it — the CPU side of the frame-selec
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-import tempfile
-from pathlib import Path
+import functools
 
 import numpy as np
 
 from caliscope_amd.frame_selector import FrameSelection, check_selection_arguments
+from tests.native_build import CSRC, NATIVE, load_native
 
-ROOT = Path(__file__).resolve().parent.parent
 D = C.POINTER(C.c_double)
 I32 = C.POINTER(C.c_int32)
 I64 = C.POINTER(C.c_int64)
 U64 = C.POINTER(C.c_uint64)
-_LIB = None
 
 
 def _p(a, t=D):
     return None if a is None else a.ctypes.data_as(t)
 
 
+@functools.cache
 def harness():
     """Compile (once per process) and load the harness."""
-    global _LIB
-    if _LIB is None:
-        out = Path(tempfile.mkdtemp(prefix="frame_select_harness_")) / "libframe_select_harness.so"
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", f"-I{ROOT / 'caliscope_amd' / 'csrc'}",
-                        str(ROOT / "tests" / "native" / "frame_select_harness.cpp"), "-o", str(out)], check=True)
-        lib = C.CDLL(str(out))
-        lib.fh_homography.restype = C.c_int
-        lib.fh_homography.argtypes = [D, D, C.c_int, C.c_int, D, D, D]
-        lib.fh_select_frames.restype = None
-        lib.fh_select_frames.argtypes = [C.c_int32, I64, D, C.c_int64, I64, I64, I32, D, D, C.c_int, C.c_int, C.c_int, C.c_int, U64, D, D, I32, D,
-                                         I32, I32, I32, I32, I32]
-        _LIB = lib
-    return _LIB
+    lib = load_native(NATIVE / "frame_select_harness.cpp", include=(CSRC,))
+    lib.fh_homography.restype = C.c_int
+    lib.fh_homography.argtypes = [D, D, C.c_int, C.c_int, D, D, D]
+    lib.fh_select_frames.restype = None
+    lib.fh_select_frames.argtypes = [C.c_int32, I64, D, C.c_int64, I64, I64, I32, D, D, C.c_int, C.c_int, C.c_int, C.c_int, U64, D, D, I32, D,
+                                     I32, I32, I32, I32, I32]
+    return lib
 
 
 def homography(obj_xy, img_xy, float32_io=True):

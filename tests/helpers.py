@@ -63,3 +63,21 @@ def small_problem(n_cams=6, n_points=300, k=6, refine=False, loss="linear", outl
     par = BundleParameterization.from_camera_array(sc.cameras_init, n_points=n_points, refine_intrinsics=refine)
     x0 = par.pack(sc.cameras_init, sc.points_init)
     return sc, par, x0
+
+
+def null_outputs(monkeypatch, table, name, drop=(), fields=()):
+    """Until the test ends, calls of the library function ``name`` (typed by the signature table ``table``) hand the library a null
+    pointer for some optional outputs: the output arguments at the positions ``drop`` (counted after the descriptor and the device),
+    and the members ``fields`` of an output structure passed by reference as the last argument.  The wrappers of caliscope_amd always
+    ask for every output; this reaches the other side of the library's ``if (out)`` branches through them."""
+    from caliscope_amd import _lib
+
+    lib = _lib.bind(_lib.load(), table)
+    real = getattr(lib, name)
+
+    def call(desc, device, *outs):
+        for field in fields:
+            setattr(outs[-1]._obj, field, None)
+        return real(desc, device, *(None if i in drop else o for i, o in enumerate(outs)))
+
+    monkeypatch.setattr(lib, name, call)  # (stays in place: _lib.bind types a table once, so later calls do not look the name up anew)

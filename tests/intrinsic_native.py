@@ -3,40 +3,33 @@ caliscope_amd.calibrate_intrinsics that runs on it — the CPU side of the intri
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-import tempfile
-from pathlib import Path
+import functools
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
+from tests.native_build import CSRC, NATIVE, load_native
+
 D = C.POINTER(C.c_double)
 I32 = C.POINTER(C.c_int32)
 I64 = C.POINTER(C.c_int64)
-_LIB = None
 
 
 def _p(a, t=D):
     return None if a is None else a.ctypes.data_as(t)
 
 
+@functools.cache
 def harness():
     """Compile (once per process) and load the harness."""
-    global _LIB
-    if _LIB is None:
-        out = Path(tempfile.mkdtemp(prefix="intrinsic_harness_")) / "libintrinsic_harness.so"
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", f"-I{ROOT / 'caliscope_amd' / 'csrc'}",
-                        str(ROOT / "tests" / "native" / "intrinsic_harness.cpp"), "-o", str(out)], check=True)
-        lib = C.CDLL(str(out))
-        lib.ih_work_stride.restype = C.c_int
-        lib.ih_start.restype = None
-        lib.ih_start.argtypes = [C.c_int, C.c_double, C.c_double, D]
-        lib.ih_point.restype = C.c_int
-        lib.ih_point.argtypes = [C.c_int, D, D, D, D, D, D, D]
-        lib.ih_intrinsics_batch.restype = None
-        lib.ih_intrinsics_batch.argtypes = [C.c_int32, I32, D, D, C.c_int64, I64, I32, D, D, C.c_int, C.c_int, D, D, I32, I32, D, D, I32]
-        _LIB = lib
-    return _LIB
+    lib = load_native(NATIVE / "intrinsic_harness.cpp", include=(CSRC,))
+    lib.ih_work_stride.restype = C.c_int
+    lib.ih_start.restype = None
+    lib.ih_start.argtypes = [C.c_int, C.c_double, C.c_double, D]
+    lib.ih_point.restype = C.c_int
+    lib.ih_point.argtypes = [C.c_int, D, D, D, D, D, D, D]
+    lib.ih_intrinsics_batch.restype = None
+    lib.ih_intrinsics_batch.argtypes = [C.c_int32, I32, D, D, C.c_int64, I64, I32, D, D, C.c_int, C.c_int, D, D, I32, I32, D, D, I32]
+    return lib
 
 
 def start_intrinsics(model, width, height):

@@ -3,39 +3,32 @@ that runs on it — the CPU side of the pose-bootstrap tests."""
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-import tempfile
-from pathlib import Path
+import functools
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
+from tests.native_build import CSRC, NATIVE, load_native
+
 D = C.POINTER(C.c_double)
 I32 = C.POINTER(C.c_int32)
 I64 = C.POINTER(C.c_int64)
-_LIB = None
 
 
 def _p(a, t=D):
     return a.ctypes.data_as(t)
 
 
+@functools.cache
 def harness():
     """Compile (once per process) and load the harness."""
-    global _LIB
-    if _LIB is None:
-        out = Path(tempfile.mkdtemp(prefix="pnp_harness_")) / "libpnp_harness.so"
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", f"-I{ROOT / 'caliscope_amd' / 'csrc'}",
-                        str(ROOT / "tests" / "native" / "pnp_harness.cpp"), "-o", str(out)], check=True)
-        lib = C.CDLL(str(out))
-        lib.ph_pnp_view.restype = C.c_int
-        lib.ph_pnp_view.argtypes = [D, D, C.c_int, C.c_int, C.c_int, D, D, D]
-        lib.ph_pnp_batch.restype = None
-        lib.ph_pnp_batch.argtypes = [C.c_int64, I64, I32, I32, D, D, D, C.c_int, C.c_int, D, D, D, I32]
-        lib.ph_pair_rmse.restype = None
-        lib.ph_pair_rmse.argtypes = [C.c_int64, D, I64, D, D, D, I64]
-        _LIB = lib
-    return _LIB
+    lib = load_native(NATIVE / "pnp_harness.cpp", include=(CSRC,))
+    lib.ph_pnp_view.restype = C.c_int
+    lib.ph_pnp_view.argtypes = [D, D, C.c_int, C.c_int, C.c_int, D, D, D]
+    lib.ph_pnp_batch.restype = None
+    lib.ph_pnp_batch.argtypes = [C.c_int64, I64, I32, I32, D, D, D, C.c_int, C.c_int, D, D, D, I32]
+    lib.ph_pair_rmse.restype = None
+    lib.ph_pair_rmse.argtypes = [C.c_int64, D, I64, D, D, D, I64]
+    return lib
 
 
 def pnp_view(obj, uv, min_points=4, f32=False):

@@ -4,44 +4,37 @@ tests share."""
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-import tempfile
+import functools
 from pathlib import Path
 
 import numpy as np
 
 from caliscope_amd.reprojection_stats import ReportDesc, ReportOut, check_reprojection_arguments, run_reprojection_call
+from tests.native_build import CSRC, NATIVE, load_native
 
-ROOT = Path(__file__).resolve().parent.parent
 I32 = C.POINTER(C.c_int32)
 I64 = C.POINTER(C.c_int64)
 F64 = C.POINTER(C.c_double)
-_LIB = None
 
 
+@functools.cache
 def harness():
     """Compile (once per process) and load the harness."""
-    global _LIB
-    if _LIB is None:
-        out = Path(tempfile.mkdtemp(prefix="report_harness_")) / "libreport_harness.so"
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", f"-I{ROOT / 'caliscope_amd' / 'csrc'}",
-                        str(ROOT / "tests" / "native" / "report_harness.cpp"), "-o", str(out)], check=True)
-        lib = C.CDLL(str(out))
-        lib.rh_last_error.restype = C.c_char_p
-        lib.rh_constants.restype = None
-        lib.rh_constants.argtypes = [I32]
-        lib.rh_interpolate.restype = C.c_double
-        lib.rh_interpolate.argtypes = [C.c_double, C.c_double, C.c_double]
-        lib.rh_rank_plan.restype = None
-        lib.rh_rank_plan.argtypes = [C.c_int64, C.c_double, I64, F64]
-        lib.rh_select.restype = C.c_double
-        lib.rh_select.argtypes = [F64, C.c_int64, C.c_int64]
-        lib.rh_percentile.restype = C.c_double
-        lib.rh_percentile.argtypes = [F64, C.c_int64, C.c_double]
-        lib.rh_reprojection_filter.restype = C.c_int
-        lib.rh_reprojection_filter.argtypes = [C.POINTER(ReportDesc), C.POINTER(ReportOut)]
-        _LIB = lib
-    return _LIB
+    lib = load_native(NATIVE / "report_harness.cpp", flags=("-Wno-unknown-pragmas",), include=(CSRC,))
+    lib.rh_last_error.restype = C.c_char_p
+    lib.rh_constants.restype = None
+    lib.rh_constants.argtypes = [I32]
+    lib.rh_interpolate.restype = C.c_double
+    lib.rh_interpolate.argtypes = [C.c_double, C.c_double, C.c_double]
+    lib.rh_rank_plan.restype = None
+    lib.rh_rank_plan.argtypes = [C.c_int64, C.c_double, I64, F64]
+    lib.rh_select.restype = C.c_double
+    lib.rh_select.argtypes = [F64, C.c_int64, C.c_int64]
+    lib.rh_percentile.restype = C.c_double
+    lib.rh_percentile.argtypes = [F64, C.c_int64, C.c_double]
+    lib.rh_reprojection_filter.restype = C.c_int
+    lib.rh_reprojection_filter.argtypes = [C.POINTER(ReportDesc), C.POINTER(ReportOut)]
+    return lib
 
 
 def constants() -> dict:

@@ -3,37 +3,30 @@
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-import tempfile
-from pathlib import Path
+import functools
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
+from tests.native_build import CSRC, NATIVE, load_native
+
 D = C.POINTER(C.c_double)
 I32 = C.POINTER(C.c_int32)
 I64 = C.POINTER(C.c_int64)
-_LIB = None
 
 
+@functools.cache
 def harness():
     """Compile (once per process) and load the harness.  -ffp-contract=off: the per-pair arithmetic is written without fused
     multiply-adds, as the device build keeps it."""
-    global _LIB
-    if _LIB is None:
-        out = Path(tempfile.mkdtemp(prefix="scale_harness_")) / "libscale_harness.so"
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", f"-I{ROOT / 'caliscope_amd' / 'csrc'}",
-                        str(ROOT / "tests" / "native" / "scale_harness.cpp"), "-o", str(out)], check=True)
-        lib = C.CDLL(str(out))
-        lib.sh_last_error.restype = C.c_char_p
-        lib.sh_constants.restype = None
-        lib.sh_constants.argtypes = [I32]
-        lib.sh_lane_pairs.restype = C.c_int64
-        lib.sh_lane_pairs.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, I32, I32]
-        lib.sh_scale_errors.restype = C.c_int
-        lib.sh_scale_errors.argtypes = [C.c_int64, D, C.c_int64, I64, I64, D, D, I32]
-        _LIB = lib
-    return _LIB
+    lib = load_native(NATIVE / "scale_harness.cpp", flags=("-ffp-contract=off",), include=(CSRC,))
+    lib.sh_last_error.restype = C.c_char_p
+    lib.sh_constants.restype = None
+    lib.sh_constants.argtypes = [I32]
+    lib.sh_lane_pairs.restype = C.c_int64
+    lib.sh_lane_pairs.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, I32, I32]
+    lib.sh_scale_errors.restype = C.c_int
+    lib.sh_scale_errors.argtypes = [C.c_int64, D, C.c_int64, I64, I64, D, D, I32]
+    return lib
 
 
 def constants() -> dict:

@@ -298,7 +298,7 @@ def test_library_checks_its_input_and_has_no_cpu_fallback():
         HARNESS.scale_errors(world, [0, 2, 2 + n], np.zeros(2 + n, dtype=np.int64), np.zeros((2 + n, 3)))
 
 
-def test_host_half_in_a_build_without_device_code(tmp_path):
+def test_host_half_in_a_build_without_device_code():
     """The entry point (input checks and binning, plain C++ in csrc/cba_solve.cpp) is part of every build of the C ABI; the CPU test
     build of tests/test_cpu_abi.py has no device code, so there a bad call is refused with the same messages and a valid one is
     CBA_ERR_UNSUPPORTED, never a number.  (Its own interpreter: this process has loaded the real library.)"""
@@ -307,10 +307,9 @@ def test_host_half_in_a_build_without_device_code(tmp_path):
     import sys
     import textwrap
 
-    root = Path(__file__).resolve().parent.parent
-    out = tmp_path / "libcaliscope_ba_cpu.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", "-I", str(root / "include"), str(root / "tests" / "native" / "cpu_library.cpp"),
-                    str(root / "caliscope_amd" / "csrc" / "cba_solve.cpp"), "-o", str(out)], check=True)
+    from tests.native_build import CSRC, INCLUDE, NATIVE, ROOT as root, compile_native
+
+    out = compile_native(NATIVE / "cpu_library.cpp", CSRC / "cba_solve.cpp", flags=("-pthread",), include=(INCLUDE,))
     body = """
         import json
         import numpy as np

@@ -10,20 +10,15 @@ import re
 import subprocess
 import sys
 import textwrap
-from pathlib import Path
 
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
+from tests.native_build import CSRC, INCLUDE, NATIVE, ROOT, compile_native
 
 
 @pytest.fixture(scope="module")
-def cpu_lib(tmp_path_factory):
-    out = tmp_path_factory.mktemp("cpuabi") / "libcaliscope_ba_cpu.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", "-I", str(ROOT / "include"),
-                    str(ROOT / "tests" / "native" / "cpu_library.cpp"), str(ROOT / "caliscope_amd" / "csrc" / "cba_solve.cpp"),
-                    "-o", str(out)], check=True)
-    return out
+def cpu_lib():
+    return compile_native(NATIVE / "cpu_library.cpp", CSRC / "cba_solve.cpp", flags=("-pthread",), include=(INCLUDE,))
 
 
 def _run(cpu_lib, body: str, timeout=240):

@@ -152,3 +152,23 @@ def test_fisheye_camera_without_intrinsics_goes_through():
     fish = vol.camera_array.cameras[2]
     assert fish.fisheye and len(np.asarray(fish.distortions).ravel()) == 4
     assert abs(fish.matrix[0, 0] - 700.0) <= 0.01 * 700.0, fish.matrix
+
+
+def test_device_without_the_iteration_counts(monkeypatch):
+    """iters_out is optional in the C ABI (the wrapper always asks for it): a call without it returns every other output bit for bit,
+    and those stand against the g++ build as in test_device_matches_cpu_build.  Two cameras of eight views."""
+    from caliscope_amd.calibrate_intrinsics import INTRINSICS_SIGNATURES
+    from tests.helpers import null_outputs
+
+    model, size, vstart, vcam, xy, obj = S.pack([S.camera_scene(31, n_views=8, noise=0.3), S.camera_scene(32, n_views=8, fisheye=True, noise=0.3)])
+    full = DeviceIntrinsics().intrinsics_batch(model, size, None, vstart, vcam, xy, obj, True, 0)
+    cpu = HarnessIntrinsics().intrinsics_batch(model, size, None, vstart, vcam, xy, obj, True, 0)
+    null_outputs(monkeypatch, INTRINSICS_SIGNATURES, "cba_pose_intrinsics_batch", drop={3})
+    got = DeviceIntrinsics().intrinsics_batch(model, size, None, vstart, vcam, xy, obj, True, 0)
+    assert not got[3].any() and full[3].all()  # nothing was copied back
+    for k in (0, 1, 2, 4, 5, 6):
+        assert np.array_equal(got[k], full[k]), k
+    assert np.array_equal(got[2], cpu[2]) and np.array_equal(got[6], cpu[6]) and (got[2] == 0).all()
+    well = (cpu[6] == 0) & (np.diff(vstart) >= 8)
+    for k, rows in ((0, slice(None)), (1, slice(None)), (4, well), (5, well)):
+        assert (np.abs(got[k][rows] - cpu[k][rows]) <= BASE_ATOL * DEVICE_FACTOR * np.maximum(1.0, np.abs(cpu[k][rows]))).all(), k

@@ -19,14 +19,47 @@ def lib():
     return _lib.load()
 
 
+def _declared(header: str) -> set:
+    """The cba_* functions a header of include/ declares (comments aside)."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", (ROOT / "include" / header).read_text(), flags=re.S)
+    return set(re.findall(r"\b(cba_[a-z_0-9]+)\s*\(", text)) - {"cba_problem"}
+
+
 def test_header_symbols_are_exported_and_bound(lib):
-    header = (ROOT / "include" / "caliscope_ba.h").read_text()
-    declared = set(re.findall(r"\b(cba_[a-z_0-9]+)\s*\(", header))
-    declared -= {"cba_problem"}
-    assert declared, "no declarations parsed"
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in the header but not exported"
-    assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    """Every header of include/ against the built library and the signature tables: what a header declares is exported, and bound by
+    exactly one table (caliscope_ba.h by _lib.SIGNATURES, the others by the tables of the modules that call them); no table binds a
+    name that no header declares.  The cba_last_error / cba_set_error a small header declares again are caliscope_ba.h's."""
+    from caliscope_amd import (calibrate_intrinsics, coverage_analysis, epipolar_pose, frame_selector, pose_network, reconstruction,
+                               reprojection_stats, vertical)
+
+    tables = {
+        "caliscope_ba.h": [_lib.SIGNATURES],
+        "caliscope_pose.h": [pose_network.POSE_SIGNATURES, epipolar_pose.EPI_SIGNATURES, calibrate_intrinsics.INTRINSICS_SIGNATURES,
+                             frame_selector.FRAME_SELECT_SIGNATURES],
+        "caliscope_coverage.h": [coverage_analysis.COVERAGE_SIGNATURES],
+        "caliscope_vertical.h": [vertical.VERTICAL_SIGNATURES],
+        "caliscope_report.h": [reprojection_stats.REPORT_SIGNATURES],
+        "caliscope_trajectory.h": [reconstruction.TRAJECTORY_SIGNATURES],
+    }
+    assert set(tables) == {p.name for p in (ROOT / "include").glob("*.h")}
+    base = _declared("caliscope_ba.h")
+    assert {"cba_last_error", "cba_set_error"} <= base
+    bound_so_far = set()
+    for header, sigs in tables.items():
+        declared = _declared(header)
+        if header != "caliscope_ba.h":
+            declared -= {"cba_last_error", "cba_set_error"}
+        assert declared, f"no declarations parsed in {header}"
+        for name in declared:
+            assert hasattr(lib, name), f"{name} declared in {header} but not exported"
+        bound = [name for table in sigs for name in table]
+        assert sorted(bound) == sorted(declared), (header, set(bound) ^ declared)  # each exactly once, and nothing undeclared
+        assert not bound_so_far & declared, (header, bound_so_far & declared)
+        bound_so_far |= declared
+        for table in sigs:  # the tables type the functions they name
+            typed = _lib.bind(lib, table)
+            assert all(getattr(typed, name).argtypes == args and getattr(typed, name).restype == res for name, (res, args) in table.items())
+    assert len(_declared("caliscope_pose.h")) == 6
     assert lib.cba_version() == 100
     assert lib.cba_timer_count() == 13 and lib.cba_timer_name(2) == b"build" and lib.cba_timer_name(12) == b"exchange"
 

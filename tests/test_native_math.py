@@ -1,8 +1,6 @@
 """The per-observation arithmetic the HIP kernels inline (caliscope_amd/csrc/ba_math.h), compiled for the
 host by g++ and compared with the numpy oracle — runs without a GPU."""
 import ctypes
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -12,9 +10,9 @@ from caliscope_amd.bundle_parameterization import BundleParameterization
 from oracle import camera_model as cm
 from oracle.residuals import joint_jacobian, joint_residuals
 from tests.helpers import small_problem
+from tests.native_build import CSRC, NATIVE, load_native
 from tests.test_oracle_pins import _mixed_arrays
 
-ROOT = Path(__file__).resolve().parent.parent
 D = ctypes.POINTER(ctypes.c_double)
 
 
@@ -23,12 +21,8 @@ def _p(a):
 
 
 @pytest.fixture(scope="module")
-def mh(tmp_path_factory):
-    out = tmp_path_factory.mktemp("mh") / "libmath_harness.so"
-    subprocess.run(
-        ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", f"-I{ROOT / 'caliscope_amd' / 'csrc'}",
-         str(ROOT / "tests" / "native" / "math_harness.cpp"), "-o", str(out)], check=True)
-    lib = ctypes.CDLL(str(out))
+def mh():
+    lib = load_native(NATIVE / "math_harness.cpp", include=(CSRC,))
     lib.mh_chol3_solve.restype = ctypes.c_int
     lib.mh_robust.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double, D]
     return lib

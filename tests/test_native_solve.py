@@ -2,8 +2,6 @@
 device primitives (tests/native/dense_engine.cpp) and compared, evaluation by evaluation, with the Python driver
 (oracle/trf_driver.py) on the numpy engine and, at convergence, with scipy."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -14,17 +12,14 @@ from oracle.engine import OracleEngine
 from oracle.residuals import joint_jacobian, joint_residuals
 from oracle.solver import optimize_scipy
 from tests.helpers import aligned_difference, small_problem
+from tests.native_build import CSRC, NATIVE, load_native
 
-ROOT = Path(__file__).resolve().parent.parent
 FUN = C.CFUNCTYPE(None, _lib.c_double_p, _lib.c_double_p)
 
 
 @pytest.fixture(scope="module")
-def native(tmp_path_factory):
-    out = tmp_path_factory.mktemp("ns") / "libnative_solve.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", str(ROOT / "caliscope_amd" / "csrc" / "cba_solve.cpp"),
-                    str(ROOT / "tests" / "native" / "dense_engine.cpp"), "-o", str(out)], check=True)
-    lib = C.CDLL(str(out))
+def native():
+    lib = load_native(CSRC / "cba_solve.cpp", NATIVE / "dense_engine.cpp")
     lib.de_create.restype = C.c_void_p
     lib.de_create.argtypes = [C.c_int, C.c_int, C.c_int, FUN, FUN]
     lib.de_destroy.argtypes = [C.c_void_p]

@@ -292,3 +292,21 @@ def test_non_finite_projection_falls_back_to_the_host_filter(caplog):
     else:
         pd.testing.assert_frame_equal(outcome[0], outcome[1])
     assert "not finite" in caplog.text
+
+
+def test_a_filter_call_that_does_not_ask_for_the_mask(monkeypatch):
+    """keep of cba_report_out is optional (the wrapper always asks for it in a filter call): without it the thresholds, the kept counts
+    and the floor count come back as in a full call, which stand against the harness bit for bit as in _check_filter.  Two cameras,
+    forty rows, one of them under the floor."""
+    from caliscope_amd.reprojection_stats import REPORT_SIGNATURES
+    from tests.helpers import null_outputs
+
+    rng = np.random.default_rng(12)
+    err, cam = rng.gamma(2.0, 0.5, 40), np.r_[np.zeros(28, np.int32), np.ones(12, np.int32)]
+    full = _check_filter(err, cam, 2, "percentile", 60.0, floor=10)
+    assert full.n_floor_cams == 1 and full.keep.any()
+    null_outputs(monkeypatch, REPORT_SIGNATURES, "cba_reprojection_filter", fields=("keep",))
+    got = N.filter_with_given_errors(DeviceReprojectionStats(), err, cam, 2, "percentile", 60.0, "per_camera", 10)
+    assert not got.keep.any()  # nothing was copied back
+    assert np.array_equal(_bits(got.cam_threshold), _bits(full.cam_threshold)) and np.array_equal(got.cam_kept, full.cam_kept)
+    assert got.n_floor_cams == full.n_floor_cams and np.array_equal(_bits(got.err), _bits(full.err))

@@ -3,22 +3,18 @@
 must receive exactly the pairs of ``sum_p W_p V'^-1 W_p^T`` (the reference forms the same sums
 implicitly in ``J^T J``, core/reprojection.py:128-234), and the plan must keep the lanes busy."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
+from tests.native_build import NATIVE, load_native
+
 I32P, F64P, I64P = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_long)
 
 
 @pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    out = tmp_path_factory.mktemp("plan") / "libplan_harness.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", str(ROOT / "tests" / "native" / "plan_harness.cpp"), "-o", str(out)],
-                   check=True)
-    lib = C.CDLL(str(out))
+def harness():
+    lib = load_native(NATIVE / "plan_harness.cpp", flags=("-pthread",))
     lib.plan_replay.restype = C.c_int
     lib.plan_replay.argtypes = [C.c_int] * 17 + [I32P, I32P, F64P, F64P, I64P]
     lib.bind_replay.restype = C.c_int

@@ -8,14 +8,14 @@ import re
 import subprocess
 import sys
 import textwrap
-from pathlib import Path
 
 import numpy as np
 import pytest
 from scipy.sparse import coo_matrix
 from scipy.sparse.csgraph import connected_components
 
-ROOT = Path(__file__).resolve().parent.parent
+from tests.native_build import CSRC, INCLUDE, NATIVE, ROOT, compile_native, load_native
+
 I32P, I64P, F64P = C.POINTER(C.c_int32), C.POINTER(C.c_long), C.POINTER(C.c_double)
 U8P, U16P = C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)
 ERR_INVALID, ERR_UNSUPPORTED = -1, -4
@@ -35,10 +35,8 @@ def _p(a, t):
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    out = tmp_path_factory.mktemp("setup") / "libsetup_harness.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", str(ROOT / "tests" / "native" / "setup_harness.cpp"), "-o", str(out)], check=True)
-    lib = C.CDLL(str(out))
+def lib():
+    lib = load_native(NATIVE / "setup_harness.cpp", flags=("-pthread",))
     lib.sp_last_error.restype = C.c_char_p
     lib.sp_point_tables.restype = C.c_int
     lib.sp_point_tables.argtypes = [C.c_int, C.c_long, I32P, I32P, C.c_int, C.c_int, C.c_int] + [I32P] * 7 + [I64P]
@@ -366,11 +364,8 @@ def test_mailbox_layout(lib, ncp):
 
 # ---- problem description, through the CPU build of the ABI ---------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def cpu_lib(tmp_path_factory):
-    out = tmp_path_factory.mktemp("cpuabi_setup") / "libcaliscope_ba_cpu.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", "-I", str(ROOT / "include"), str(ROOT / "tests" / "native" / "cpu_library.cpp"),
-                    str(ROOT / "caliscope_amd" / "csrc" / "cba_solve.cpp"), "-o", str(out)], check=True)
-    return out
+def cpu_lib():
+    return compile_native(NATIVE / "cpu_library.cpp", CSRC / "cba_solve.cpp", flags=("-pthread",), include=(INCLUDE,))
 
 
 def test_every_rejection_of_a_problem_description(cpu_lib):

@@ -1,22 +1,19 @@
 """trf::termination (csrc/trf_math.h): scipy's check_termination as the native driver and the device both run it — the four outcomes and the
 two boundaries of its strict comparisons, against scipy's own function."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 from scipy.optimize._lsq.common import check_termination
 
-ROOT = Path(__file__).resolve().parent.parent
+from tests.native_build import NATIVE, load_native
+
 NONE = -100
 
 
 @pytest.fixture(scope="module")
-def th(tmp_path_factory):
-    out = tmp_path_factory.mktemp("th") / "libtermination.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", str(ROOT / "tests" / "native" / "termination_harness.cpp"), "-o", str(out)], check=True)
-    lib = C.CDLL(str(out))
+def th():
+    lib = load_native(NATIVE / "termination_harness.cpp")
     lib.th_termination.restype = C.c_int
     lib.th_termination.argtypes = [C.c_double] * 7
     lib.th_reduction_ratio.restype = C.c_double

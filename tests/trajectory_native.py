@@ -3,42 +3,34 @@ caliscope_amd.reconstruction that runs on it, and the recording and the comparis
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-import tempfile
-from pathlib import Path
+import functools
 
 import numpy as np
 import pandas as pd
 
 from caliscope_amd.reconstruction import TrajDesc, TrajOut, run_trajectory_call
+from tests.native_build import CSRC, NATIVE, load_native
 
-ROOT = Path(__file__).resolve().parent.parent
 I64 = C.POINTER(C.c_int64)
 F64 = C.POINTER(C.c_double)
 U8 = C.POINTER(C.c_uint8)
 WORLD_COLS = ["sync_index", "object_id", "keypoint_id", "x_coord", "y_coord", "z_coord", "frame_time"]
-_LIB = None
 
 
+@functools.cache
 def harness():
     """Compile (once per process) and load the harness."""
-    global _LIB
-    if _LIB is None:
-        out = Path(tempfile.mkdtemp(prefix="trajectory_harness_")) / "libtrajectory_harness.so"
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", f"-I{ROOT / 'caliscope_amd' / 'csrc'}",
-                        str(ROOT / "tests" / "native" / "trajectory_harness.cpp"), "-o", str(out)], check=True)
-        lib = C.CDLL(str(out))
-        lib.th_last_error.restype = C.c_char_p
-        lib.th_lerp.restype = C.c_double
-        lib.th_lerp.argtypes = [C.c_double, C.c_double, C.c_int64, C.c_int64]
-        lib.th_filtfilt.restype = C.c_int
-        lib.th_filtfilt.argtypes = [F64, C.c_int64, C.c_int, F64, F64, F64, F64]
-        lib.th_world_stages.restype = None
-        lib.th_world_stages.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, F64, F64, F64, U8, F64, F64]
-        lib.th_reconstruct_trajectories.restype = C.c_int
-        lib.th_reconstruct_trajectories.argtypes = [C.POINTER(TrajDesc), C.POINTER(TrajOut)]
-        _LIB = lib
-    return _LIB
+    lib = load_native(NATIVE / "trajectory_harness.cpp", flags=("-Wno-unknown-pragmas",), include=(CSRC,))
+    lib.th_last_error.restype = C.c_char_p
+    lib.th_lerp.restype = C.c_double
+    lib.th_lerp.argtypes = [C.c_double, C.c_double, C.c_int64, C.c_int64]
+    lib.th_filtfilt.restype = C.c_int
+    lib.th_filtfilt.argtypes = [F64, C.c_int64, C.c_int, F64, F64, F64, F64]
+    lib.th_world_stages.restype = None
+    lib.th_world_stages.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, F64, F64, F64, U8, F64, F64]
+    lib.th_reconstruct_trajectories.restype = C.c_int
+    lib.th_reconstruct_trajectories.argtypes = [C.POINTER(TrajDesc), C.POINTER(TrajOut)]
+    return lib
 
 
 def _f64(a):

@@ -3,48 +3,40 @@ that runs on it, and the fixtures, tolerances and synthetic fields the vertical 
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-import tempfile
-from pathlib import Path
+import functools
 
 import numpy as np
 
 from caliscope_amd import vertical as V
 from caliscope_amd.exceptions import BackendError
+from tests.native_build import CSRC, NATIVE, ROOT, load_native
 
-ROOT = Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / "tests" / "golden" / "vertical"
 I32 = C.POINTER(C.c_int32)
 I64 = C.POINTER(C.c_int64)
 F64 = C.POINTER(C.c_double)
-_LIB = None
 
 # Tolerances against the reference's recorded answers: angles absolute, uncertainties and costs relative, stop_step equal.
 ANGLE_ATOL = 1e-12
 REL_TOL = 1e-10
 
 
+@functools.cache
 def harness():
     """Compile (once per process) and load the harness."""
-    global _LIB
-    if _LIB is None:
-        out = Path(tempfile.mkdtemp(prefix="vertical_harness_")) / "libvertical_harness.so"
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", f"-I{ROOT / 'caliscope_amd' / 'csrc'}",
-                        str(ROOT / "tests" / "native" / "vertical_harness.cpp"), "-o", str(out)], check=True)
-        lib = C.CDLL(str(out))
-        lib.vh_last_error.restype = C.c_char_p
-        lib.vh_constants.restype = None
-        lib.vh_constants.argtypes = [I32]
-        lib.vh_n_chunks.restype = C.c_int64
-        lib.vh_n_chunks.argtypes = [C.c_int64]
-        lib.vh_gravity_vec.restype = None
-        lib.vh_gravity_vec.argtypes = [C.c_double, C.c_double, F64]
-        lib.vh_roll_pitch.restype = None
-        lib.vh_roll_pitch.argtypes = [F64, F64]
-        lib.vh_vertical_fit.restype = C.c_int
-        lib.vh_vertical_fit.argtypes = [C.c_int32, C.c_int32, C.c_int64, I32, I32, F64, F64, I64] + [C.c_void_p] * 5 + [C.c_int32, F64, I32, I32]
-        _LIB = lib
-    return _LIB
+    lib = load_native(NATIVE / "vertical_harness.cpp", include=(CSRC,))
+    lib.vh_last_error.restype = C.c_char_p
+    lib.vh_constants.restype = None
+    lib.vh_constants.argtypes = [I32]
+    lib.vh_n_chunks.restype = C.c_int64
+    lib.vh_n_chunks.argtypes = [C.c_int64]
+    lib.vh_gravity_vec.restype = None
+    lib.vh_gravity_vec.argtypes = [C.c_double, C.c_double, F64]
+    lib.vh_roll_pitch.restype = None
+    lib.vh_roll_pitch.argtypes = [F64, F64]
+    lib.vh_vertical_fit.restype = C.c_int
+    lib.vh_vertical_fit.argtypes = [C.c_int32, C.c_int32, C.c_int64, I32, I32, F64, F64, I64] + [C.c_void_p] * 5 + [C.c_int32, F64, I32, I32]
+    return lib
 
 
 def constants() -> dict:
