@@ -326,14 +326,21 @@ CBA_HD void chol3_bwd(const double* L, const double* y, double* x) {
   x[0] = (y[0] - L[1] * x[1] - L[3] * x[2]) * L[0];
 }
 
-// tan(x) for |x| <= pi/2 from + - * / alone, without contraction: the same bits from hipcc and from g++ (the maths libraries'
+// tan(x) from + - * / alone, without contraction: the same bits from hipcc and from g++ (the maths libraries'
 // tan differ in the last bit, which the pose refinements downstream of undistort_one amplify to 1e-8).  sin and cos of x / 2 by
 // their Taylor series in Horner form (12 terms each: the first one left out is below 1e-19 at pi/4), then tan x = 2 s c / (c^2 - s^2);
 // a few ulp.  At pi/2 itself the denominator is held at 1e-16 (libm's tan gives 1.6e16 there).
+// Beyond pi/2 the nearest multiple of pi is taken off first, pi in two parts whose first has 33 bits (the product is exact up to 2^20
+// periods): undistort_one's Newton iteration leaves [0, pi/2] when theta_d has no root there (coefficients outside the model), and the
+// series alone would run into the held denominator and return 1e15.  rint is exact; |x| <= pi/2 does not take the branch.
 CBA_HD double tan_portable(double x) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
+  if (fabs(x) > 1.5707963267948966) {
+    const double k = rint(x / 3.141592653589793);
+    x = (x - k * 3.14159265346825122834) - k * 1.21542010130123844986e-10;
+  }
   const double a = 0.5 * x, q = a * a;
   double s = 1.0, c = 1.0;
 #pragma unroll

@@ -525,6 +525,7 @@ int cba_triangulate(const cba_triangulate_desc* d, int32_t device, double* xyz_o
     return fail(CBA_ERR_INVALID, "cba_triangulate: bad descriptor");
   if (d->cam_intr && !d->cam_model) return fail(CBA_ERR_INVALID, "cba_triangulate: cam_intr given without cam_model");
   if (d->n_points == 0) return CBA_OK;
+  if (const int rc = triangulate_starts_ok(fail, d->n_points, d->pt_start)) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(CBA_ERR_NO_DEVICE, "cba_triangulate: no HIP device");
   if (device < 0 || device >= ndev) return fail(CBA_ERR_INVALID, "cba_triangulate: device %d of %d", device, ndev);

@@ -7,6 +7,7 @@
 //   cs_plan                                 camera-sorted super-chunks of k_build_cs
 //   constraint_plan / constraint_orphans    rows of cba_set_constraints grouped by connected component
 //   MailLayout                              the mapped host mailbox
+//   triangulate_starts_ok                   the point table of a cba_triangulate_desc
 // Shared by the device library (cba_lib.hip), the CPU test build of the C ABI (tests/native/cpu_library.cpp) and the CPU harness of the set-up
 // (tests/native/setup_harness.cpp, tests/test_setup_plan.py).  The kernel constants a function depends on (CHUNK, HEAVY_OBS, ...) are its arguments;
 // `fail(code, fmt, ...)` is the including file's error reporter; include/caliscope_ba.h comes before this file.
@@ -417,3 +418,16 @@ struct MailLayout {
   size_t cam, flags, bcam, total;
   explicit MailLayout(int ncp) : cam(kScalars), flags(cam + (size_t)3 * ncp + 8), bcam(flags + 2), total(bcam + (size_t)4 * ncp) {}
 };
+
+// ---- cba_triangulate -----------------------------------------------------------------------------------------------------------------
+// k_triangulate reads obs_cam and obs_xy at [pt_start[q], pt_start[q + 1]) and the call sizes its copies by pt_start[n_points]: the table starts at 0
+// and never decreases (so that every entry lies in [0, pt_start[n_points]]).  n_points > 0.
+template <typename Fail>
+static int triangulate_starts_ok(Fail fail, int64_t n_points, const int64_t* pt_start) {
+  if (pt_start[0] != 0) return fail(CBA_ERR_INVALID, "cba_triangulate: pt_start[0] is %lld, not 0", (long long)pt_start[0]);
+  for (int64_t q = 0; q < n_points; ++q)
+    if (pt_start[q + 1] < pt_start[q])
+      return fail(CBA_ERR_INVALID, "cba_triangulate: pt_start[%lld] = %lld is below pt_start[%lld] = %lld", (long long)(q + 1), (long long)pt_start[q + 1],
+                  (long long)q, (long long)pt_start[q]);
+  return CBA_OK;
+}

@@ -396,7 +396,8 @@ int cba_set_constraints(cba_problem* p, int32_t n_con, const int32_t* groups_a, 
  * float32 arrays) and `triangulate_image_points` (core/point_data.py:121-229: per point the 2k x 4 DLT matrix with
  * rows x P[2] - P[0], y P[2] - P[1], smallest right-singular vector).  One GPU thread per point; the singular
  * vector is the eigenvector of the smallest eigenvalue of A^T A (4 x 4, cyclic Jacobi).
- * Observations of a point are contiguous: point q owns obs_cam/obs_xy[pt_start[q] .. pt_start[q+1]).
+ * Observations of a point are contiguous: point q owns obs_cam/obs_xy[pt_start[q] .. pt_start[q+1]); pt_start[0] is 0 and the
+ * table never decreases (CBA_ERR_INVALID otherwise, the message names the entry, nothing is written).
  * cam_intr == NULL: obs_xy already holds undistorted normalised coordinates (the reference function's own input).
  * Points with fewer than two observations get NaN. */
 typedef struct {

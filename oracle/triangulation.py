@@ -10,6 +10,7 @@ TEST INFRASTRUCTURE ONLY (see oracle/__init__.py).  What the reference does with
   at most 10 steps, stop below 1e-8, ``theta_d`` clipped to [-pi/2, pi/2]).  **Parity unpinned**: the reference has no
   golden vector for either; they are validated by the round trip ``distort(undistort(p)) == p`` against the pinned
   projection functions of ``oracle/camera_model.py``.
+  Nor pinned, outside the model: a pinhole whose ``1 + k1 r^2 + ...`` crosses zero; fisheye coefficients that send Newton out of [0, pi/2].
 * ``CameraData.normalized_projection_matrix`` = ``[R | t]`` (3 x 4, identity intrinsics).
 * ``triangulate_image_points`` (``core/point_data.py:121-229``): per 3-D point the 2k x 4 DLT matrix with rows
   ``x P[2] - P[0]``, ``y P[2] - P[1]`` in ascending camera order, ``np.linalg.svd``, last right-singular vector,

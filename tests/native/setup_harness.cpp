@@ -82,6 +82,9 @@ int sp_constraint_plan(int P, int ncp, int n_con, const int* groups_a, const int
   return 0;
 }
 
+// the point table of a cba_triangulate_desc: 0, or CBA_ERR_INVALID with sp_last_error() naming the entry
+int sp_triangulate_starts_ok(long n_points, const long* pt_start) { return triangulate_starts_ok(fail, n_points, (const int64_t*)pt_start); }
+
 // out: cam, flags, bcam, total, scalars, sequence slot (doubles)
 void sp_mail_layout(int ncp, long* out) {
   const MailLayout m(ncp);
