@@ -213,6 +213,9 @@ struct cba_problem {
   int rank = 0, world = 1;
   unsigned long long group_generation = 0;
   bool sharded() const { return comm.load() != nullptr || group != nullptr || comm_aborted.load(); }
+  bool small_solve_on = true;  // CBA_SMALL_SOLVE=0: rigs of ncp <= SMALL_N take the blocked route too (tests/test_dense_solve_gpu.py)
+  // the dense camera system is formed, factored and solved by ONE workgroup (k_small_solve): no finalisation launch, no k_chol_step
+  bool one_workgroup_solve() const { return ncp <= SMALL_N && small_solve_on && !sharded() && !chol_trace; }
 };
 
 // What a small handle is made of is recycled: per device the library keeps up to four first arena chunks (4 MB), streams and mapped host
@@ -1100,7 +1103,7 @@ static int configure_kernels(cba_problem* p) {
   if (p->n_heavy && (rc = allow_lds(k_heavy_schur<NC>, (size_t)p->ncp * 3 * sizeof(double) + (size_t)p->ncp * sizeof(int)))) return rc;
   if ((rc = allow_lds(k_chol_apply, (size_t)p->ncp * 8))) return rc;
   if ((rc = allow_lds(k_step_cam, (size_t)p->lay.ncp_pad * 8))) return rc;
-  if (p->ncp <= SMALL_N && (rc = allow_lds(k_small_solve<NC>, kSmallSolveLds))) return rc;
+  if (p->one_workgroup_solve() && (rc = allow_lds(k_small_solve<NC>, kSmallSolveLds))) return rc;
   return CBA_OK;
 }
 
@@ -1313,6 +1316,7 @@ int cba_create(const cba_problem_desc* d, const cba_options* opt, cba_problem** 
   p->loss = d->loss; p->f_scale = d->f_scale;
   if (const char* e = std::getenv("CBA_REG_FINALIZE")) p->fuse_reg_finalize = e[0] != '0';
   if (const char* e = std::getenv("CBA_SPEC_SKIP")) p->spec_skip = e[0] != '0';
+  if (const char* e = std::getenv("CBA_SMALL_SOLVE")) p->small_solve_on = e[0] != '0';
 #ifdef CBA_PROFILING
   p->schur_clock = std::getenv("CBA_SCHUR_CLOCK") != nullptr;
   p->want_chol_trace = std::getenv("CBA_CHOL_TRACE") != nullptr;
@@ -1446,7 +1450,7 @@ int cba_get_info(cba_problem* p, cba_info* o) {
     const bool camg = cs ? (p->nct == 6 ? build_cs_camg<6>(p) : build_cs_camg<9>(p)) : (p->nct == 6 ? build_camg<6>(p) : build_camg<9>(p));
     const bool uglob = cs && (p->nct == 6 ? build_cs_uglob<6>(p) : build_cs_uglob<9>(p));
     o->build_camg = (camg ? 1 : 0) | (p->tab_global ? 2 : 0) | (cs ? 4 : 0) | (uglob ? 8 : 0) | (p->backsub_rec ? 16 : 0) |
-                    (p->con.n_con && p->con.small ? 32 : 0);
+                    (p->con.n_con && p->con.small ? 32 : 0) | (p->one_workgroup_solve() ? 64 : 0);
   }
   o->spec_jv_skipped = p->spec_jv_skipped;
   return CBA_OK;
@@ -1929,7 +1933,7 @@ static int run_newton_chain(cba_problem* p, double lam, const double* lam_dev, b
     // (fold + unprime + finalize as ONE kernel, a thread per camera pair, measured slower than the three launches: 42 instead of 31 us — 2080 threads
     // with 36 entries each against 147k threads with one)
     // one launch for the reduction and the finalisation where nothing comes between them (k_reg_finalize; CBA_REG_FINALIZE=0: the two launches)
-    const bool fused_finalize = fold_in_finalize && !(ncp <= SMALL_N && !p->chol_trace) && p->fuse_reg_finalize;
+    const bool fused_finalize = fold_in_finalize && !p->one_workgroup_solve() && p->fuse_reg_finalize;
     if (fused_finalize) {
       const int per = REG_REDUCE_Y_MAX / p->reg_reduce_y;
       const int tile_x = (p->gsz * p->gsz * NC * NC + 64 * per - 1) / (64 * per), fold_x = (p->gsz * NC * NC + 63) / 64, rhs_x = (p->lay.ncp_pad + 63) / 64;
@@ -1964,7 +1968,7 @@ static int run_newton_chain(cba_problem* p, double lam, const double* lam_dev, b
       hipLaunchKernelGGL(k_tri_pack, dim3(tg), dim3(256), 0, p->stream, p->Sacc, p->tri, ncp, 1, p->lay.ncp_pad);
     }
     const long nn = (long)ncp * ncp;
-    small_solve = ncp <= SMALL_N && !p->sharded() && !p->chol_trace;
+    small_solve = p->one_workgroup_solve();
     if (!small_solve && !fused_finalize) {
       hipLaunchKernelGGL((k_schur_finalize<NC>), dim3((int)((nn + 255) / 256)), dim3(256), 0, p->stream, p->Sacc,
                          p->Sacc + (size_t)ncp * ncp, p->Upacked, p->g, p->sinv, p->param_cam, p->param_loc, ncp, lam, lam_dev, p->cam_diag, p->S, p->rhs, p->Lbuf, p->ldw,

@@ -356,7 +356,10 @@ typedef struct {
                                observations than one chunk holds;
                                bit 5: the constraint rows run the small-component kernels (k_con_schur_small / k_con_backsub_small: every
                                component has at most 64 rows and its dense blocks fit 120 KB of LDS, no heavy points; CBA_CON_SMALL=0 turns them
-                               off); 0 without constraint rows. */
+                               off); 0 without constraint rows;
+                               bit 6: the dense camera system is solved by k_small_solve (one workgroup forms, factors and solves it in LDS:
+                               at most 96 camera parameters on a single rank; CBA_SMALL_SOLVE=0 sends such rigs down the blocked route,
+                               k_chol_step + k_chol_apply, which every larger rig takes). */
   int64_t spec_jv_skipped;  /* speculative J.g passes the device skipped because the solve ended at their trial point (cba_set_tolerances) */
 } cba_info;
 int cba_get_info(cba_problem* p, cba_info* out);
