@@ -659,6 +659,45 @@ class CaptureVolume:
         return CaptureVolume(self.camera_array, self.image_points.take(keep_rows), self.world_points.take(seen), self.constraints,
                              _known_map=new_row[obj].astype(np.int32))
 
+    # -- parameter uncertainty (caliscope_amd/uncertainty.py; the reference has none) ----------------------------------------------
+    def parameter_uncertainty(self, *, refine_intrinsics: bool = False, loss: str = "linear", f_scale: float | None = None, _solver=None):
+        """How well the matched observations determine every posed camera and every world point at the volume's current parameters
+        (meaningful after ``optimize()`` with the same ``refine_intrinsics`` and ``loss``): an
+        :class:`~caliscope_amd.uncertainty.UncertaintyReport` in the inner-constraint gauge from one device call.  ``f_scale`` is in
+        residual units and defaults to ``pixel_f_scale()``.  World points with fewer than two matched observations take no part and
+        have NaN rows in ``point_cov`` / ``point_std``.  A volume with constraints raises ``CalibrationError``: constraint rows couple
+        points and fix the scale, which this version does not model.  ``_solver`` replaces the device call (tests)."""
+        from caliscope_amd.uncertainty import DeviceUncertainty, build_report
+
+        if self.constraints is not None:
+            raise CalibrationError("parameter_uncertainty handles volumes without constraints: distance constraints couple points and fix the "
+                                   "scale of the gauge.  Build the volume without its ConstraintSet to get the reprojection-only covariance.")
+        mask, camera_indices, image_coords, obj_indices = self._matched_arrays()
+        if int(mask.sum()) == 0:
+            raise ValueError("No matched observations for the parameter covariance")
+        par = BundleParameterization.from_camera_array(self.camera_array, n_points=len(self.world_points), refine_intrinsics=refine_intrinsics)
+        tabs = par.device_tables()
+        x = par.pack(self.camera_array, self.world_points.points)
+        cam_x = np.zeros((len(par.blocks), 9))
+        for i, (blk, off) in enumerate(zip(par.blocks, par.camera_param_offsets)):
+            cam_x[i, : blk.n_params] = x[off : off + blk.n_params]
+        n_world = len(self.world_points)
+        views = np.bincount(obj_indices, minlength=n_world)
+        used = views >= 2
+        if not used.any():
+            raise ValueError("No world point has two matched observations")
+        new_row = np.cumsum(used, dtype=np.int64) - 1
+        keep = used[obj_indices]
+        backend = _solver or DeviceUncertainty()
+        result = backend.parameter_covariance(tabs["cam_model"], tabs["cam_n_params"], tabs["cam_const"], cam_x, self.world_points.points[used],
+                                              camera_indices[keep], new_row[obj_indices[keep]].astype(np.int32), image_coords[keep], loss=loss,
+                                              f_scale=self.pixel_f_scale() if f_scale is None else float(f_scale))
+        if not used.all():  # back to the rows of world_points
+            point_cov = np.full((n_world, 3, 3), np.nan)
+            point_cov[used] = result.point_cov
+            object.__setattr__(result, "point_cov", point_cov)
+        return build_report(result, [blk.cam_id for blk in par.blocks], tabs["cam_n_params"], cam_x)
+
     # -- scale accuracy (reference :755-831) ---------------------------------------------------------------
     def _scale_groups(self):
         """The (frame, object) groups of the scale report as flat arrays, or None when no observation carries object geometry:

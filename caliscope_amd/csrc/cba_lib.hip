@@ -1747,16 +1747,29 @@ static int run_linearize(cba_problem* p, cba_linearization* out) {
 // The dense solve is ncp / 32 + 2 small dependent launches.  Rounds 1-2 replayed them from a hipGraph recorded at create time; since the fused
 // iteration keeps the host a whole iteration ahead of the device, plain launches are the faster form (round 3, per iteration: cfg2 139 against
 // 149 us, cfg4 645 against 654 — the kernel behind a graph launch starts ~10 us late), and the graph is gone (round 4).
-static int enqueue_cholesky(cba_problem* p) {
-  const int n = p->ncp, nbk = (n + NB - 1) / NB;
+//
+// The factorisation launches take raw device pointers: cba_parameter_covariance (covariance_lib.hip, which declares the function again)
+// factors its own matrix with them.  W: (n + 1) x ldw work matrix (rows 0..n-1 the matrix, both triangles; row n a right-hand side), ldw a
+// multiple of 4; Xinv: (blocks + 1) NB x NB; Tinv: n x ldw, zero on entry outside what a call writes (the upper block triangle); flags[2] is
+// raised by a pivot that is not positive.  Not part of the C ABI.
+namespace cba {
+__attribute__((visibility("hidden"))) void enqueue_chol_factor(double* W, int n, int ldw, int* flags, long long* trace, double* Xinv, double* Tinv,
+                                                               hipStream_t stream) {
+  const int nbk = (n + NB - 1) / NB;
   for (int k = -1; k < nbk; ++k) {
     // step k: panel k solved for the blocks below it (and the rhs row), D_k+1 factored; extra workgroups apply the
     // rank-NB update of panel k - 1 to the blocks right of the current panel
     const int n_panel = k < 0 ? 1 : nbk - k;
     const int x = nbk - k - 1, n_trailing = k < 1 ? 0 : x * (x + 1) / 2;
     const int n_inverse = (k >= 1) ? (nbk - k) * k : 0;  // blocks (i >= k, j < k) of T = L^-T take the term of panel k - 1
-    hipLaunchKernelGGL(k_chol_step, dim3(n_panel + n_trailing + n_inverse), dim3(CHOL_THREADS), 0, p->stream, p->Lbuf, n, p->ldw, k, p->flags, p->chol_trace, p->Xinv, p->Tinv);
+    hipLaunchKernelGGL(k_chol_step, dim3(n_panel + n_trailing + n_inverse), dim3(CHOL_THREADS), 0, stream, W, n, ldw, k, flags, trace, Xinv, Tinv);
   }
+}
+}  // namespace cba
+
+static int enqueue_cholesky(cba_problem* p) {
+  const int n = p->ncp, nbk = (n + NB - 1) / NB;
+  enqueue_chol_factor(p->Lbuf, n, p->ldw, p->flags, p->chol_trace, p->Xinv, p->Tinv, p->stream);
   hipLaunchKernelGGL(k_chol_apply, dim3(nbk), dim3(APPLY_THREADS), (size_t)n * 8, p->stream, (const double*)p->Tinv, (const double*)p->Lbuf, n, p->ldw, p->s);
   return CBA_OK;
 }

@@ -1,0 +1,498 @@
+// cba_parameter_covariance of libcaliscope_ba.so (C ABI: include/caliscope/uncertainty.h): the covariance of every camera's parameters and
+// of every point in the inner-constraint gauge, sigma0^2 pinv(J^T J), from the bordered system with points and multipliers eliminated.
+// The formulas, the per-element arithmetic, the checks and the host-side small matrices are covariance_math.h (shared with
+// tests/native/covariance_harness.cpp); this file holds the kernels and the entry point.  Everything is FP64.
+//
+//   k_unc_cam        one thread per camera: the CamTab of ba_math.h and the camera's gauge rows, written into B (B starts as Nc).
+//   k_unc_obs        one thread per observation, in point order: project_full + robust_one, the W block A^T B and B^T B stored per
+//                    observation, A^T A added to U of the camera and rho to the cost (atomics; the cost per wave by shuffles).
+//   k_unc_point      one wave per point: V = sum B^T B, V^-1 (chol3), Z = V^-1 Np, Y_a = W_a V^-1 per observation (stored: the point
+//                    formula reads them again), -W_a Z into B and -Y_a W_b^T into the dense Schur complement for every ordered pair of the
+//                    point's observations whose entry lies in the upper triangle (atomics: a repeated (camera, point) pair simply adds).
+//   k_unc_d          D = sum Np^T Z over the points: grid-stride, 28 sums per thread, per wave by shuffles, then atomics.
+//   (host)           D^-1 (7 x 7, cov_spd_inverse) and sigma0^2 between two launches.
+//   k_unc_assemble   one thread per entry of the upper triangle: St = U + Schur + B D^-1 B^T, scaled by 1 / sqrt of its diagonal on both
+//                    sides, into both triangles of the Cholesky work matrix.
+//   k_chol_step      the solver's blocked Cholesky (cba_kernels.h through enqueue_chol_factor of cba_lib.hip): L and T = L^-T.
+//   k_unc_pivots     one thread per pivot: a pivot at or below COV_PIVOT_TINY raises the numeric error.
+//   k_unc_ttt        C = St^-1 = Ds T T^T Ds by v_mfma_f64_16x16x4: one workgroup per 32 x 32 block of the upper block triangle, four
+//                    16 x 16 tiles, depth from the block's column to the end (T is upper triangular); written to both triangles.
+//   (host)           E = C B D^-1 and F (cov_gauge_terms: O(ncp^2) flops), the camera outputs sigma0^2 C.
+//   k_unc_point_cov  one wave per point: sigma0^2 (V^-1 + Z F Z^T + sum_ab Y_a^T C_ab Y_b + sum_a sym(Y_a^T E_a Z^T)), the k^2 pairs and
+//                    the k rank-7 terms spread over the lanes, 3 x 3 sums by shuffles.
+//
+// Null stream throughout.  Scaling by sigma0^2 has no kernel of its own: the point kernel applies it, the camera blocks take it on the
+// host where they are copied into the caller's arrays.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "ba_math.h"
+#include "covariance_math.h"
+#include "device_call.h"
+
+namespace cba {
+// cba_lib.hip: the launches of the blocked Cholesky on raw device pointers
+__attribute__((visibility("hidden"))) void enqueue_chol_factor(double* W, int n, int ldw, int* flags, long long* trace, double* Xinv, double* Tinv,
+                                                               hipStream_t stream);
+}  // namespace cba
+
+using namespace cba;
+
+namespace {
+
+constexpr int NB = 32;  // block width of the Cholesky (cba_kernels.h)
+typedef double v4f64 __attribute__((ext_vector_type(4)));
+enum CovFlag : int { F_POINT = 0, F_DIAG = 1, F_CHOL = 2, F_TINY = 3, F_WHICH = 4, N_FLAGS = 8 };
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;  // lane 0 holds the sum
+}
+
+__global__ void __launch_bounds__(COV_BLOCK)
+k_unc_cam(int32_t n_cams, const int32_t* __restrict__ cam_model, const int32_t* __restrict__ cam_off, const double* __restrict__ cam_const,
+          const double* __restrict__ cam_x, double* __restrict__ tab, double* __restrict__ B) {
+  const int32_t c = blockIdx.x * COV_BLOCK + threadIdx.x;
+  if (c >= n_cams) return;
+  const int32_t off = cam_off[c], np = cam_off[c + 1] - off;
+  double xc[MAX_NC];
+#pragma unroll
+  for (int i = 0; i < MAX_NC; ++i) xc[i] = cam_x[(int64_t)c * MAX_NC + i];
+  CamTab t;
+  cam_prepare(xc, cam_const + (int64_t)c * CAM_CONST_STRIDE, cam_model[c], np, &t, off);
+  const double* src = reinterpret_cast<const double*>(&t);
+#pragma unroll
+  for (int i = 0; i < CAMTAB_DOUBLES; ++i) tab[(int64_t)c * CAMTAB_DOUBLES + i] = src[i];
+  double N[MAX_NC][COV_GAUGE];
+  cov_gauge_cam(t, N);
+#pragma unroll
+  for (int r = 0; r < MAX_NC; ++r)
+    if (r < np) {
+#pragma unroll
+      for (int j = 0; j < COV_GAUGE; ++j) B[(int64_t)(off + r) * COV_GAUGE + j] = N[r][j];
+    }
+}
+
+__global__ void __launch_bounds__(COV_BLOCK)
+k_unc_obs(int64_t n_obs, const int64_t* __restrict__ order, const int32_t* __restrict__ obs_cam, const int32_t* __restrict__ obs_pt,
+          const double* __restrict__ obs_uv, const double* __restrict__ tab, const double* __restrict__ points, int loss, double f_scale,
+          double* __restrict__ Wblk, double* __restrict__ Vobs, int32_t* __restrict__ cam_sorted, double* __restrict__ U, double* __restrict__ cost) {
+  const int64_t i = (int64_t)blockIdx.x * COV_BLOCK + threadIdx.x;
+  double rho = 0.0;
+  if (i < n_obs) {
+    const int64_t o = order[i];
+    const int32_t cam = obs_cam[o];
+    const int64_t p = obs_pt[o];
+    const CamTab& c = reinterpret_cast<const CamTab*>(tab)[cam];
+    const double X[3] = {points[3 * p], points[3 * p + 1], points[3 * p + 2]};
+    const double uv[2] = {obs_uv[2 * o], obs_uv[2 * o + 1]};
+    double A[2][MAX_NC], B[2][3], Wb[3 * MAX_NC], Vo[6];
+    rho = cov_obs_jacobian(c, X, uv, loss, f_scale, A, B);
+    cov_obs_products(A, B, Wb, Vo);
+#pragma unroll
+    for (int e = 0; e < 3 * MAX_NC; ++e) Wblk[i * (3 * MAX_NC) + e] = Wb[e];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) Vobs[i * 6 + e] = Vo[e];
+    cam_sorted[i] = cam;
+    const bool nine = c.nparams == 9.0;
+    double* Uc = U + (int64_t)cam * (MAX_NC * MAX_NC);
+#pragma unroll
+    for (int r = 0; r < MAX_NC; ++r)
+#pragma unroll
+      for (int q = r; q < MAX_NC; ++q)
+        if (q < 6 || nine) atomicAdd(&Uc[r * MAX_NC + q], A[0][r] * A[0][q] + A[1][r] * A[1][q]);
+  }
+  rho = wave_sum(rho);
+  if ((threadIdx.x & 63) == 0 && rho != 0.0) atomicAdd(cost, 0.5 * rho);
+}
+
+__global__ void __launch_bounds__(COV_POINT_THREADS)
+k_unc_point(const int64_t* __restrict__ pt_start, const int32_t* __restrict__ cam_sorted, const int32_t* __restrict__ cam_off, int32_t ncp,
+            const double* __restrict__ points, const double* __restrict__ Wblk, const double* __restrict__ Vobs, double* __restrict__ Y,
+            double* __restrict__ Vinv, double* __restrict__ Zbuf, double* __restrict__ B, double* __restrict__ Sacc, int* __restrict__ flags) {
+  __shared__ double sh_vi[9], sh_z[3 * COV_GAUGE];
+  const int64_t p = blockIdx.x;
+  const int t = threadIdx.x;
+  const int64_t s = pt_start[p], k = pt_start[p + 1] - s;
+  double V[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int64_t a = 0; a < k; ++a) {
+#pragma unroll
+    for (int e = 0; e < 6; ++e) V[e] += Vobs[(s + a) * 6 + e];
+  }
+  double Vi[6];
+  if (!cov_point_vinv(V, Vi)) {  // (every lane holds the same V: the branch is uniform)
+    if (t == 0) { flags[F_POINT] = 1; atomicMax(&flags[F_WHICH], (int)p + 1); }
+    return;
+  }
+  const double X[3] = {points[3 * p], points[3 * p + 1], points[3 * p + 2]};
+  double Z[3][COV_GAUGE];
+  cov_point_z(Vi, X, Z);
+  if (t == 0) {
+#pragma unroll
+    for (int e = 0; e < 6; ++e) Vinv[p * 6 + e] = Vi[e];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) sh_vi[3 * a + b] = cov_sym3(Vi, a, b);
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int j = 0; j < COV_GAUGE; ++j) { sh_z[a * COV_GAUGE + j] = Z[a][j]; Zbuf[p * (3 * COV_GAUGE) + a * COV_GAUGE + j] = Z[a][j]; }
+  }
+  __syncthreads();
+  constexpr int WB = 3 * MAX_NC;
+  for (int64_t it = t; it < k * WB; it += COV_POINT_THREADS) {  // Y_a = W_a V^-1
+    const int64_t a = it / WB;
+    const int e = (int)(it % WB), r = e / 3, q = e % 3;
+    const double* w = Wblk + (s + a) * WB + 3 * r;
+    Y[(s + a) * WB + e] = w[0] * sh_vi[q] + w[1] * sh_vi[3 + q] + w[2] * sh_vi[6 + q];
+  }
+  __syncthreads();  // (Y of this point is read below by other lanes)
+  for (int64_t it = t; it < k * (MAX_NC * COV_GAUGE); it += COV_POINT_THREADS) {  // B -= W_a Z
+    const int64_t a = it / (MAX_NC * COV_GAUGE);
+    const int e = (int)(it % (MAX_NC * COV_GAUGE)), r = e / COV_GAUGE, j = e % COV_GAUGE;
+    const int32_t cam = cam_sorted[s + a], off = cam_off[cam], np = cam_off[cam + 1] - off;
+    if (r >= np) continue;
+    const double* w = Wblk + (s + a) * WB + 3 * r;
+    atomicAdd(&B[(int64_t)(off + r) * COV_GAUGE + j], -(w[0] * sh_z[j] + w[1] * sh_z[COV_GAUGE + j] + w[2] * sh_z[2 * COV_GAUGE + j]));
+  }
+  constexpr int BLK = MAX_NC * MAX_NC;
+  for (int64_t it = t; it < k * k * BLK; it += COV_POINT_THREADS) {  // Schur -= Y_a W_b^T, upper triangle
+    const int64_t ab = it / BLK, a = ab / k, b = ab % k;
+    const int e = (int)(it % BLK), r = e / MAX_NC, c = e % MAX_NC;
+    const int32_t cam_a = cam_sorted[s + a], off_a = cam_off[cam_a], np_a = cam_off[cam_a + 1] - off_a;
+    const int32_t cam_b = cam_sorted[s + b], off_b = cam_off[cam_b], np_b = cam_off[cam_b + 1] - off_b;
+    const int32_t row = off_a + r, col = off_b + c;
+    if (r >= np_a || c >= np_b || row > col) continue;
+    const double* y = Y + (s + a) * WB + 3 * r;
+    const double* w = Wblk + (s + b) * WB + 3 * c;
+    atomicAdd(&Sacc[(int64_t)row * ncp + col], -(y[0] * w[0] + y[1] * w[1] + y[2] * w[2]));
+  }
+}
+
+__global__ void __launch_bounds__(COV_BLOCK)
+k_unc_d(int64_t n_points, const double* __restrict__ points, const double* __restrict__ Zbuf, double* __restrict__ D) {
+  double acc[COV_GAUGE * (COV_GAUGE + 1) / 2];
+#pragma unroll
+  for (int e = 0; e < COV_GAUGE * (COV_GAUGE + 1) / 2; ++e) acc[e] = 0.0;
+  for (int64_t p = (int64_t)blockIdx.x * COV_BLOCK + threadIdx.x; p < n_points; p += (int64_t)gridDim.x * COV_BLOCK) {
+    double N[3][COV_GAUGE], Z[3][COV_GAUGE];
+    cov_gauge_point(points[3 * p], points[3 * p + 1], points[3 * p + 2], N);
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int j = 0; j < COV_GAUGE; ++j) Z[a][j] = Zbuf[p * (3 * COV_GAUGE) + a * COV_GAUGE + j];
+    int e = 0;
+#pragma unroll
+    for (int j = 0; j < COV_GAUGE; ++j)
+#pragma unroll
+      for (int m = j; m < COV_GAUGE; ++m) acc[e++] += N[0][j] * Z[0][m] + N[1][j] * Z[1][m] + N[2][j] * Z[2][m];
+  }
+  int e = 0;
+#pragma unroll
+  for (int j = 0; j < COV_GAUGE; ++j)
+#pragma unroll
+    for (int m = j; m < COV_GAUGE; ++m) {
+      const double v = wave_sum(acc[e++]);
+      if ((threadIdx.x & 63) == 0) atomicAdd(&D[j * COV_GAUGE + m], v);
+    }
+}
+
+// entry (row <= col) of St = U + Schur + B D^-1 B^T
+__device__ __forceinline__ double st_entry(int row, int col, int32_t ncp, const double* __restrict__ U, const double* __restrict__ Sacc,
+                                           const double* __restrict__ B, const double* __restrict__ Dinv, const int32_t* __restrict__ param_cam,
+                                           const int32_t* __restrict__ param_loc) {
+  double v = Sacc[(int64_t)row * ncp + col];
+  if (param_cam[row] == param_cam[col]) v += U[(int64_t)param_cam[row] * (MAX_NC * MAX_NC) + param_loc[row] * MAX_NC + param_loc[col]];
+#pragma unroll
+  for (int j = 0; j < COV_GAUGE; ++j) {
+    double s = 0.0;
+#pragma unroll
+    for (int m = 0; m < COV_GAUGE; ++m) s += Dinv[j * COV_GAUGE + m] * B[(int64_t)col * COV_GAUGE + m];
+    v += B[(int64_t)row * COV_GAUGE + j] * s;
+  }
+  return v;
+}
+
+__global__ void __launch_bounds__(COV_BLOCK)
+k_unc_assemble(int32_t ncp, int ldw, const double* __restrict__ U, const double* __restrict__ Sacc, const double* __restrict__ B,
+               const double* __restrict__ Dinv, const int32_t* __restrict__ param_cam, const int32_t* __restrict__ param_loc,
+               double* __restrict__ W, double* __restrict__ scale, int* __restrict__ flags) {
+  const int64_t t = (int64_t)blockIdx.x * COV_BLOCK + threadIdx.x;
+  if (t >= (int64_t)ncp * ncp) return;
+  const int row = (int)(t / ncp), col = (int)(t % ncp);
+  if (col < row) return;
+  const double dr = st_entry(row, row, ncp, U, Sacc, B, Dinv, param_cam, param_loc);
+  const double dc = st_entry(col, col, ncp, U, Sacc, B, Dinv, param_cam, param_loc);
+  double sr = 1.0, sc = 1.0;
+  if (dr > 0.0 && dr < 1.7e308) sr = 1.0 / sqrt(dr); else flags[F_DIAG] = 1;
+  if (dc > 0.0 && dc < 1.7e308) sc = 1.0 / sqrt(dc); else flags[F_DIAG] = 1;
+  const double v = (row == col ? dr : st_entry(row, col, ncp, U, Sacc, B, Dinv, param_cam, param_loc)) * sr * sc;
+  W[(int64_t)row * ldw + col] = v;
+  W[(int64_t)col * ldw + row] = v;
+  if (row == col) scale[row] = sr;
+}
+
+__global__ void __launch_bounds__(COV_BLOCK)
+k_unc_pivots(int n, int ldw, const double* __restrict__ W, int* __restrict__ flags) {
+  const int j = blockIdx.x * COV_BLOCK + threadIdx.x;
+  if (j >= n) return;
+  const double l = W[(int64_t)j * ldw + j];
+  if (!(l * l > COV_PIVOT_TINY) || !(l < 1.7e308)) flags[F_TINY] = 1;
+}
+
+// T: (32 blocks) x ldw with ldw = 32 blocks, zero outside the upper triangle of its first n rows and columns: no read needs a bound.
+__global__ void __launch_bounds__(256)
+k_unc_ttt(int n, int ldw, const double* __restrict__ T, const double* __restrict__ scale, double* __restrict__ C) {
+  const int bi = blockIdx.y, bj = blockIdx.x;
+  if (bj < bi) return;
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int ti = wv >> 1, tj = wv & 1, lr = lane & 15, kq = 4 * (lane >> 4);
+  const double* pa = T + (int64_t)(bi * NB + ti * 16 + lr) * ldw + kq;
+  const double* pb = T + (int64_t)(bj * NB + tj * 16 + lr) * ldw + kq;
+  v4f64 acc = {0.0, 0.0, 0.0, 0.0};
+  // a lane loads 4 consecutive doubles of its row per 16-deep slab; MFMA step t pairs the t-th of each lane's four on both operands: the
+  // same permutation of the depth index on both sides, so the sum is unchanged
+  for (int q0 = bj * NB; q0 < ldw; q0 += 16) {
+    const double2 a0 = *reinterpret_cast<const double2*>(pa + q0), a1 = *reinterpret_cast<const double2*>(pa + q0 + 2);
+    const double2 b0 = *reinterpret_cast<const double2*>(pb + q0), b1 = *reinterpret_cast<const double2*>(pb + q0 + 2);
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a0.x, b0.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a0.y, b0.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a1.x, b1.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a1.y, b1.y, acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int gi = bi * NB + ti * 16 + (lane >> 4) + 4 * r, gj = bj * NB + tj * 16 + lr;
+    if (gi < n && gj < n && gi <= gj) {
+      const double v = acc[r] * scale[gi] * scale[gj];
+      C[(int64_t)gi * n + gj] = v;
+      C[(int64_t)gj * n + gi] = v;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(COV_POINT_THREADS)
+k_unc_point_cov(const int64_t* __restrict__ pt_start, const int32_t* __restrict__ cam_sorted, const int32_t* __restrict__ cam_off, int32_t ncp,
+                const double* __restrict__ Y, const double* __restrict__ Vinv, const double* __restrict__ Zbuf, const double* __restrict__ C,
+                const double* __restrict__ E, const double* __restrict__ F, double sigma0_sq, double* __restrict__ out) {
+  const int64_t p = blockIdx.x;
+  const int t = threadIdx.x;
+  const int64_t s = pt_start[p], k = pt_start[p + 1] - s;
+  constexpr int WB = 3 * MAX_NC;
+  double Z[3][COV_GAUGE];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int j = 0; j < COV_GAUGE; ++j) Z[a][j] = Zbuf[p * (3 * COV_GAUGE) + a * COV_GAUGE + j];
+  double full[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  for (int64_t it = t; it < k * k; it += COV_POINT_THREADS) {  // Y_a^T C_ab Y_b
+    const int64_t a = it / k, b = it % k;
+    const int32_t cam_a = cam_sorted[s + a], off_a = cam_off[cam_a], np_a = cam_off[cam_a + 1] - off_a;
+    const int32_t cam_b = cam_sorted[s + b], off_b = cam_off[cam_b], np_b = cam_off[cam_b + 1] - off_b;
+    double Yb[WB];
+#pragma unroll
+    for (int e = 0; e < WB; ++e) Yb[e] = Y[(s + b) * WB + e];
+#pragma unroll
+    for (int r = 0; r < MAX_NC; ++r) {
+      if (r < np_a) {
+        const double* crow = C + (int64_t)(off_a + r) * ncp + off_b;
+        double t3[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int c = 0; c < MAX_NC; ++c) {
+          const double cv = c < np_b ? crow[c] : 0.0;
+#pragma unroll
+          for (int q = 0; q < 3; ++q) t3[q] += cv * Yb[3 * c + q];
+        }
+        const double* ya = Y + (s + a) * WB + 3 * r;
+#pragma unroll
+        for (int pp = 0; pp < 3; ++pp)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) full[pp][q] += ya[pp] * t3[q];
+      }
+    }
+  }
+  for (int64_t a = t; a < k; a += COV_POINT_THREADS) {  // Y_a^T E_a Z^T and its transpose (the sum is symmetrised below: twice the term)
+    const int32_t cam_a = cam_sorted[s + a], off_a = cam_off[cam_a], np_a = cam_off[cam_a + 1] - off_a;
+#pragma unroll
+    for (int r = 0; r < MAX_NC; ++r) {
+      if (r < np_a) {
+        const double* er = E + (int64_t)(off_a + r) * COV_GAUGE;
+        double t3[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < COV_GAUGE; ++j) {
+          const double ev = er[j];
+#pragma unroll
+          for (int q = 0; q < 3; ++q) t3[q] += ev * Z[q][j];
+        }
+        const double* ya = Y + (s + a) * WB + 3 * r;
+#pragma unroll
+        for (int pp = 0; pp < 3; ++pp)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) full[pp][q] += 2.0 * ya[pp] * t3[q];
+      }
+    }
+  }
+#pragma unroll
+  for (int pp = 0; pp < 3; ++pp)
+#pragma unroll
+    for (int q = 0; q < 3; ++q) full[pp][q] = wave_sum(full[pp][q]);
+  if (t != 0) return;
+  double Vi[6], Fm[COV_GAUGE * COV_GAUGE], P[6];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) Vi[e] = Vinv[p * 6 + e];
+#pragma unroll
+  for (int e = 0; e < COV_GAUGE * COV_GAUGE; ++e) Fm[e] = F[e];
+  cov_point_base(Vi, Z, Fm, P);
+  int e = 0;
+#pragma unroll
+  for (int pp = 0; pp < 3; ++pp)
+#pragma unroll
+    for (int q = pp; q < 3; ++q) {
+      out[p * 6 + e] = sigma0_sq * (P[e] + 0.5 * (full[pp][q] + full[q][pp]));
+      ++e;
+    }
+}
+
+}  // namespace
+
+extern "C" int cba_parameter_covariance(const cba_cov_desc* d, int32_t device, cba_cov_out* out) {
+  const char* what = "cba_parameter_covariance";
+  if (!d || !out) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
+  // every index the kernels use, checked on the host before anything reaches the device
+  std::string msg;
+  CovPlan plan;
+  int rc = cov_validate(d, plan, msg);
+  if (rc) return err(rc, msg);
+  rc = select_device(device, what);
+  if (rc) return rc;
+  const int32_t n_cams = d->n_cams, ncp = plan.ncp();
+  const int64_t n_obs = d->n_obs, n_points = d->n_points;
+  const int nbk = (ncp + NB - 1) / NB, ldw = nbk * NB;  // the work matrix and T padded to whole blocks: k_unc_ttt reads without bounds
+  std::vector<int32_t> param_cam((size_t)ncp), param_loc((size_t)ncp);
+  for (int32_t c = 0; c < n_cams; ++c)
+    for (int32_t r = plan.cam_off[(size_t)c]; r < plan.cam_off[(size_t)c + 1]; ++r) { param_cam[(size_t)r] = c; param_loc[(size_t)r] = r - plan.cam_off[(size_t)c]; }
+  std::vector<double> cam_x((size_t)n_cams * MAX_NC, 0.0);  // (the caller's rows behind a six-parameter camera's pose are not read)
+  for (int32_t c = 0; c < n_cams; ++c)
+    for (int i = 0; i < d->cam_nparams[c]; ++i) cam_x[(size_t)c * MAX_NC + i] = d->cam_x[(size_t)c * MAX_NC + i];
+
+  Buffers buf;
+  const int32_t* dmodel = buf.in(d->cam_model, n_cams);
+  const int32_t* dcam_off = buf.in(plan.cam_off.data(), n_cams + 1);
+  const double* dconst = buf.in(d->cam_const, n_cams, CAM_CONST_STRIDE);
+  const double* dcam_x = buf.in(cam_x.data(), n_cams, MAX_NC);
+  const double* dpoints = buf.in(d->points, n_points, 3);
+  const int32_t* dobs_cam = buf.in(d->obs_cam, n_obs);
+  const int32_t* dobs_pt = buf.in(d->obs_pt, n_obs);
+  const double* dobs_uv = buf.in(d->obs_uv, n_obs, 2);
+  const int64_t* dorder = buf.in(plan.order.data(), n_obs);
+  const int64_t* dpt_start = buf.in(plan.pt_start.data(), n_points + 1);
+  const int32_t* dparam_cam = buf.in(param_cam.data(), ncp);
+  const int32_t* dparam_loc = buf.in(param_loc.data(), ncp);
+  double* dtab = buf.make<double>(n_cams, CAMTAB_DOUBLES);
+  double* dWblk = buf.make<double>(n_obs, 3 * MAX_NC);
+  double* dVobs = buf.make<double>(n_obs, 6);
+  double* dY = buf.make<double>(n_obs, 3 * MAX_NC);
+  int32_t* dcam_sorted = buf.make<int32_t>(n_obs);
+  double* dVinv = buf.make<double>(n_points, 6);
+  double* dZ = buf.make<double>(n_points, 3 * COV_GAUGE);
+  double* dB = buf.make<double>(ncp, COV_GAUGE);
+  double* dscale = buf.make<double>(ncp);
+  double* dC = buf.make<double>(ncp, ncp);
+  double* dXinv = buf.make<double>(nbk + 1, NB * NB);
+  // zeroed in one block: the work matrix [ldw + 1][ldw] and T [ldw][ldw] (first: their rows are read sixteen bytes at a time), U [n_cams][81],
+  // Schur [ncp][ncp], D [49], cost [1], flags
+  const size_t n_U = (size_t)n_cams * MAX_NC * MAX_NC, n_S = (size_t)ncp * ncp, n_W = ((size_t)ldw + 1) * ldw, n_T = (size_t)ldw * ldw;
+  const size_t n_zero = n_U + n_S + COV_GAUGE * COV_GAUGE + 1 + n_W + n_T + N_FLAGS;
+  double* dzero = buf.make<double>(n_zero);
+  if (buf.status()) return buf.result(what);
+  double* dW = dzero;
+  double* dT = dW + n_W;
+  double* dU = dT + n_T;
+  double* dSacc = dU + n_U;
+  double* dD = dSacc + n_S;
+  double* dcost = dD + COV_GAUGE * COV_GAUGE;
+  int* dflags = reinterpret_cast<int*>(dcost + 1);
+  buf.check(hipMemsetAsync(dzero, 0, n_zero * sizeof(double), 0));
+  if (buf.status()) return buf.result(what);
+
+  const auto blocks = [](int64_t n) { return dim3((unsigned)((n + COV_BLOCK - 1) / COV_BLOCK)); };
+  hipLaunchKernelGGL(k_unc_cam, blocks(n_cams), dim3(COV_BLOCK), 0, 0, n_cams, dmodel, dcam_off, dconst, dcam_x, dtab, dB);
+  hipLaunchKernelGGL(k_unc_obs, blocks(n_obs), dim3(COV_BLOCK), 0, 0, n_obs, dorder, dobs_cam, dobs_pt, dobs_uv, (const double*)dtab, dpoints, (int)d->loss,
+                     d->f_scale, dWblk, dVobs, dcam_sorted, dU, dcost);
+  hipLaunchKernelGGL(k_unc_point, dim3((unsigned)n_points), dim3(COV_POINT_THREADS), 0, 0, dpt_start, (const int32_t*)dcam_sorted, dcam_off, ncp, dpoints,
+                     (const double*)dWblk, (const double*)dVobs, dY, dVinv, dZ, dB, dSacc, dflags);
+  const int64_t d_blocks = (n_points + COV_BLOCK - 1) / COV_BLOCK;
+  hipLaunchKernelGGL(k_unc_d, dim3((unsigned)(d_blocks < 256 ? d_blocks : 256)), dim3(COV_BLOCK), 0, 0, n_points, dpoints, (const double*)dZ, dD);
+  buf.check(hipGetLastError());
+  std::vector<double> D(COV_GAUGE * COV_GAUGE + 1);  // D and the cost behind it
+  std::vector<int> flags(N_FLAGS, 0);
+  buf.out(D.data(), (const double*)dD, COV_GAUGE * COV_GAUGE + 1);
+  buf.out(flags.data(), (const int*)dflags, N_FLAGS);
+  if (buf.status()) return buf.result(what);
+  if (flags[F_POINT])
+    return err(CBA_ERR_NUMERIC, std::string(what) + ": point " + std::to_string(flags[F_WHICH] - 1) + ": its observations do not determine it (rays parallel or not finite)");
+  const double cost = D[COV_GAUGE * COV_GAUGE];
+  D.resize(COV_GAUGE * COV_GAUGE);
+  for (int j = 0; j < COV_GAUGE; ++j)
+    for (int m = j + 1; m < COV_GAUGE; ++m) D[(size_t)m * COV_GAUGE + j] = D[(size_t)j * COV_GAUGE + m];
+  if (!std::isfinite(cost) || !cov_spd_inverse(D, COV_GAUGE))
+    return err(CBA_ERR_NUMERIC, std::string(what) + ": the points do not fix the seven gauge directions (all on one line, or not finite)");
+  const double sigma0_sq = 2.0 * cost / (double)plan.dof;
+  const double* dDinv = buf.in(D.data(), COV_GAUGE * COV_GAUGE);
+  if (buf.status()) return buf.result(what);
+
+  hipLaunchKernelGGL(k_unc_assemble, blocks((int64_t)ncp * ncp), dim3(COV_BLOCK), 0, 0, ncp, ldw, (const double*)dU, (const double*)dSacc, (const double*)dB, dDinv,
+                     dparam_cam, dparam_loc, dW, dscale, dflags);
+  enqueue_chol_factor(dW, ncp, ldw, dflags, nullptr, dXinv, dT, 0);
+  hipLaunchKernelGGL(k_unc_pivots, blocks(ncp), dim3(COV_BLOCK), 0, 0, (int)ncp, ldw, (const double*)dW, dflags);
+  hipLaunchKernelGGL(k_unc_ttt, dim3((unsigned)nbk, (unsigned)nbk), dim3(256), 0, 0, (int)ncp, ldw, (const double*)dT, (const double*)dscale, dC);
+  buf.check(hipGetLastError());
+  std::vector<double> C(n_S), B((size_t)ncp * COV_GAUGE);
+  buf.out(flags.data(), (const int*)dflags, N_FLAGS);
+  buf.out(C.data(), (const double*)dC, ncp, ncp);
+  buf.out(B.data(), (const double*)dB, ncp, COV_GAUGE);
+  if (buf.status()) return buf.result(what);
+  if (flags[F_DIAG] || flags[F_CHOL] || flags[F_TINY])
+    return err(CBA_ERR_NUMERIC, std::string(what) + ": the reduced camera system is not positive definite beyond the gauge (a pivot is not safely positive): "
+                                                    "the scene does not determine every camera parameter");
+  std::vector<double> point_cov;
+  if (out->point_cov) {
+    std::vector<double> E, F;
+    cov_gauge_terms(ncp, C.data(), B.data(), D.data(), E, F);
+    const double* dE = buf.in(E.data(), ncp, COV_GAUGE);
+    const double* dF = buf.in(F.data(), COV_GAUGE * COV_GAUGE);
+    double* dout = buf.make<double>(n_points, 6);
+    if (buf.status()) return buf.result(what);
+    hipLaunchKernelGGL(k_unc_point_cov, dim3((unsigned)n_points), dim3(COV_POINT_THREADS), 0, 0, dpt_start, (const int32_t*)dcam_sorted, dcam_off, ncp,
+                       (const double*)dY, (const double*)dVinv, (const double*)dZ, (const double*)dC, dE, dF, sigma0_sq, dout);
+    buf.check(hipGetLastError());
+    point_cov.resize((size_t)n_points * 6);
+    buf.out(point_cov.data(), (const double*)dout, n_points, 6);
+    if (buf.status()) return buf.result(what);
+    for (double v : point_cov)
+      if (!std::isfinite(v)) return err(CBA_ERR_NUMERIC, std::string(what) + ": a point covariance is not finite");
+  }
+  for (double v : C)
+    if (!std::isfinite(v)) return err(CBA_ERR_NUMERIC, std::string(what) + ": a camera covariance is not finite");
+  // outputs, written only now: a failed call leaves the caller's arrays alone
+  if (out->point_cov) std::copy(point_cov.begin(), point_cov.end(), out->point_cov);
+  if (out->cam_cov_full)
+    for (size_t i = 0; i < n_S; ++i) out->cam_cov_full[i] = sigma0_sq * C[i];
+  if (out->cam_cov)
+    for (int32_t c = 0; c < n_cams; ++c) {
+      const int32_t off = plan.cam_off[(size_t)c], np = plan.cam_off[(size_t)c + 1] - off;
+      for (int r = 0; r < MAX_NC; ++r)
+        for (int q = 0; q < MAX_NC; ++q)
+          out->cam_cov[((size_t)c * MAX_NC + r) * MAX_NC + q] = (r < np && q < np) ? sigma0_sq * C[(size_t)(off + r) * ncp + off + q] : 0.0;
+    }
+  if (out->sigma0_sq) *out->sigma0_sq = sigma0_sq;
+  if (out->dof) *out->dof = plan.dof;
+  if (out->cost) *out->cost = cost;
+  return CBA_OK;
+}

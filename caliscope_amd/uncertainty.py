@@ -1,0 +1,220 @@
+"""How well the observations determine every camera and every point: the free-network covariance in one device call.
+
+Reprojection RMS says how well a calibration fits, not how well the data pin it down: a rig can fit to 0.3 px and still have a
+camera whose depth is barely constrained.  ``cba_parameter_covariance`` (``include/caliscope/uncertainty.h``,
+``csrc/covariance_math.h``, ``csrc/covariance_lib.hip``) returns the covariance of the bundle-adjustment parameters in the
+inner-constraint (minimum-trace, free-network) gauge, ``sigma0^2 pinv(J^T J)``, with ``J`` the Jacobian the solver uses: the
+camera blocks from a dense factorisation of the reduced camera system bordered by the seven gauge directions, the point blocks
+from a 3 x 3 formula per point.  :meth:`CaptureVolume.parameter_uncertainty` is built on it and returns an
+:class:`UncertaintyReport`: per camera the covariance of its parameters, of its centre (world units) and the standard deviation of
+its orientation (degrees), per world point its covariance.  The reference computes no covariance.
+
+Scope: volumes without distance constraints (constraint rows couple points and fix the scale).
+
+There is no CPU fallback: without the library or a GPU the call raises ``BackendError``.  ``_solver`` of the method replaces the
+device call (an object with ``parameter_covariance``, as :class:`DeviceUncertainty`) — the CPU test-suite passes a g++ build of the
+same arithmetic.
+
+The sums behind every output are added with floating-point atomics in the order of arrival: results vary in their last bits from
+run to run.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from caliscope_amd import _lib
+from caliscope_amd.exceptions import BackendError
+
+LOSSES = {"linear": 0, "huber": 1, "soft_l1": 2, "cauchy": 3, "arctan": 4}
+
+
+class CovDesc(C.Structure):
+    _fields_ = [("n_cams", C.c_int32), ("n_points", C.c_int64), ("n_obs", C.c_int64), ("cam_model", _lib.c_int32_p), ("cam_nparams", _lib.c_int32_p),
+                ("cam_const", _lib.c_double_p), ("cam_x", _lib.c_double_p), ("points", _lib.c_double_p), ("obs_cam", _lib.c_int32_p),
+                ("obs_pt", _lib.c_int32_p), ("obs_uv", _lib.c_double_p), ("loss", C.c_int32), ("f_scale", C.c_double)]
+
+
+class CovOut(C.Structure):
+    _fields_ = [("cam_cov", _lib.c_double_p), ("cam_cov_full", _lib.c_double_p), ("point_cov", _lib.c_double_p), ("sigma0_sq", _lib.c_double_p),
+                ("dof", _lib.c_int64_p), ("cost", _lib.c_double_p)]
+
+
+UNCERTAINTY_SIGNATURES = {
+    "cba_parameter_covariance": (C.c_int, [C.POINTER(CovDesc), C.c_int32, C.POINTER(CovOut)]),
+}
+
+
+@dataclass(frozen=True)
+class CovarianceResult:
+    """What one ``parameter_covariance`` call returns: ``cam_cov`` (n_cams, 9, 9) with the upper-left nparams x nparams used,
+    ``cam_cov_full`` (ncp, ncp), ``point_cov`` (n_points, 3, 3), ``cam_offsets`` (n_cams + 1) into the rows of ``cam_cov_full``."""
+
+    cam_cov: np.ndarray
+    cam_cov_full: np.ndarray
+    point_cov: np.ndarray
+    cam_offsets: np.ndarray
+    sigma0_sq: float
+    dof: int
+    cost: float
+
+
+def check_covariance_arguments(cam_model, cam_nparams, cam_const, cam_x, points, obs_cam, obs_pt, obs_uv, loss, f_scale):
+    """The arguments of a ``parameter_covariance`` call in the layout of ``cba_cov_desc``, as a dict (``ValueError`` for an unknown
+    loss, arrays of the wrong shape or mismatched lengths; the range of every index, the observation counts and the degrees of
+    freedom are the library's check)."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {sorted(LOSSES)}, got {loss!r}")
+    cam_model = np.ascontiguousarray(cam_model, dtype=np.int32).reshape(-1)
+    n_cams = len(cam_model)
+    cam_nparams = np.ascontiguousarray(cam_nparams, dtype=np.int32).reshape(-1)
+    cam_const = np.ascontiguousarray(cam_const, dtype=np.float64).reshape(-1, 12)
+    cam_x = np.ascontiguousarray(cam_x, dtype=np.float64).reshape(-1, 9)
+    if len(cam_nparams) != n_cams or len(cam_const) != n_cams or len(cam_x) != n_cams:
+        raise ValueError("parameter_covariance: cam_model, cam_nparams, cam_const and cam_x differ in length")
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    obs_cam = np.ascontiguousarray(obs_cam, dtype=np.int32).reshape(-1)
+    obs_pt = np.ascontiguousarray(obs_pt, dtype=np.int32).reshape(-1)
+    obs_uv = np.ascontiguousarray(obs_uv, dtype=np.float64).reshape(-1, 2)
+    if len(obs_pt) != len(obs_cam) or len(obs_uv) != len(obs_cam):
+        raise ValueError("parameter_covariance: obs_cam, obs_pt and obs_uv differ in length")
+    return dict(cam_model=cam_model, cam_nparams=cam_nparams, cam_const=cam_const, cam_x=cam_x, points=points, obs_cam=obs_cam, obs_pt=obs_pt,
+                obs_uv=obs_uv, loss=LOSSES[loss], f_scale=float(f_scale))
+
+
+def run_covariance_call(call, args: dict, what: str, last_error) -> CovarianceResult:
+    """Fill ``cba_cov_desc`` / ``cba_cov_out`` from checked arguments, run ``call(desc_ref, out_ref) -> code`` and collect the result
+    (shared by the device binding and the test harness: same structures, same error type and message)."""
+    n_cams, n_points = len(args["cam_model"]), len(args["points"])
+    widths = np.where((args["cam_nparams"] == 6) | (args["cam_nparams"] == 9), args["cam_nparams"], 0).astype(np.int64)  # (others: refused by the call)
+    offsets = np.concatenate([[0], np.cumsum(widths)])
+    ncp = int(offsets[-1])
+    cam_cov, cam_cov_full, point_cov = np.zeros((n_cams, 9, 9)), np.zeros((ncp, ncp)), np.zeros((n_points, 6))
+    sigma0_sq, dof, cost = np.zeros(1), np.zeros(1, dtype=np.int64), np.zeros(1)
+    desc = CovDesc(n_cams=n_cams, n_points=n_points, n_obs=len(args["obs_cam"]), cam_model=_lib.ptr(args["cam_model"]),
+                   cam_nparams=_lib.ptr(args["cam_nparams"]), cam_const=_lib.ptr(args["cam_const"]), cam_x=_lib.ptr(args["cam_x"]),
+                   points=_lib.ptr(args["points"]), obs_cam=_lib.ptr(args["obs_cam"]), obs_pt=_lib.ptr(args["obs_pt"]), obs_uv=_lib.ptr(args["obs_uv"]),
+                   loss=args["loss"], f_scale=args["f_scale"])
+    out = CovOut(cam_cov=_lib.ptr(cam_cov), cam_cov_full=_lib.ptr(cam_cov_full), point_cov=_lib.ptr(point_cov), sigma0_sq=_lib.ptr(sigma0_sq),
+                 dof=_lib.ptr(dof), cost=_lib.ptr(cost))
+    rc = call(C.byref(desc), C.byref(out))
+    if rc != 0:
+        raise BackendError(f"{what} failed (code {rc}): {last_error()}")
+    full = np.empty((n_points, 3, 3))
+    for (a, b), e in zip(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)), range(6)):
+        full[:, a, b] = full[:, b, a] = point_cov[:, e]
+    return CovarianceResult(cam_cov=cam_cov, cam_cov_full=cam_cov_full, point_cov=full, cam_offsets=offsets, sigma0_sq=float(sigma0_sq[0]),
+                            dof=int(dof[0]), cost=float(cost[0]))
+
+
+class DeviceUncertainty:
+    """The device call ``cba_parameter_covariance`` on ``device_id``."""
+
+    def __init__(self, device_id: int = 0):
+        self.device_id = device_id
+
+    def parameter_covariance(self, cam_model, cam_nparams, cam_const, cam_x, points, obs_cam, obs_pt, obs_uv, *, loss="linear",
+                             f_scale=1.0) -> CovarianceResult:
+        """Covariance of every camera's parameters and of every point at the given parameters; see ``include/caliscope/uncertainty.h``."""
+        args = check_covariance_arguments(cam_model, cam_nparams, cam_const, cam_x, points, obs_cam, obs_pt, obs_uv, loss, f_scale)
+        lib = _lib.bind(_lib.load(), UNCERTAINTY_SIGNATURES)
+        return run_covariance_call(lambda d, o: lib.cba_parameter_covariance(d, self.device_id, o), args, "cba_parameter_covariance",
+                                   lambda: _lib.last_error(lib))
+
+
+# ---- first-order propagation on the host ------------------------------------------------------------------------------------------------
+def _skew(v):
+    return np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+
+
+def rotation_and_left_jacobian(rvec):
+    """``R = exp([r]x)`` and the left Jacobian ``Jl`` of SO(3) at ``r`` (``exp([r + dr]x) ~ exp([Jl dr]x) exp([r]x)``), with the series
+    of ``cam_prepare`` below 1e-4."""
+    r = np.asarray(rvec, dtype=np.float64)
+    th2 = float(r @ r)
+    th = np.sqrt(th2)
+    if th < 1e-4:
+        sinc, a, b = 1.0 - th2 / 6.0 + th2 * th2 / 120.0, 0.5 - th2 / 24.0 + th2 * th2 / 720.0, 1.0 / 6.0 - th2 / 120.0 + th2 * th2 / 5040.0
+    else:
+        sinc, a, b = np.sin(th) / th, (1.0 - np.cos(th)) / th2, (th - np.sin(th)) / (th2 * th)
+    K = _skew(r)
+    K2 = K @ K
+    return np.eye(3) + sinc * K + a * K2, np.eye(3) + a * K + b * K2
+
+
+def centre_jacobian(rvec, tvec):
+    """d c / d (rvec, tvec) (3 x 6) of the camera centre ``c = -R(r)^T t``: a rotation increment ``w = Jl dr`` turns ``R^T`` into
+    ``R^T (I - [w]x)``, so ``dc = R^T [w]x t - R^T dt = -R^T [t]x Jl dr - R^T dt``."""
+    R, Jl = rotation_and_left_jacobian(rvec)
+    return np.hstack([-R.T @ _skew(np.asarray(tvec, dtype=np.float64)) @ Jl, -R.T])
+
+
+@dataclass(frozen=True)
+class CameraUncertainty:
+    """One camera of an :class:`UncertaintyReport`.  ``param_cov`` is nparams x nparams in the order rvec, tvec (, s, k1, k2);
+    ``centre_cov`` / ``centre_std`` are in world units; ``rotation_std_deg`` is the root of the summed variances of the three rotation
+    angles (``sqrt(trace(Jl S_rr Jl^T))``); ``scale_std``, ``k1_std``, ``k2_std`` are None unless the intrinsics were free (``scale_std``
+    is relative: the focal length's is ``scale_std * f``)."""
+
+    cam_id: int
+    param_cov: np.ndarray
+    centre_cov: np.ndarray
+    centre_std: np.ndarray
+    rotation_std_deg: float
+    scale_std: float | None = None
+    k1_std: float | None = None
+    k2_std: float | None = None
+
+    @property
+    def position_std(self) -> float:
+        """``sqrt(trace(centre_cov))``."""
+        return float(np.sqrt(np.trace(self.centre_cov)))
+
+
+@dataclass(frozen=True)
+class UncertaintyReport:
+    """Parameter uncertainty of a calibration in the inner-constraint gauge (the covariance of smallest trace among all gauges:
+    no camera or point is held fixed).  ``sigma0`` is the a-posteriori standard deviation of unit weight in residual units
+    (pixels / fx) under the loss of the call, ``dof`` the degrees of freedom 2 n_obs - n_params + 7.  ``point_cov[i]`` /
+    ``point_std[i]`` belong to row ``i`` of the volume's world points."""
+
+    sigma0: float
+    dof: int
+    cameras: dict
+    point_cov: np.ndarray
+    point_std: np.ndarray
+    cam_cov_full: np.ndarray
+    gauge: str = "inner"
+
+    def worst_cameras(self, n: int = 3) -> list:
+        """The ``n`` cameras with the largest centre uncertainty, worst first: ``(cam_id, position_std, rotation_std_deg)``."""
+        ranked = sorted(self.cameras.values(), key=lambda c: c.position_std, reverse=True)
+        return [(c.cam_id, c.position_std, c.rotation_std_deg) for c in ranked[: max(int(n), 0)]]
+
+
+def build_report(result: CovarianceResult, cam_ids, cam_nparams, cam_x) -> UncertaintyReport:
+    """The report of one call: the covariance blocks as returned, the centre and the rotation propagated to first order."""
+    cameras = {}
+    cam_x = np.asarray(cam_x, dtype=np.float64).reshape(-1, 9)
+    for i, cam_id in enumerate(cam_ids):
+        np_i = int(cam_nparams[i])
+        cov = result.cam_cov[i, :np_i, :np_i].copy()
+        Jc = centre_jacobian(cam_x[i, :3], cam_x[i, 3:6])
+        centre_cov = Jc @ cov[:6, :6] @ Jc.T
+        centre_cov = 0.5 * (centre_cov + centre_cov.T)
+        _, Jl = rotation_and_left_jacobian(cam_x[i, :3])
+        rot_var = float(np.trace(Jl @ cov[:3, :3] @ Jl.T))
+        free = {} if np_i == 6 else dict(zip(("scale_std", "k1_std", "k2_std"), (float(v) for v in np.sqrt(np.maximum(np.diag(cov)[6:9], 0.0)))))
+        cameras[int(cam_id)] = CameraUncertainty(cam_id=int(cam_id), param_cov=cov, centre_cov=centre_cov,
+                                                 centre_std=np.sqrt(np.maximum(np.diag(centre_cov), 0.0)),
+                                                 rotation_std_deg=float(np.degrees(np.sqrt(max(rot_var, 0.0)))), **free)
+    point_std = np.sqrt(np.maximum(np.einsum("ijj->ij", result.point_cov), 0.0))
+    return UncertaintyReport(sigma0=float(np.sqrt(max(result.sigma0_sq, 0.0))), dof=result.dof, cameras=cameras, point_cov=result.point_cov,
+                             point_std=point_std, cam_cov_full=result.cam_cov_full)
+
+
+__all__ = ["DeviceUncertainty", "CovarianceResult", "CameraUncertainty", "UncertaintyReport", "check_covariance_arguments", "run_covariance_call",
+           "build_report", "centre_jacobian", "rotation_and_left_jacobian", "UNCERTAINTY_SIGNATURES", "LOSSES"]
