@@ -15,6 +15,7 @@
 #include "ba_math.h"
 #include "trf_math.h"
 #include "wg_binding.h"
+#include "chol_schedule.h"
 
 namespace cba {
 
@@ -2366,6 +2367,15 @@ k_reg_finalize(TilePlan tp, const int* __restrict__ tile_wg_begin, const double*
 // trip of three 8 KB blocks.  History: (a) panel-solve + trailing-update kernels, 2 launches and ~28 us per panel;
 // (b) one launch with a left-looking update of depth k0 - its operands (up to 160 KB) all pass through the one CU
 // that runs the critical workgroup, 6-10 us per step at the memory-level parallelism of a single CU.
+//
+// The above is the PARENT schedule (EARLY = false, CBA_CHOL_EARLY=0: kept as the A/B reference).  The default (EARLY = true) takes stage 1 off
+// the critical workgroup's chain — a second global round trip, eight dependent MFMAs and a barrier per step: block (b, k) arrives complete,
+// because the panel workgroups b >= k + 2 of launch k - 1, which used to end after 2-3 us of its 9.5, applied P_k-2 AND P_k-1 to it there
+// (waves 4..7, idle before).  P_k-1 of that launch is formed from the workgroup's own L_b,k-1 (sh_X) and a private copy of L_k,k-1 =
+// U_k,k-1 X_k-1^T, recomputed with the instruction sequence of stage 2, with the K grouping of chol_rank_nb_tile, and subtracted after P_k-2:
+// every block takes the same sums in the same order, the factor is the parent's to the bit.  U_k,k-1 is read from a SIDE SLOT (behind the
+// inverses in Xinv), not from W, where the critical workgroup replaces it by L_k,k-1 during the same launch; its writer is the workgroup that
+// completed it one launch earlier.  Roles, blocks and counts of both schedules: chol_schedule.h (replayed by tests/native/chol_schedule_check.cpp).
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 constexpr int CHOL_THREADS = 512;   // 8 waves; 1024 threads measured slower (register budget halves, the panel solve spills)
 
@@ -2374,10 +2384,10 @@ constexpr int CHOL_THREADS = 512;   // 8 waves; 1024 threads measured slower (re
 // are clamped to the live ones (callers ignore the padding rows).  A lane loads 4 consecutive doubles of row
 // (lane & 15) of its tile per 16-deep slab; the K index of an MFMA is lane >> 4, and step t pairs the t-th of each
 // lane's 4 doubles: the same permutation of K on both operands, so the sum is unchanged.
-__device__ __forceinline__ void chol_rank_nb(const double* __restrict__ A, int rcA, const double* __restrict__ B, int rcB,
-                                             int ldw, double (*red)[16][17], int wv, int lane) {
-  if (wv >= 4) return;
-  const int ti = wv >> 1, tj = wv & 1, lr = lane & 15, kq = 4 * (lane >> 4);
+// the 16 x 16 tile `tile` (row half tile >> 1, column half tile & 1) of A B^T in the MFMA's accumulator layout: c[r] is row (lane >> 4) + 4 r,
+// column lane & 15 of the tile.  MFMA (s, h, e) sums the K indices 16 s + 4 (lane >> 4) + 2 h + e.
+__device__ __forceinline__ v4f64 chol_rank_nb_tile(const double* __restrict__ A, int rcA, const double* __restrict__ B, int rcB, int ldw, int tile, int lane) {
+  const int ti = tile >> 1, tj = tile & 1, lr = lane & 15, kq = 4 * (lane >> 4);
   const double* pa = A + (long)min(ti * 16 + lr, rcA - 1) * ldw + kq;
   const double* pb = B + (long)min(tj * 16 + lr, rcB - 1) * ldw + kq;
   double2 a[NB / 16][2], b[NB / 16][2];
@@ -2396,10 +2406,17 @@ __device__ __forceinline__ void chol_rank_nb(const double* __restrict__ A, int r
       c = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][h].x, b[s][h].x, c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][h].y, b[s][h].y, c, 0, 0, 0);
     }
+  return c;
+}
+__device__ __forceinline__ void chol_rank_nb(const double* __restrict__ A, int rcA, const double* __restrict__ B, int rcB,
+                                             int ldw, double (*red)[16][17], int wv, int lane) {
+  if (wv >= 4) return;
+  const v4f64 c = chol_rank_nb_tile(A, rcA, B, rcB, ldw, wv, lane);
 #pragma unroll
-  for (int r = 0; r < 4; ++r) red[wv][(lane >> 4) + 4 * r][lr] = c[r];
+  for (int r = 0; r < 4; ++r) red[wv][(lane >> 4) + 4 * r][lane & 15] = c[r];
 }
 
+template <bool EARLY>
 __global__ void __launch_bounds__(CHOL_THREADS)
 k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ flags, long long* __restrict__ trace, double* __restrict__ Xinv,
             double* __restrict__ Tinv = nullptr) {
@@ -2411,18 +2428,16 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
   const int nbk = (n + NB - 1) / NB;
   constexpr int EPT = NB * NB / CHOL_THREADS, ISTEP = CHOL_THREADS / NB;  // elements of a 32 x 32 block per thread
   const int j = tid & 31, i0 = tid >> 5;                  // (i0 + h * ISTEP, j), h < EPT
-  const int n_panel = (k < 0) ? 1 : nbk - k;
-  const int n_trailing = (k < 1) ? 0 : (nbk - k - 1) * (nbk - k) / 2;
+  const CholWork wk = chol_decode<EARLY>(nbk, k, (int)blockIdx.x, Tinv != nullptr);
 
-  if ((int)blockIdx.x >= n_panel + n_trailing) {
+  if (wk.role == CHOL_INVERSE) {
     // inverse role (Tinv != nullptr, k >= 1): T = L^-T is built next to the factorisation, off its critical path, so that the backward substitution
     // — a serial chain of one workgroup, 2.3 us per block — becomes one matrix-vector product (k_chol_apply).  With M = L^-1:
     //     M_ij = -X_i sum_{m=j}^{i-1} L_im M_mj   (i > j),   M_jj = X_j;    T_ji = M_ij^T is what is stored (upper block triangle).
     // The sum is accumulated right-looking: launch k adds the term m = k - 1 to every block (i >= k, j < k) — L_i,k-1 comes from the panel solves
     // of launch k - 1, T_j,k-1 was finalised there — and finalises row i = k with X_k (factored by launch k - 1's look-ahead):
     //     acc^T_ji += T_j,k-1 L_i,k-1^T ;      i == k:  T_jk = -acc^T_jk X_k^T.
-    const int t2 = blockIdx.x - n_panel - n_trailing;
-    const int bi = k + t2 / k, bj = t2 % k, m = k - 1;
+    const int bi = wk.bi, bj = wk.bj, m = k - 1;
     const int ri = bi * NB, rci = min(NB, n - ri), rj = bj * NB, rcj = min(NB, n - rj);
     double* Tb = Tinv + (long)rj * ldw + ri;  // block (bj, bi)
     double old[EPT];
@@ -2465,11 +2480,9 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
     return;
   }
 
-  if ((int)blockIdx.x >= n_panel) {
-    // trailing role: block (bi, bj), k + 1 <= bj < bi <= nbk, takes the update of panel k - 1
-    int t = blockIdx.x - n_panel, bj = k + 1;
-    while (t >= nbk - bj) { t -= nbk - bj; ++bj; }
-    const int bi = bj + 1 + t;
+  if (wk.role == CHOL_TRAILING) {
+    // trailing role: block (bi, bj), k + 1 (EARLY: k + 2) <= bj < bi <= nbk, takes the update of panel k - 1
+    const int bi = wk.bi, bj = wk.bj;
     const int ri = (bi < nbk) ? bi * NB : n, rci = (bi < nbk) ? min(NB, n - ri) : 1;
     const int rj = bj * NB, rcj = min(NB, n - rj);
     const int m0 = (k - 1) * NB;
@@ -2490,18 +2503,23 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
     return;
   }
 
-  const int b = k + 1 + blockIdx.x;                       // row block; nbk = the rhs row
+  const int b = wk.bi;                                    // row block; nbk = the rhs row
   const int rb = (b < nbk) ? b * NB : n;                  // first row
   const int rc = (b < nbk) ? min(NB, n - rb) : 1;         // live rows
   const bool has_diag = b < nbk;
   double* Wb = W + (long)rb * ldw;
   // optional phase stamps of the critical workgroup (b == k + 1), 100 MHz wall clock: CBA_CHOL_TRACE=1
-  const bool stamp = trace != nullptr && blockIdx.x == 0 && tid == 0;
+  const bool stamp = trace != nullptr && wk.critical && tid == 0;
 #define CHOL_STAMP(ph) do { if (stamp) trace[(k + 1) * 8 + (ph)] = wall_clock64(); } while (0)
   CHOL_STAMP(0);
 
   // everything this thread needs from global, in one round trip
   double d_ij[EPT], m_ij[EPT], l_ij[EPT];
+  // early update (EARLY, b >= k + 2): block (b, k + 1) of `rc1` live columns, one 16 x 16 tile per wave 4..7; side slot s at side + s NB NB
+  const bool early = EARLY && wk.early;
+  const int r1 = (k + 1) * NB, rc1 = min(NB, n - r1);
+  double* side = Xinv + (long)chol_side_slot(nbk, 0) * NB * NB;
+  const int eti = (wv >> 1) & 1, etj = wv & 1;
 #pragma unroll
   for (int h = 0; h < EPT; ++h) {
     const int i = i0 + h * ISTEP;
@@ -2520,18 +2538,46 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
       m_ij[h] = (i < rc && j < nbp) ? Wb[(long)i * ldw + k0 + j] : 0.0;
       l_ij[h] = Xinv[(long)k * NB * NB + i * NB + j];  // X_k = L_kk^-1 (identity-padded), written by the factorisation of D_k
     }
+    double u_ij[EPT];  // EARLY: U_k+1,k, complete, as the workgroup that completed it left it in side slot k (zero beyond its live rows)
+    v4f64 w_e = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (EARLY) {
+#pragma unroll
+      for (int h = 0; h < EPT; ++h) {
+        const int i = i0 + h * ISTEP;
+        u_ij[h] = (early && i < rc1) ? side[(long)k * NB * NB + i * NB + j] : 0.0;
+      }
+      if (early && wv >= 4) {  // W_b,k+1 - P_k-1(b, k + 1) from global operands: what the trailing workgroup of the parent schedule formed
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = eti * 16 + (lane >> 4) + 4 * r, jj = etj * 16 + (lane & 15);
+          w_e[r] = (i < rc && jj < rc1) ? Wb[(long)i * ldw + r1 + jj] : 0.0;
+        }
+        if (wk.upd_terms == 2) {
+          const v4f64 c = chol_rank_nb_tile(Wb + (k0 - NB), rc, W + (long)r1 * ldw + (k0 - NB), rc1, ldw, wv - 4, lane);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) w_e[r] -= c[r];
+        }
+      }
+    }
 
     CHOL_STAMP(1);
-    // 1. pending update of this block's panel columns by panel k - 1 (all earlier panels were applied by the trailing
-    // workgroups of earlier steps)
-    if (k >= 1) chol_rank_nb(Wb + (k0 - NB), rc, W + (long)k0 * ldw + (k0 - NB), nbp, ldw, sh_red, wv, lane);
-    __syncthreads();
-    CHOL_STAMP(2);
+    if constexpr (!EARLY) {
+      // 1. pending update of this block's panel columns by panel k - 1 (all earlier panels were applied by the trailing
+      // workgroups of earlier steps)
+      if (k >= 1) chol_rank_nb(Wb + (k0 - NB), rc, W + (long)k0 * ldw + (k0 - NB), nbp, ldw, sh_red, wv, lane);
+      __syncthreads();
+      CHOL_STAMP(2);
+    }
 #pragma unroll
     for (int h = 0; h < EPT; ++h) {
       const int i = i0 + h * ISTEP;
-      const double upd = (k >= 1) ? sh_red[(i >> 4) * 2 + (j >> 4)][i & 15][j & 15] : 0.0;
-      sh_U[i][j] = m_ij[h] - upd;
+      if constexpr (EARLY) {
+        sh_U[i][j] = m_ij[h];  // complete on arrival
+        if (early) sh_D[NB + i][j] = u_ij[h];  // (sh_D is the critical workgroup's: free here)
+      } else {
+        const double upd = (k >= 1) ? sh_red[(i >> 4) * 2 + (j >> 4)][i & 15][j & 15] : 0.0;
+        sh_U[i][j] = m_ij[h] - upd;
+      }
       sh_L[i][j] = l_ij[h];
     }
     __syncthreads();
@@ -2551,6 +2597,20 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
         const int i = ti * 16 + (lane >> 4) + 4 * r, jj = tj * 16 + (lane & 15);
         sh_X[i][jj] = (jj < nbp && i < rc) ? c[r] : 0.0;
       }
+    } else if (EARLY && early) {
+      // waves 4..7: the same product for the critical block, L_k+1,k = U_k+1,k X_k^T, into rows 0..NB-1 of sh_D (the critical workgroup's own
+      // result is not visible in this launch)
+      v4f64 c = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int t = 0; t < NB / 4; ++t) {
+        const int q = 4 * t + (lane >> 4);
+        c = __builtin_amdgcn_mfma_f64_16x16x4f64(sh_D[NB + eti * 16 + (lane & 15)][q], sh_L[etj * 16 + (lane & 15)][q], c, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = eti * 16 + (lane >> 4) + 4 * r, jj = etj * 16 + (lane & 15);
+        sh_D[i][jj] = (i < rc1) ? c[r] : 0.0;
+      }
     }
     __syncthreads();
 #pragma unroll
@@ -2559,6 +2619,26 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
       if (i < rc && j < nbp) Wb[(long)i * ldw + k0 + j] = sh_X[i][j];
     }
     CHOL_STAMP(4);
+    if (EARLY && early && wv >= 4) {
+      // early update, second term: P_k(b, k + 1) = L_bk L_k+1,k^T from LDS with the K grouping of chol_rank_nb_tile (MFMA (s, h, e) sums
+      // K = 16 s + 4 (lane >> 4) + 2 h + e), subtracted after P_k-1 as the panel workgroup of the parent's next launch did
+      v4f64 c = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int t = 0; t < NB / 4; ++t) {
+        const int q = 16 * (t >> 2) + 4 * (lane >> 4) + (t & 3);
+        c = __builtin_amdgcn_mfma_f64_16x16x4f64(sh_X[eti * 16 + (lane & 15)][q], sh_D[etj * 16 + (lane & 15)][q], c, 0, 0, 0);
+      }
+      double* next_u = (wk.side_write >= 0) ? side + (long)wk.side_write * NB * NB : nullptr;  // b == k + 2: the next critical block
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = eti * 16 + (lane >> 4) + 4 * r, jj = etj * 16 + (lane & 15);
+        if (i < rc && jj < rc1) {
+          const double v = w_e[r] - c[r];
+          Wb[(long)i * ldw + r1 + jj] = v;
+          if (next_u) next_u[i * NB + jj] = v;
+        }
+      }
+    }
     if (!has_diag) return;
     // 3. own diagonal block, rank-NB update
     if (wv < 4) {
@@ -2588,7 +2668,14 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
   // 4. look-ahead: the next panel's diagonal block
   __syncthreads();
   CHOL_STAMP(5);
-  if (tid < WAVE) chol_factor_block(sh_D, rc, flags);
+  if (tid < WAVE) {
+    chol_factor_block(sh_D, rc, flags);
+  } else if (EARLY && k < 0 && wk.side_write >= 0) {
+    // launch -1: the idle waves copy U_10 = W_10 (column block 0 takes no update) to side slot 0 for the early update of launch 0
+    const int live = min(NB, n - NB);  // rows of block 1
+    for (int e = tid - WAVE; e < NB * NB; e += CHOL_THREADS - WAVE)
+      if (e / NB < live) side[e] = W[(long)(NB + e / NB) * ldw + e % NB];
+  }
   __syncthreads();
   chol_factor_store(sh_D, rc, Wb + rb, ldw, Xinv + (long)(k + 1) * NB * NB, tid, CHOL_THREADS, Tinv ? Tinv + (long)rb * ldw + rb : nullptr);
   CHOL_STAMP(6);

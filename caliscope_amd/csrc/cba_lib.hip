@@ -115,8 +115,9 @@ struct cba_problem {
   int det_m = 0;  // cba_options.deterministic: tasks per thread of the fixed-order camera sums (3, 5, 8 or 16; 0: atomics)
   DetPlan det{nullptr, nullptr};
   double* tri = nullptr;   // packed upper triangle of Sacc + b for the exchange of a sharded solve
-  double* Xinv = nullptr;  // inverses of the diagonal blocks of the Cholesky factor, [blocks][NB][NB] (k_chol_step)
+  double* Xinv = nullptr;  // inverses of the diagonal blocks of the Cholesky factor and, behind them, the side slots of the early update: [chol_xinv_blocks][NB][NB] (k_chol_step)
   double* Tinv = nullptr;  // T = L^-T, built block by block next to the factorisation (inverse role of k_chol_step)
+  bool chol_early = true;  // k_chol_step<true>: the pending panel update off the critical chain (chol_schedule.h; CBA_CHOL_EARLY=0: the parent's schedule, A/B)
   bool fuse_reg_finalize = true;  // k_reg_finalize in the place of k_reg_reduce + k_schur_finalize where the route allows (CBA_REG_FINALIZE=0: off)
   double* scal = nullptr;  // device scalars
   double* xbuf = nullptr;  // staging of the one all-reduce per primitive (sharded solves)
@@ -1260,7 +1261,7 @@ static int alloc_solver_buffers(cba_problem* p) {
   TRYS(dev_alloc(p, &p->S, (size_t)ncp * ncp)); p->ldw = (ncp + 3) & ~3;
   if (p->want_chol_trace) TRYS(dev_alloc(p, &p->chol_trace, (size_t)((ncp + NB - 1) / NB + 2) * 8));
   TRYS(dev_alloc(p, &p->Lbuf, (size_t)(ncp + 1) * p->ldw));
-  TRYS(dev_alloc(p, &p->Xinv, (size_t)((ncp + NB - 1) / NB + 1) * NB * NB));
+  TRYS(dev_alloc(p, &p->Xinv, (size_t)chol_xinv_blocks((ncp + NB - 1) / NB) * NB * NB));
   TRYS(dev_zeros(p, &p->Tinv, (size_t)ncp * p->ldw));
   TRYS(dev_alloc(p, &p->rhs, (size_t)p->lay.ncp_pad));
   TRYS(dev_zeros(p, &p->scal, 64)); TRYS(dev_zeros(p, &p->flags, 8)); TRYS(dev_alloc(p, &p->xbuf, 128));
@@ -1315,6 +1316,7 @@ int cba_create(const cba_problem_desc* d, const cba_options* opt, cba_problem** 
   p->C = d->n_cams; p->P = d->n_points; p->N = d->n_obs;
   p->loss = d->loss; p->f_scale = d->f_scale;
   if (const char* e = std::getenv("CBA_REG_FINALIZE")) p->fuse_reg_finalize = e[0] != '0';
+  if (const char* e = std::getenv("CBA_CHOL_EARLY")) p->chol_early = e[0] != '0';
   if (const char* e = std::getenv("CBA_SPEC_SKIP")) p->spec_skip = e[0] != '0';
   if (const char* e = std::getenv("CBA_SMALL_SOLVE")) p->small_solve_on = e[0] != '0';
 #ifdef CBA_PROFILING
@@ -1750,26 +1752,32 @@ static int run_linearize(cba_problem* p, cba_linearization* out) {
 //
 // The factorisation launches take raw device pointers: cba_parameter_covariance (covariance_lib.hip, which declares the function again)
 // factors its own matrix with them.  W: (n + 1) x ldw work matrix (rows 0..n-1 the matrix, both triangles; row n a right-hand side), ldw a
-// multiple of 4; Xinv: (blocks + 1) NB x NB; Tinv: n x ldw, zero on entry outside what a call writes (the upper block triangle); flags[2] is
-// raised by a pivot that is not positive.  Not part of the C ABI.
+// multiple of 4; Xinv: chol_xinv_blocks(blocks) NB x NB (the inverses and the side slots of the early update); Tinv: n x ldw, zero on entry outside
+// what a call writes (the upper block triangle); flags[2] is raised by a pivot that is not positive; early: the schedule (chol_schedule.h, which also
+// holds the workgroup counts of a launch — the kernel decodes its role from the same functions).  Not part of the C ABI.
 namespace cba {
 __attribute__((visibility("hidden"))) void enqueue_chol_factor(double* W, int n, int ldw, int* flags, long long* trace, double* Xinv, double* Tinv,
-                                                               hipStream_t stream) {
+                                                               bool early, hipStream_t stream) {
   const int nbk = (n + NB - 1) / NB;
   for (int k = -1; k < nbk; ++k) {
-    // step k: panel k solved for the blocks below it (and the rhs row), D_k+1 factored; extra workgroups apply the
-    // rank-NB update of panel k - 1 to the blocks right of the current panel
-    const int n_panel = k < 0 ? 1 : nbk - k;
-    const int x = nbk - k - 1, n_trailing = k < 1 ? 0 : x * (x + 1) / 2;
-    const int n_inverse = (k >= 1) ? (nbk - k) * k : 0;  // blocks (i >= k, j < k) of T = L^-T take the term of panel k - 1
-    hipLaunchKernelGGL(k_chol_step, dim3(n_panel + n_trailing + n_inverse), dim3(CHOL_THREADS), 0, stream, W, n, ldw, k, flags, trace, Xinv, Tinv);
+    // step k: panel k solved for the blocks below it (and the rhs row), D_k+1 factored; extra workgroups apply the pending rank-NB updates to
+    // the blocks right of the current panel and build T
+    if (early)
+      hipLaunchKernelGGL(k_chol_step<true>, dim3(chol_counts<true>(nbk, k, Tinv != nullptr).total()), dim3(CHOL_THREADS), 0, stream, W, n, ldw, k, flags, trace, Xinv, Tinv);
+    else
+      hipLaunchKernelGGL(k_chol_step<false>, dim3(chol_counts<false>(nbk, k, Tinv != nullptr).total()), dim3(CHOL_THREADS), 0, stream, W, n, ldw, k, flags, trace, Xinv, Tinv);
   }
+}
+// CBA_CHOL_EARLY=0 for callers without a handle (cba_parameter_covariance), read per call
+__attribute__((visibility("hidden"))) bool chol_early_from_env() {
+  const char* e = std::getenv("CBA_CHOL_EARLY");
+  return !(e && e[0] == '0');
 }
 }  // namespace cba
 
 static int enqueue_cholesky(cba_problem* p) {
   const int n = p->ncp, nbk = (n + NB - 1) / NB;
-  enqueue_chol_factor(p->Lbuf, n, p->ldw, p->flags, p->chol_trace, p->Xinv, p->Tinv, p->stream);
+  enqueue_chol_factor(p->Lbuf, n, p->ldw, p->flags, p->chol_trace, p->Xinv, p->Tinv, p->chol_early, p->stream);
   hipLaunchKernelGGL(k_chol_apply, dim3(nbk), dim3(APPLY_THREADS), (size_t)n * 8, p->stream, (const double*)p->Tinv, (const double*)p->Lbuf, n, p->ldw, p->s);
   return CBA_OK;
 }
@@ -1786,8 +1794,12 @@ static int run_cholesky(cba_problem* p) {
     HIPCHK(hipStreamSynchronize(p->stream));
     for (int s = 0; s <= nbk; ++s) {
       fprintf(stderr, "chol step %2d:", s - 1);
+      int last = 0;  // a phase is timed from the last stamp in front of it: the early schedule has no ph2 (the pending panel update left the chain)
       for (int ph = 1; ph < 7; ++ph)
-        if (h[s * 8 + ph] && h[s * 8 + ph - 1]) fprintf(stderr, " ph%d %6.2f us", ph, (h[s * 8 + ph] - h[s * 8 + ph - 1]) * 0.01); else if (h[s * 8 + ph]) fprintf(stderr, " ph%d (%6.2f)", ph, (h[s * 8 + ph] - h[s * 8]) * 0.01);
+        if (h[s * 8 + ph]) {
+          if (h[s * 8 + last]) fprintf(stderr, " ph%d %6.2f us", ph, (h[s * 8 + ph] - h[s * 8 + last]) * 0.01); else fprintf(stderr, " ph%d (      )", ph);
+          last = ph;
+        }
       if (s < nbk && h[(s + 1) * 8] && h[s * 8]) fprintf(stderr, "  | to next step start %6.2f us", (h[(s + 1) * 8] - h[s * 8]) * 0.01);
       fprintf(stderr, "\n");
     }

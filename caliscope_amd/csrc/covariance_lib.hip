@@ -21,23 +21,32 @@
 //   k_unc_point_cov  one wave per point: sigma0^2 (V^-1 + Z F Z^T + sum_ab Y_a^T C_ab Y_b + sum_a sym(Y_a^T E_a Z^T)), the k^2 pairs and
 //                    the k rank-7 terms spread over the lanes, 3 x 3 sums by shuffles.
 //
+// CBA_DETERMINISTIC=1 (read per call, as the solver's handles read it when they are made): the sums the kernels above form with FP64 atomics —
+// U, the cost, B, the Schur complement and D — are formed in a FIXED order instead, so that two calls return the same bits: the three kernels
+// skip their atomics and k_unc_cam_sums (one wave per camera: U and the camera's share of the cost), k_unc_rows (one workgroup per camera: its
+// rows of B and of the Schur complement, one thread per entry, points in order) and k_unc_fixed_sums (D and the cost from per-wave rows) take
+// their place.  Every entry has ONE owner that adds in observation order; slower (each camera scans all observations), and not the default.
+//
 // Null stream throughout.  Scaling by sigma0^2 has no kernel of its own: the point kernel applies it, the camera blocks take it on the
 // host where they are copied into the caller's arrays.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "ba_math.h"
 #include "covariance_math.h"
 #include "device_call.h"
+#include "chol_schedule.h"
 
 namespace cba {
 // cba_lib.hip: the launches of the blocked Cholesky on raw device pointers
 __attribute__((visibility("hidden"))) void enqueue_chol_factor(double* W, int n, int ldw, int* flags, long long* trace, double* Xinv, double* Tinv,
-                                                               hipStream_t stream);
+                                                               bool early, hipStream_t stream);
+__attribute__((visibility("hidden"))) bool chol_early_from_env();
 }  // namespace cba
 
 using namespace cba;
@@ -81,7 +90,8 @@ k_unc_cam(int32_t n_cams, const int32_t* __restrict__ cam_model, const int32_t* 
 __global__ void __launch_bounds__(COV_BLOCK)
 k_unc_obs(int64_t n_obs, const int64_t* __restrict__ order, const int32_t* __restrict__ obs_cam, const int32_t* __restrict__ obs_pt,
           const double* __restrict__ obs_uv, const double* __restrict__ tab, const double* __restrict__ points, int loss, double f_scale,
-          double* __restrict__ Wblk, double* __restrict__ Vobs, int32_t* __restrict__ cam_sorted, double* __restrict__ U, double* __restrict__ cost) {
+          double* __restrict__ Wblk, double* __restrict__ Vobs, int32_t* __restrict__ cam_sorted, double* __restrict__ U, double* __restrict__ cost,
+          bool fixed_order) {
   const int64_t i = (int64_t)blockIdx.x * COV_BLOCK + threadIdx.x;
   double rho = 0.0;
   if (i < n_obs) {
@@ -99,6 +109,7 @@ k_unc_obs(int64_t n_obs, const int64_t* __restrict__ order, const int32_t* __res
 #pragma unroll
     for (int e = 0; e < 6; ++e) Vobs[i * 6 + e] = Vo[e];
     cam_sorted[i] = cam;
+    if (fixed_order) return;  // (k_unc_cam_sums forms U and the cost)
     const bool nine = c.nparams == 9.0;
     double* Uc = U + (int64_t)cam * (MAX_NC * MAX_NC);
 #pragma unroll
@@ -107,14 +118,53 @@ k_unc_obs(int64_t n_obs, const int64_t* __restrict__ order, const int32_t* __res
       for (int q = r; q < MAX_NC; ++q)
         if (q < 6 || nine) atomicAdd(&Uc[r * MAX_NC + q], A[0][r] * A[0][q] + A[1][r] * A[1][q]);
   }
+  if (fixed_order) return;
   rho = wave_sum(rho);
   if ((threadIdx.x & 63) == 0 && rho != 0.0) atomicAdd(cost, 0.5 * rho);
+}
+
+// fixed order: one wave per camera.  Lane l takes the observations i = l, l + 64, .. (point order) of its camera, the lanes' sums meet in wave_sum's tree.
+__global__ void __launch_bounds__(64)
+k_unc_cam_sums(int64_t n_obs, const int64_t* __restrict__ order, const int32_t* __restrict__ obs_pt, const double* __restrict__ obs_uv,
+               const double* __restrict__ tab, const double* __restrict__ points, int loss, double f_scale, const int32_t* __restrict__ cam_sorted,
+               double* __restrict__ U, double* __restrict__ cam_cost) {
+  const int32_t cam = blockIdx.x;
+  const CamTab& c = reinterpret_cast<const CamTab*>(tab)[cam];
+  const bool nine = c.nparams == 9.0;
+  double acc[MAX_NC * (MAX_NC + 1) / 2], rho = 0.0;
+#pragma unroll
+  for (int e = 0; e < MAX_NC * (MAX_NC + 1) / 2; ++e) acc[e] = 0.0;
+  for (int64_t i = threadIdx.x; i < n_obs; i += 64) {
+    if (cam_sorted[i] != cam) continue;
+    const int64_t o = order[i], p = obs_pt[o];
+    const double X[3] = {points[3 * p], points[3 * p + 1], points[3 * p + 2]};
+    const double uv[2] = {obs_uv[2 * o], obs_uv[2 * o + 1]};
+    double A[2][MAX_NC], B[2][3];
+    rho += cov_obs_jacobian(c, X, uv, loss, f_scale, A, B);
+    int e = 0;
+#pragma unroll
+    for (int r = 0; r < MAX_NC; ++r)
+#pragma unroll
+      for (int q = r; q < MAX_NC; ++q) acc[e++] += A[0][r] * A[0][q] + A[1][r] * A[1][q];
+  }
+  double* Uc = U + (int64_t)cam * (MAX_NC * MAX_NC);
+  int e = 0;
+#pragma unroll
+  for (int r = 0; r < MAX_NC; ++r)
+#pragma unroll
+    for (int q = r; q < MAX_NC; ++q) {
+      const double v = wave_sum(acc[e++]);
+      if (threadIdx.x == 0 && (q < 6 || nine)) Uc[r * MAX_NC + q] += v;  // (U is zero on entry; this wave is the entry's only writer)
+    }
+  rho = wave_sum(rho);
+  if (threadIdx.x == 0) cam_cost[cam] = 0.5 * rho;
 }
 
 __global__ void __launch_bounds__(COV_POINT_THREADS)
 k_unc_point(const int64_t* __restrict__ pt_start, const int32_t* __restrict__ cam_sorted, const int32_t* __restrict__ cam_off, int32_t ncp,
             const double* __restrict__ points, const double* __restrict__ Wblk, const double* __restrict__ Vobs, double* __restrict__ Y,
-            double* __restrict__ Vinv, double* __restrict__ Zbuf, double* __restrict__ B, double* __restrict__ Sacc, int* __restrict__ flags) {
+            double* __restrict__ Vinv, double* __restrict__ Zbuf, double* __restrict__ B, double* __restrict__ Sacc, int* __restrict__ flags,
+            bool fixed_order) {
   __shared__ double sh_vi[9], sh_z[3 * COV_GAUGE];
   const int64_t p = blockIdx.x;
   const int t = threadIdx.x;
@@ -153,6 +203,7 @@ k_unc_point(const int64_t* __restrict__ pt_start, const int32_t* __restrict__ ca
     Y[(s + a) * WB + e] = w[0] * sh_vi[q] + w[1] * sh_vi[3 + q] + w[2] * sh_vi[6 + q];
   }
   __syncthreads();  // (Y of this point is read below by other lanes)
+  if (fixed_order) return;  // (k_unc_rows forms B and the Schur complement from Y, Z and the W blocks)
   for (int64_t it = t; it < k * (MAX_NC * COV_GAUGE); it += COV_POINT_THREADS) {  // B -= W_a Z
     const int64_t a = it / (MAX_NC * COV_GAUGE);
     const int e = (int)(it % (MAX_NC * COV_GAUGE)), r = e / COV_GAUGE, j = e % COV_GAUGE;
@@ -175,8 +226,46 @@ k_unc_point(const int64_t* __restrict__ pt_start, const int32_t* __restrict__ ca
   }
 }
 
+// fixed order: one workgroup per camera, which owns the camera's rows of B and of the Schur complement.  Thread e < 63 owns entry (r, j) of the
+// B rows, thread 64 + e, e < 81, the entries (r, off_b + c) of the Schur rows for every camera b; each walks the points in order and adds the
+// terms of its entries one after the other, so no entry has two writers and a repeated (camera, point) pair simply adds twice.
+constexpr int COV_ROWS_THREADS = 192;
+__global__ void __launch_bounds__(COV_ROWS_THREADS)
+k_unc_rows(int64_t n_points, const int64_t* __restrict__ pt_start, const int32_t* __restrict__ cam_sorted, const int32_t* __restrict__ cam_off, int32_t ncp,
+           const double* __restrict__ Wblk, const double* __restrict__ Y, const double* __restrict__ Zbuf, double* __restrict__ B, double* __restrict__ Sacc) {
+  constexpr int WB = 3 * MAX_NC;
+  const int32_t cam = blockIdx.x, off_a = cam_off[cam], np_a = cam_off[cam + 1] - off_a;
+  const int t = threadIdx.x;
+  const bool b_role = t < MAX_NC * COV_GAUGE, s_role = t >= 64 && t < 64 + MAX_NC * MAX_NC;
+  const int e = b_role ? t : t - 64;
+  const int r = b_role ? e / COV_GAUGE : e / MAX_NC, c = b_role ? e % COV_GAUGE : e % MAX_NC;
+  if (!(b_role || s_role) || r >= np_a) return;
+  for (int64_t p = 0; p < n_points; ++p) {
+    const int64_t s = pt_start[p], k = pt_start[p + 1] - s;
+    for (int64_t a = 0; a < k; ++a) {
+      if (cam_sorted[s + a] != cam) continue;
+      if (b_role) {
+        const double* w = Wblk + (s + a) * WB + 3 * r;
+        const double* z = Zbuf + p * (3 * COV_GAUGE);
+        B[(int64_t)(off_a + r) * COV_GAUGE + c] += -(w[0] * z[c] + w[1] * z[COV_GAUGE + c] + w[2] * z[2 * COV_GAUGE + c]);
+        continue;
+      }
+      const double* y = Y + (s + a) * WB + 3 * r;
+      for (int64_t b = 0; b < k; ++b) {
+        const int32_t cam_b = cam_sorted[s + b], off_b = cam_off[cam_b], np_b = cam_off[cam_b + 1] - off_b;
+        const int32_t row = off_a + r, col = off_b + c;
+        if (c >= np_b || row > col) continue;
+        const double* w = Wblk + (s + b) * WB + 3 * c;
+        Sacc[(int64_t)row * ncp + col] += -(y[0] * w[0] + y[1] * w[1] + y[2] * w[2]);
+      }
+    }
+  }
+}
+
+// D: with `rows` != nullptr (fixed order) every wave leaves its 28 sums as a row of `rows` for k_unc_fixed_sums instead of adding them to D
+constexpr int COV_D_BLOCKS = 256;
 __global__ void __launch_bounds__(COV_BLOCK)
-k_unc_d(int64_t n_points, const double* __restrict__ points, const double* __restrict__ Zbuf, double* __restrict__ D) {
+k_unc_d(int64_t n_points, const double* __restrict__ points, const double* __restrict__ Zbuf, double* __restrict__ D, double* __restrict__ rows) {
   double acc[COV_GAUGE * (COV_GAUGE + 1) / 2];
 #pragma unroll
   for (int e = 0; e < COV_GAUGE * (COV_GAUGE + 1) / 2; ++e) acc[e] = 0.0;
@@ -198,9 +287,29 @@ k_unc_d(int64_t n_points, const double* __restrict__ points, const double* __res
   for (int j = 0; j < COV_GAUGE; ++j)
 #pragma unroll
     for (int m = j; m < COV_GAUGE; ++m) {
-      const double v = wave_sum(acc[e++]);
-      if ((threadIdx.x & 63) == 0) atomicAdd(&D[j * COV_GAUGE + m], v);
+      const double v = wave_sum(acc[e]);
+      if ((threadIdx.x & 63) == 0) {
+        if (rows) rows[((int64_t)blockIdx.x * (COV_BLOCK / 64) + (threadIdx.x >> 6)) * 28 + e] = v; else atomicAdd(&D[j * COV_GAUGE + m], v);
+      }
+      ++e;
     }
+}
+
+// fixed order: thread e < 28 adds the waves' rows of D in order, thread 28 the cameras' shares of the cost
+__global__ void __launch_bounds__(64)
+k_unc_fixed_sums(const double* __restrict__ rows, int n_rows, const double* __restrict__ cam_cost, int32_t n_cams, double* __restrict__ D, double* __restrict__ cost) {
+  const int e = threadIdx.x;
+  if (e < 28) {
+    double v = 0.0;
+    for (int i = 0; i < n_rows; ++i) v += rows[(int64_t)i * 28 + e];
+    int j = 0, rest = e;
+    while (rest >= COV_GAUGE - j) { rest -= COV_GAUGE - j; ++j; }
+    D[j * COV_GAUGE + j + rest] = v;
+  } else if (e == 28) {
+    double v = 0.0;
+    for (int32_t c = 0; c < n_cams; ++c) v += cam_cost[c];
+    *cost = v;
+  }
 }
 
 // entry (row <= col) of St = U + Schur + B D^-1 B^T
@@ -404,7 +513,13 @@ extern "C" int cba_parameter_covariance(const cba_cov_desc* d, int32_t device, c
   double* dB = buf.make<double>(ncp, COV_GAUGE);
   double* dscale = buf.make<double>(ncp);
   double* dC = buf.make<double>(ncp, ncp);
-  double* dXinv = buf.make<double>(nbk + 1, NB * NB);
+  const char* det_env = std::getenv("CBA_DETERMINISTIC");
+  const bool fixed_order = det_env && det_env[0] != '\0' && !(det_env[0] == '0' && det_env[1] == '\0');  // (as caliscope_amd/engine_cache.py reads it)
+  const int64_t d_blocks_all = (n_points + COV_BLOCK - 1) / COV_BLOCK;
+  const int d_grid = (int)(d_blocks_all < COV_D_BLOCKS ? d_blocks_all : COV_D_BLOCKS), d_rows = d_grid * (COV_BLOCK / 64);
+  double* dD_rows = fixed_order ? buf.make<double>(d_rows, 28) : nullptr;
+  double* dcam_cost = fixed_order ? buf.make<double>(n_cams) : nullptr;
+  double* dXinv = buf.make<double>(chol_xinv_blocks(nbk), NB * NB);  // the inverses of the diagonal blocks and the side slots of the early update
   // zeroed in one block: the work matrix [ldw + 1][ldw] and T [ldw][ldw] (first: their rows are read sixteen bytes at a time), U [n_cams][81],
   // Schur [ncp][ncp], D [49], cost [1], flags
   const size_t n_U = (size_t)n_cams * MAX_NC * MAX_NC, n_S = (size_t)ncp * ncp, n_W = ((size_t)ldw + 1) * ldw, n_T = (size_t)ldw * ldw;
@@ -424,11 +539,18 @@ extern "C" int cba_parameter_covariance(const cba_cov_desc* d, int32_t device, c
   const auto blocks = [](int64_t n) { return dim3((unsigned)((n + COV_BLOCK - 1) / COV_BLOCK)); };
   hipLaunchKernelGGL(k_unc_cam, blocks(n_cams), dim3(COV_BLOCK), 0, 0, n_cams, dmodel, dcam_off, dconst, dcam_x, dtab, dB);
   hipLaunchKernelGGL(k_unc_obs, blocks(n_obs), dim3(COV_BLOCK), 0, 0, n_obs, dorder, dobs_cam, dobs_pt, dobs_uv, (const double*)dtab, dpoints, (int)d->loss,
-                     d->f_scale, dWblk, dVobs, dcam_sorted, dU, dcost);
+                     d->f_scale, dWblk, dVobs, dcam_sorted, dU, dcost, fixed_order);
+  if (fixed_order)
+    hipLaunchKernelGGL(k_unc_cam_sums, dim3((unsigned)n_cams), dim3(64), 0, 0, n_obs, dorder, dobs_pt, dobs_uv, (const double*)dtab, dpoints, (int)d->loss, d->f_scale,
+                       (const int32_t*)dcam_sorted, dU, dcam_cost);
   hipLaunchKernelGGL(k_unc_point, dim3((unsigned)n_points), dim3(COV_POINT_THREADS), 0, 0, dpt_start, (const int32_t*)dcam_sorted, dcam_off, ncp, dpoints,
-                     (const double*)dWblk, (const double*)dVobs, dY, dVinv, dZ, dB, dSacc, dflags);
-  const int64_t d_blocks = (n_points + COV_BLOCK - 1) / COV_BLOCK;
-  hipLaunchKernelGGL(k_unc_d, dim3((unsigned)(d_blocks < 256 ? d_blocks : 256)), dim3(COV_BLOCK), 0, 0, n_points, dpoints, (const double*)dZ, dD);
+                     (const double*)dWblk, (const double*)dVobs, dY, dVinv, dZ, dB, dSacc, dflags, fixed_order);
+  if (fixed_order)  // (a point whose observations do not determine it has raised F_POINT: the call returns below before anything reads these sums)
+    hipLaunchKernelGGL(k_unc_rows, dim3((unsigned)n_cams), dim3(COV_ROWS_THREADS), 0, 0, n_points, dpt_start, (const int32_t*)dcam_sorted, dcam_off, ncp,
+                       (const double*)dWblk, (const double*)dY, (const double*)dZ, dB, dSacc);
+  hipLaunchKernelGGL(k_unc_d, dim3((unsigned)d_grid), dim3(COV_BLOCK), 0, 0, n_points, dpoints, (const double*)dZ, dD, dD_rows);
+  if (fixed_order)
+    hipLaunchKernelGGL(k_unc_fixed_sums, dim3(1), dim3(64), 0, 0, (const double*)dD_rows, d_rows, (const double*)dcam_cost, n_cams, dD, dcost);
   buf.check(hipGetLastError());
   std::vector<double> D(COV_GAUGE * COV_GAUGE + 1);  // D and the cost behind it
   std::vector<int> flags(N_FLAGS, 0);
@@ -449,7 +571,7 @@ extern "C" int cba_parameter_covariance(const cba_cov_desc* d, int32_t device, c
 
   hipLaunchKernelGGL(k_unc_assemble, blocks((int64_t)ncp * ncp), dim3(COV_BLOCK), 0, 0, ncp, ldw, (const double*)dU, (const double*)dSacc, (const double*)dB, dDinv,
                      dparam_cam, dparam_loc, dW, dscale, dflags);
-  enqueue_chol_factor(dW, ncp, ldw, dflags, nullptr, dXinv, dT, 0);
+  enqueue_chol_factor(dW, ncp, ldw, dflags, nullptr, dXinv, dT, chol_early_from_env(), 0);
   hipLaunchKernelGGL(k_unc_pivots, blocks(ncp), dim3(COV_BLOCK), 0, 0, (int)ncp, ldw, (const double*)dW, dflags);
   hipLaunchKernelGGL(k_unc_ttt, dim3((unsigned)nbk, (unsigned)nbk), dim3(256), 0, 0, (int)ncp, ldw, (const double*)dT, (const double*)dscale, dC);
   buf.check(hipGetLastError());
