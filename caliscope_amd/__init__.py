@@ -1,9 +1,10 @@
 """caliscope_amd: multi-camera calibration and reconstruction on the MI355X.  The sub-modules are imported by name; the two entry points
-of the per-recording stage and the uncertainty report are also reachable from the package (loaded on first use, so that importing the
+of the per-recording stage, the uncertainty report and the reliability report are also reachable from the package (loaded on first use, so that importing the
 package stays as cheap)."""
 
 _EXPORTS = {"reconstruct_trajectories": "caliscope_amd.reconstruction", "reconstruct_xyz": "caliscope_amd.reconstruction",
-            "UncertaintyReport": "caliscope_amd.uncertainty", "DeviceUncertainty": "caliscope_amd.uncertainty"}
+            "UncertaintyReport": "caliscope_amd.uncertainty", "DeviceUncertainty": "caliscope_amd.uncertainty",
+            "ReliabilityReport": "caliscope_amd.reliability", "DeviceReliability": "caliscope_amd.reliability"}
 
 __all__ = sorted(_EXPORTS)
 

@@ -669,34 +669,82 @@ class CaptureVolume:
         points and fix the scale, which this version does not model.  ``_solver`` replaces the device call (tests)."""
         from caliscope_amd.uncertainty import DeviceUncertainty, build_report
 
+        par, args, used, _, _ = self._free_network_arguments("parameter_uncertainty", "covariance", refine_intrinsics)
+        backend = _solver or DeviceUncertainty()
+        result = backend.parameter_covariance(*args, loss=loss, f_scale=self.pixel_f_scale() if f_scale is None else float(f_scale))
+        if not used.all():  # back to the rows of world_points
+            point_cov = np.full((len(self.world_points), 3, 3), np.nan)
+            point_cov[used] = result.point_cov
+            object.__setattr__(result, "point_cov", point_cov)
+        return build_report(result, [blk.cam_id for blk in par.blocks], args[1], args[3])
+
+    def _free_network_arguments(self, method: str, what: str, refine_intrinsics: bool):
+        """What ``parameter_uncertainty`` and ``observation_reliability`` hand their device call: ``(parameterisation, the eight
+        positional arguments, used world points (mask), image-point row of every observation of the call, its world-point row)``.
+        Matched observations of world points with at least two of them; a volume with constraints raises ``CalibrationError``."""
         if self.constraints is not None:
-            raise CalibrationError("parameter_uncertainty handles volumes without constraints: distance constraints couple points and fix the "
-                                   "scale of the gauge.  Build the volume without its ConstraintSet to get the reprojection-only covariance.")
+            raise CalibrationError(f"{method} handles volumes without constraints: distance constraints couple points and fix the "
+                                   f"scale of the gauge.  Build the volume without its ConstraintSet to get the reprojection-only {what}.")
         mask, camera_indices, image_coords, obj_indices = self._matched_arrays()
         if int(mask.sum()) == 0:
-            raise ValueError("No matched observations for the parameter covariance")
+            raise ValueError(f"No matched observations for {method}")
         par = BundleParameterization.from_camera_array(self.camera_array, n_points=len(self.world_points), refine_intrinsics=refine_intrinsics)
         tabs = par.device_tables()
         x = par.pack(self.camera_array, self.world_points.points)
         cam_x = np.zeros((len(par.blocks), 9))
         for i, (blk, off) in enumerate(zip(par.blocks, par.camera_param_offsets)):
             cam_x[i, : blk.n_params] = x[off : off + blk.n_params]
-        n_world = len(self.world_points)
-        views = np.bincount(obj_indices, minlength=n_world)
+        views = np.bincount(obj_indices, minlength=len(self.world_points))
         used = views >= 2
         if not used.any():
             raise ValueError("No world point has two matched observations")
         new_row = np.cumsum(used, dtype=np.int64) - 1
         keep = used[obj_indices]
-        backend = _solver or DeviceUncertainty()
-        result = backend.parameter_covariance(tabs["cam_model"], tabs["cam_n_params"], tabs["cam_const"], cam_x, self.world_points.points[used],
-                                              camera_indices[keep], new_row[obj_indices[keep]].astype(np.int32), image_coords[keep], loss=loss,
-                                              f_scale=self.pixel_f_scale() if f_scale is None else float(f_scale))
-        if not used.all():  # back to the rows of world_points
-            point_cov = np.full((n_world, 3, 3), np.nan)
-            point_cov[used] = result.point_cov
-            object.__setattr__(result, "point_cov", point_cov)
-        return build_report(result, [blk.cam_id for blk in par.blocks], tabs["cam_n_params"], cam_x)
+        args = (tabs["cam_model"], tabs["cam_n_params"], tabs["cam_const"], cam_x, self.world_points.points[used], camera_indices[keep],
+                new_row[obj_indices[keep]].astype(np.int32), image_coords[keep])
+        return par, args, used, np.flatnonzero(mask)[keep], obj_indices[keep]
+
+    # -- reliability of the observations (caliscope_amd/reliability.py; the reference has a percentile cut only) ---------------------
+    def observation_reliability(self, *, refine_intrinsics: bool = False, loss: str = "linear", f_scale: float | None = None, delta0: float = 4.13,
+                                _solver=None):
+        """How strongly the other observations control every matched observation at the volume's current parameters (meaningful after
+        ``optimize()`` with the same ``refine_intrinsics`` and ``loss``), and how far its residual is from what the adjustment allows: a
+        :class:`~caliscope_amd.reliability.ReliabilityReport` from one device call, aligned to the rows of ``image_points``.  Rows that
+        take no part (unmatched, or on a world point with fewer than two matched observations) are NaN.  ``f_scale`` is in residual
+        units and defaults to ``pixel_f_scale()``; ``delta0`` is the non-centrality behind ``mdb_px`` (4.13: Baarda's value for a
+        significance of 0.1 % and a power of 80 %, a convention).  Reprojection rows only: a volume with constraints raises
+        ``CalibrationError``.  Under a robust loss ``w`` is an approximation.  ``_solver`` replaces the device call (tests)."""
+        from caliscope_amd.reliability import DeviceReliability, build_report
+
+        par, args, _, rows, obs_world = self._free_network_arguments("observation_reliability", "reliability report", refine_intrinsics)
+        backend = _solver or DeviceReliability()
+        result = backend.observation_reliability(*args, loss=loss, f_scale=self.pixel_f_scale() if f_scale is None else float(f_scale))
+        return build_report(result, rows, len(self.image_points._df), args[2][args[5], 0], [blk.cam_id for blk in par.blocks], args[5], obs_world,
+                            len(self.world_points), delta0=delta0)
+
+    def filter_by_w_test(self, alpha: float = 0.001, *, refine_intrinsics: bool = False, loss: str = "linear", f_scale: float | None = None,
+                         _solver=None) -> "CaptureVolume":
+        """One pass of data snooping (Baarda's w-test): the observations whose standardised residual contradicts the adjustment at the
+        two-sided significance ``alpha`` go, judged by ``observation_reliability()`` at the volume's current parameters.  A blunder
+        smears onto the other observations of its point, so per world point at most ONE observation is removed: the one with the
+        largest ``|w|``, if that exceeds the critical value, and never if the point would be left with fewer than two matched views.
+        Unlike ``filter_outliers`` nothing goes from a volume in which nothing is wrong beyond the share ``alpha`` predicts.  The
+        volume is assembled from the row mask as ``filter_outliers`` assembles it (unmatched rows go, world points left without an
+        observation are pruned, ``optimization_status`` is None).  For the next pass re-optimise the result and call again."""
+        from caliscope_amd.reliability import critical_value, snooping_mask
+
+        report = self.observation_reliability(refine_intrinsics=refine_intrinsics, loss=loss, f_scale=f_scale, _solver=_solver)
+        mask, _, _, obj_indices = self._matched_arrays()
+        views = np.bincount(obj_indices, minlength=len(self.world_points))
+        keep = snooping_mask(report.max_abs_w[mask], obj_indices, views, critical_value(alpha))
+        keep_rows = np.zeros(len(mask), dtype=bool)
+        keep_rows[np.flatnonzero(mask)[keep]] = True
+        obj = self.img_to_obj_map[keep_rows]
+        seen = np.zeros(len(self.world_points), dtype=bool)
+        seen[obj] = True
+        new_row = np.cumsum(seen, dtype=np.int64) - 1
+        return CaptureVolume(self.camera_array, self.image_points.take(keep_rows), self.world_points.take(seen), self.constraints,
+                             _known_map=new_row[obj].astype(np.int32))
 
     # -- scale accuracy (reference :755-831) ---------------------------------------------------------------
     def _scale_groups(self):

@@ -39,6 +39,7 @@
 
 #include "ba_math.h"
 #include "covariance_math.h"
+#include "covariance_pipeline.h"
 #include "device_call.h"
 #include "chol_schedule.h"
 
@@ -470,13 +471,12 @@ k_unc_point_cov(const int64_t* __restrict__ pt_start, const int32_t* __restrict_
 
 }  // namespace
 
-extern "C" int cba_parameter_covariance(const cba_cov_desc* d, int32_t device, cba_cov_out* out) {
-  const char* what = "cba_parameter_covariance";
-  if (!d || !out) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
+// covariance_pipeline.h: everything up to C, shared with cba_observation_reliability (reliability_lib.hip)
+int cba::cov_pipeline(const cba_cov_desc* d, int32_t device, const char* what, bool canonical, const std::function<int(const CovPipeline&)>& finish) {
   // every index the kernels use, checked on the host before anything reaches the device
   std::string msg;
   CovPlan plan;
-  int rc = cov_validate(d, plan, msg);
+  int rc = cov_validate(d, plan, msg, what, canonical);
   if (rc) return err(rc, msg);
   rc = select_device(device, what);
   if (rc) return rc;
@@ -583,38 +583,55 @@ extern "C" int cba_parameter_covariance(const cba_cov_desc* d, int32_t device, c
   if (flags[F_DIAG] || flags[F_CHOL] || flags[F_TINY])
     return err(CBA_ERR_NUMERIC, std::string(what) + ": the reduced camera system is not positive definite beyond the gauge (a pivot is not safely positive): "
                                                     "the scene does not determine every camera parameter");
-  std::vector<double> point_cov;
-  if (out->point_cov) {
-    std::vector<double> E, F;
-    cov_gauge_terms(ncp, C.data(), B.data(), D.data(), E, F);
-    const double* dE = buf.in(E.data(), ncp, COV_GAUGE);
-    const double* dF = buf.in(F.data(), COV_GAUGE * COV_GAUGE);
-    double* dout = buf.make<double>(n_points, 6);
-    if (buf.status()) return buf.result(what);
-    hipLaunchKernelGGL(k_unc_point_cov, dim3((unsigned)n_points), dim3(COV_POINT_THREADS), 0, 0, dpt_start, (const int32_t*)dcam_sorted, dcam_off, ncp,
-                       (const double*)dY, (const double*)dVinv, (const double*)dZ, (const double*)dC, dE, dF, sigma0_sq, dout);
-    buf.check(hipGetLastError());
-    point_cov.resize((size_t)n_points * 6);
-    buf.out(point_cov.data(), (const double*)dout, n_points, 6);
-    if (buf.status()) return buf.result(what);
-    for (double v : point_cov)
-      if (!std::isfinite(v)) return err(CBA_ERR_NUMERIC, std::string(what) + ": a point covariance is not finite");
-  }
-  for (double v : C)
-    if (!std::isfinite(v)) return err(CBA_ERR_NUMERIC, std::string(what) + ": a camera covariance is not finite");
-  // outputs, written only now: a failed call leaves the caller's arrays alone
-  if (out->point_cov) std::copy(point_cov.begin(), point_cov.end(), out->point_cov);
-  if (out->cam_cov_full)
-    for (size_t i = 0; i < n_S; ++i) out->cam_cov_full[i] = sigma0_sq * C[i];
-  if (out->cam_cov)
-    for (int32_t c = 0; c < n_cams; ++c) {
-      const int32_t off = plan.cam_off[(size_t)c], np = plan.cam_off[(size_t)c + 1] - off;
-      for (int r = 0; r < MAX_NC; ++r)
-        for (int q = 0; q < MAX_NC; ++q)
-          out->cam_cov[((size_t)c * MAX_NC + r) * MAX_NC + q] = (r < np && q < np) ? sigma0_sq * C[(size_t)(off + r) * ncp + off + q] : 0.0;
+  const CovPipeline pipe = {&plan, n_cams, ncp, n_obs, n_points, dorder, dpt_start, dcam_sorted, dcam_off, dtab, dpoints, dobs_uv, dY, dVinv, dZ, dC,
+                            &C, &B, &D, sigma0_sq, cost};
+  return finish(pipe);
+}
+
+extern "C" int cba_parameter_covariance(const cba_cov_desc* d, int32_t device, cba_cov_out* out) {
+  const char* what = "cba_parameter_covariance";
+  if (!d || !out) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
+  return cov_pipeline(d, device, what, false, [&](const CovPipeline& pipe) -> int {
+    const CovPlan& plan = *pipe.plan;
+    const int32_t n_cams = pipe.n_cams, ncp = pipe.ncp;
+    const int64_t n_points = pipe.n_points;
+    const std::vector<double>& C = *pipe.C_host;
+    const size_t n_S = (size_t)ncp * ncp;
+    const double sigma0_sq = pipe.sigma0_sq, cost = pipe.cost;
+    Buffers buf;
+    std::vector<double> point_cov;
+    if (out->point_cov) {
+      std::vector<double> E, F;
+      cov_gauge_terms(ncp, C.data(), pipe.B_host->data(), pipe.Dinv_host->data(), E, F);
+      const double* dE = buf.in(E.data(), ncp, COV_GAUGE);
+      const double* dF = buf.in(F.data(), COV_GAUGE * COV_GAUGE);
+      double* dout = buf.make<double>(n_points, 6);
+      if (buf.status()) return buf.result(what);
+      hipLaunchKernelGGL(k_unc_point_cov, dim3((unsigned)n_points), dim3(COV_POINT_THREADS), 0, 0, pipe.pt_start, pipe.cam_sorted, pipe.cam_off, ncp,
+                         pipe.Y, pipe.Vinv, pipe.Z, pipe.C, dE, dF, sigma0_sq, dout);
+      buf.check(hipGetLastError());
+      point_cov.resize((size_t)n_points * 6);
+      buf.out(point_cov.data(), (const double*)dout, n_points, 6);
+      if (buf.status()) return buf.result(what);
+      for (double v : point_cov)
+        if (!std::isfinite(v)) return err(CBA_ERR_NUMERIC, std::string(what) + ": a point covariance is not finite");
     }
-  if (out->sigma0_sq) *out->sigma0_sq = sigma0_sq;
-  if (out->dof) *out->dof = plan.dof;
-  if (out->cost) *out->cost = cost;
-  return CBA_OK;
+    for (double v : C)
+      if (!std::isfinite(v)) return err(CBA_ERR_NUMERIC, std::string(what) + ": a camera covariance is not finite");
+    // outputs, written only now: a failed call leaves the caller's arrays alone
+    if (out->point_cov) std::copy(point_cov.begin(), point_cov.end(), out->point_cov);
+    if (out->cam_cov_full)
+      for (size_t i = 0; i < n_S; ++i) out->cam_cov_full[i] = sigma0_sq * C[i];
+    if (out->cam_cov)
+      for (int32_t c = 0; c < n_cams; ++c) {
+        const int32_t off = plan.cam_off[(size_t)c], np = plan.cam_off[(size_t)c + 1] - off;
+        for (int r = 0; r < MAX_NC; ++r)
+          for (int q = 0; q < MAX_NC; ++q)
+            out->cam_cov[((size_t)c * MAX_NC + r) * MAX_NC + q] = (r < np && q < np) ? sigma0_sq * C[(size_t)(off + r) * ncp + off + q] : 0.0;
+      }
+    if (out->sigma0_sq) *out->sigma0_sq = sigma0_sq;
+    if (out->dof) *out->dof = plan.dof;
+    if (out->cost) *out->cost = cost;
+    return CBA_OK;
+  });
 }

@@ -10,7 +10,9 @@
 // Every camera is handled nine wide: a six-parameter camera has zero columns 6..8 in A, so zero rows in W_a, Y_a and Nc; loops have
 // constant bounds and static indices (nothing here may live in scratch memory on the device).
 #pragma once
+#include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -69,8 +71,10 @@ CBA_HD void cov_gauge_point(double X, double Y, double Z, double (*N)[COV_GAUGE]
 }
 
 // One observation: residual and Jacobian blocks (project_full), both rows scaled for the robust loss (robust_one per scalar residual,
-// as scipy does).  A is nine wide with zeros behind the camera's parameters.  Returns rho0 + rho1 (cost = 0.5 sum).
-CBA_HD double cov_obs_jacobian(const CamTab& c, const double* X, const double* uv, int loss, double f_scale, double (*A)[MAX_NC], double (*B)[3]) {
+// as scipy does).  A is nine wide with zeros behind the camera's parameters.  Returns rho0 + rho1 (cost = 0.5 sum).  `r_scaled`, when
+// given, receives the two residuals as scipy scales them for the loss (the residuals themselves for the linear loss).
+CBA_HD double cov_obs_jacobian(const CamTab& c, const double* X, const double* uv, int loss, double f_scale, double (*A)[MAX_NC], double (*B)[3],
+                               double* r_scaled = nullptr) {
   double e[2];
 #pragma unroll
   for (int r = 0; r < 2; ++r)
@@ -82,6 +86,7 @@ CBA_HD double cov_obs_jacobian(const CamTab& c, const double* X, const double* u
   for (int r = 0; r < 2; ++r) {
     double js, rs;
     rho += robust_one(loss, f_scale, e[r], &js, &rs);
+    if (r_scaled) r_scaled[r] = rs;
 #pragma unroll
     for (int k = 0; k < MAX_NC; ++k) A[r][k] *= js;
 #pragma unroll
@@ -159,16 +164,18 @@ CBA_HD void cov_point_base(const double* Vi, const double (*Z)[COV_GAUGE], const
 // ---- host only -------------------------------------------------------------------------------------------------------------------
 
 struct CovPlan {
-  std::vector<int64_t> order;     // observations sorted by (point, input position)
+  std::vector<int64_t> order;     // observations sorted by (point, input position), or by (point, camera, uv, input position): cov_validate
   std::vector<int64_t> pt_start;  // [n_points + 1] into the sorted observations
   std::vector<int32_t> cam_off;   // [n_cams + 1] first parameter of a camera; cam_off[n_cams] = ncp
   int64_t dof = 0;
   int32_t ncp() const { return cam_off.back(); }
 };
 
-// Every check of the header, and the plan.  0 or a CBA_ERR_* with `msg` naming the offender.
-inline int cov_validate(const cba_cov_desc* d, CovPlan& plan, std::string& msg) {
-  const std::string what = "cba_parameter_covariance: ";
+// Every check of the header, and the plan.  0 or a CBA_ERR_* with `msg` naming the offender (`call`: the entry point the message starts with).
+// `canonical`: the observations of a point are ordered by (camera, bits of u, bits of v, input position) instead of by input position alone,
+// so that the sorted table, and with CBA_DETERMINISTIC=1 every bit computed from it, does not depend on the order of the caller's rows.
+inline int cov_validate(const cba_cov_desc* d, CovPlan& plan, std::string& msg, const char* call = "cba_parameter_covariance", bool canonical = false) {
+  const std::string what = std::string(call) + ": ";
   auto fail = [&](int code, const std::string& m) { msg = what + m; return code; };
   if (d->n_cams <= 0) return fail(CBA_ERR_INVALID, "n_cams must be positive, got " + std::to_string(d->n_cams));
   if (d->n_points <= 0 || d->n_points > INT32_MAX) return fail(CBA_ERR_INVALID, "n_points must be in [1, 2^31), got " + std::to_string(d->n_points));
@@ -206,6 +213,19 @@ inline int cov_validate(const cba_cov_desc* d, CovPlan& plan, std::string& msg) 
   std::vector<int64_t> next(plan.pt_start.begin(), plan.pt_start.end() - 1);
   plan.order.resize((size_t)d->n_obs);
   for (int64_t o = 0; o < d->n_obs; ++o) plan.order[(size_t)next[(size_t)d->obs_pt[o]]++] = o;
+  if (canonical) {
+    const auto bits = [&](int64_t o, int j) { uint64_t b; std::memcpy(&b, d->obs_uv + 2 * o + j, sizeof b); return b; };
+    const auto before = [&](int64_t a, int64_t b) {
+      if (d->obs_cam[a] != d->obs_cam[b]) return d->obs_cam[a] < d->obs_cam[b];
+      if (bits(a, 0) != bits(b, 0)) return bits(a, 0) < bits(b, 0);
+      if (bits(a, 1) != bits(b, 1)) return bits(a, 1) < bits(b, 1);
+      return a < b;
+    };
+    for (int64_t p = 0; p < d->n_points; ++p) {
+      const auto first = plan.order.begin() + plan.pt_start[(size_t)p], last = plan.order.begin() + plan.pt_start[(size_t)p + 1];
+      if (!std::is_sorted(first, last, before)) std::sort(first, last, before);  // (rows grouped by point and camera arrive sorted)
+    }
+  }
   return CBA_OK;
 }
 

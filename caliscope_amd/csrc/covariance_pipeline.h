@@ -1,0 +1,41 @@
+// The part of cba_parameter_covariance that cba_observation_reliability needs too (covariance_lib.hip defines it, reliability_lib.hip is
+// its second caller): the host checks, the uploads, every launch up to C = St^-1 (k_unc_cam .. k_unc_ttt, the header of covariance_lib.hip
+// lists them) and the numeric refusals on the way.  `finish` runs while the device buffers of the call are alive and returns the call's
+// code; whatever it allocates it owns.  Nothing is written to a caller's array before `finish` does so.  `canonical` is cov_validate's: the
+// order of a point's observations in the sorted table (cba_parameter_covariance keeps the input order, as it always has).
+#pragma once
+#include <cstdint>
+#include <functional>
+#include <vector>
+
+#include "covariance_math.h"
+
+namespace cba {
+
+struct CovPipeline {
+  const CovPlan* plan;  // order, pt_start, cam_off, dof (host)
+  int32_t n_cams, ncp;
+  int64_t n_obs, n_points;
+  // device: the point-ordered observation table and what the kernels left
+  const int64_t* order;       // [n_obs] sorted position -> the caller's row
+  const int64_t* pt_start;    // [n_points + 1]
+  const int32_t* cam_sorted;  // [n_obs] camera of a sorted position
+  const int32_t* cam_off;     // [n_cams + 1]
+  const double* tab;          // [n_cams] CamTab
+  const double* points;       // [n_points][3]
+  const double* obs_uv;       // [n_obs][2], the caller's order
+  const double* Y;            // [n_obs][27] Y_a = W_a V^-1, sorted order
+  const double* Vinv;         // [n_points][6]
+  const double* Z;            // [n_points][21]
+  const double* C;            // [ncp][ncp] St^-1, both triangles
+  // host
+  const std::vector<double>* C_host;     // [ncp][ncp]
+  const std::vector<double>* B_host;     // [ncp][7]
+  const std::vector<double>* Dinv_host;  // [7][7]
+  double sigma0_sq, cost;
+};
+
+__attribute__((visibility("hidden"))) int cov_pipeline(const cba_cov_desc* d, int32_t device, const char* what, bool canonical,
+                                                       const std::function<int(const CovPipeline&)>& finish);
+
+}  // namespace cba
