@@ -286,11 +286,8 @@ __device__ __forceinline__ int pub_solve_ends(const PubArgs& pub, double ta, dou
   const double ratio = trf::reduction_ratio(actual, pub.scal[45]);
   return trf::termination(actual, cost, sqrt(tb), sqrt(pub.scal[2]), ratio, pub.ftol, pub.xtol) != trf::TERMINATION_NONE ? 1 : 0;
 }
-__global__ void __launch_bounds__(64 * REDUCE_RY)
-k_reduce_rows_pub(const double* __restrict__ partial, int nrow, int width, double* __restrict__ out, double* __restrict__ grad_out,
-                  const int* __restrict__ cam_off, const int* __restrict__ cam_np, int stride, int tri, PubArgs pub) {
-  CBA_STAMP(ST_REDUCE_PUB);
-  if (blockIdx.x + 1 < gridDim.x) { reduce_rows_block(partial, nrow, width, out, grad_out, cam_off, cam_np, stride, tri); return; }
+// the packet workgroup (blockDim = (64, REDUCE_RY)) of k_reduce_rows_pub and k_reduce_scale_pub
+__device__ __forceinline__ void publish_packet(const PubArgs& pub) {
   __shared__ double sh_w[2][REDUCE_RY];
   const int t = threadIdx.y * 64 + threadIdx.x;
   const double own = (t < pub.n_scal) ? pub.scal[t] : 0.0;  // (requested with the partial rows, not behind their sums)
@@ -318,6 +315,13 @@ k_reduce_rows_pub(const double* __restrict__ partial, int nrow, int width, doubl
   __threadfence_system();
   __syncthreads();
   if (t == 0) reinterpret_cast<volatile unsigned long long*>(pub.host_scal)[63] = pub.seq;
+}
+__global__ void __launch_bounds__(64 * REDUCE_RY)
+k_reduce_rows_pub(const double* __restrict__ partial, int nrow, int width, double* __restrict__ out, double* __restrict__ grad_out,
+                  const int* __restrict__ cam_off, const int* __restrict__ cam_np, int stride, int tri, PubArgs pub) {
+  CBA_STAMP(ST_REDUCE_PUB);
+  if (blockIdx.x + 1 < gridDim.x) { reduce_rows_block(partial, nrow, width, out, grad_out, cam_off, cam_np, stride, tri); return; }
+  publish_packet(pub);
 }
 // Sharded solves: every host-visible primitive ends with ONE all-reduce of the scalars it produced.  k_xpack gathers
 // the scal slots named by `mask`, the four flags (as 0/1 doubles) and, when asked, this rank's max |g| (scal[4]) in
@@ -2857,6 +2861,110 @@ k_chol_apply(const double* __restrict__ Tinv, const double* __restrict__ W, int 
   if (cl == 0 && row < n) out[row] = s;
 }
 
+// The last launch of the factorisation and the backward substitution as ONE launch (solver path, nbk >= 2; CBA_CHOL_ENDS=0: k_chol_step
+// k = nbk - 1, a launch boundary, k_chol_apply).  Launch nbk - 1 has one panel workgroup, the rhs row, y_last = W_nbk,last X_last^T, and nbk - 1
+// inverse workgroups that finish the last block column of T; k_chol_apply's workgroup j then reads row block j of T and all of y.  Here
+// workgroup j does, for itself,
+//   0. the row sums over the columns in front of the last block (final since launch nbk - 2), requested with everything else;
+//   1. y_last, with the panel role's instructions (the pending update of the parent schedule included);
+//   2. its block T(j, last), with the inverse role's (j == last: X_last^T, stored by the look-ahead of launch nbk - 2);
+//   3. the last block's terms of the row sums from LDS: k_chol_apply's additions in k_chol_apply's order, x to the bit.
+// Nothing reads T, y or L after the solve (every solve forms them anew), so T(:, last) and y_last are not stored: this launch writes x only.
+// Blocks read: chol_last_apply_for_each_read of chol_schedule.h (replayed by tests/native/chol_schedule_ends_check.cpp).
+template <bool EARLY>
+__global__ void __launch_bounds__(CHOL_THREADS)
+k_chol_last_apply(const double* __restrict__ W, int n, int ldw, const double* __restrict__ Xinv, const double* __restrict__ Tinv,
+                  double* __restrict__ out) {
+  CBA_STAMP(ST_CHOL_APPLY);
+  static_assert(CHOL_THREADS == 16 * NB, "16 lanes per row of a block");
+  __shared__ double sh_red[4][16][17];
+  __shared__ double sh_U[NB][NB + 1], sh_T[NB][NB + 1], sh_y[NB];
+  __shared__ __attribute__((aligned(16))) double sh_L[NB][NB + 2];
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  const int nbk = (n + NB - 1) / NB, k = nbk - 1, k0 = k * NB, nbp = n - k0;  // the last panel: nbp live columns
+  constexpr int EPT = NB * NB / CHOL_THREADS, ISTEP = CHOL_THREADS / NB;
+  const int j = tid & 31, i0 = tid >> 5;
+  const int bj = (int)blockIdx.x, rj = bj * NB, rcj = min(NB, n - rj);  // block row of T
+  const double* Wn = W + (long)n * ldw;                                  // the rhs row
+  const double* Tb = Tinv + (long)rj * ldw + k0;                         // block (bj, last)
+  double m_ij[EPT], l_ij[EPT], old[EPT];
+#pragma unroll
+  for (int h = 0; h < EPT; ++h) {
+    const int i = i0 + h * ISTEP;
+    m_ij[h] = (i < 1 && j < nbp) ? Wn[k0 + j] : 0.0;
+    l_ij[h] = Xinv[(long)k * NB * NB + i * NB + j];  // X_last (identity-padded)
+    // bj < last: what the block has so far (its first term is this launch's when bj == last - 1); bj == last: the finished X_last^T
+    old[h] = (k - 1 != bj && i < rcj && j < nbp) ? Tb[(long)i * ldw + j] : 0.0;
+  }
+  // 0. k_chol_apply's sums over the finished columns: lane cl of the 16 of a row takes columns bj NB + cl + 32 m (a0) and + 16 (a1)
+  const int r = tid >> 4, cl = tid & 15, row = rj + r;
+  double a0 = 0.0, a1 = 0.0;
+  if (row < n) {
+    const double* Tr = Tinv + (long)row * ldw;
+    for (int c = rj + cl; c < k0; c += 32) { a0 = fma(Tr[c], Wn[c], a0); a1 = fma(Tr[c + 16], Wn[c + 16], a1); }
+  }
+  // 1. y_last = U X_last^T, U = the rhs row's panel columns (k_chol_step's stages 1 and 2 for b = nbk)
+  if constexpr (!EARLY) {
+    chol_rank_nb(Wn + (k0 - NB), 1, W + (long)k0 * ldw + (k0 - NB), nbp, ldw, sh_red, wv, lane);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int h = 0; h < EPT; ++h) {
+    const int i = i0 + h * ISTEP;
+    if constexpr (EARLY) sh_U[i][j] = m_ij[h];
+    else sh_U[i][j] = m_ij[h] - sh_red[(i >> 4) * 2 + (j >> 4)][i & 15][j & 15];
+    sh_L[i][j] = l_ij[h];
+  }
+  __syncthreads();
+  if (wv < 2) {  // the row tiles ti = 0 of the panel solve: row 0 is all there is
+    const int tj = wv;
+    v4f64 c = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int t = 0; t < NB / 4; ++t) {
+      const int q = 4 * t + (lane >> 4);
+      c = __builtin_amdgcn_mfma_f64_16x16x4f64(sh_U[lane & 15][q], sh_L[tj * 16 + (lane & 15)][q], c, 0, 0, 0);
+    }
+    if (lane < 16) sh_y[tj * 16 + lane] = (tj * 16 + lane < nbp) ? c[0] : 0.0;
+  }
+  __syncthreads();  // (sh_U and sh_red are free again)
+  // 2. T(bj, last) = -(old + T_bj,last-1 L_last,last-1^T) X_last^T (the inverse role for bi == k)
+  if (bj < k) {
+    chol_rank_nb(Tinv + (long)rj * ldw + (k0 - NB), rcj, W + (long)k0 * ldw + (k0 - NB), nbp, ldw, sh_red, wv, lane);
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < EPT; ++h) {
+      const int i = i0 + h * ISTEP;
+      sh_U[i][j] = (i < rcj && j < nbp) ? old[h] + sh_red[(i >> 4) * 2 + (j >> 4)][i & 15][j & 15] : 0.0;
+    }
+    __syncthreads();
+    if (wv < 4) {
+      const int ti = wv >> 1, tj = wv & 1;
+      v4f64 c = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int t = 0; t < NB / 4; ++t) {
+        const int q = 4 * t + (lane >> 4);
+        c = __builtin_amdgcn_mfma_f64_16x16x4f64(sh_U[ti * 16 + (lane & 15)][q], sh_L[tj * 16 + (lane & 15)][q], c, 0, 0, 0);
+      }
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) sh_T[ti * 16 + (lane >> 4) + 4 * rr][tj * 16 + (lane & 15)] = -c[rr];
+    }
+  } else {
+#pragma unroll
+    for (int h = 0; h < EPT; ++h) sh_T[i0 + h * ISTEP][j] = old[h];
+  }
+  __syncthreads();
+  // 3. the last block's terms, then the 16 lanes of a row meet
+  if (row < n) {
+    const int c = k0 + cl;
+    if (c + 16 < n) { a0 = fma(sh_T[r][cl], sh_y[cl], a0); a1 = fma(sh_T[r][cl + 16], sh_y[cl + 16], a1); }
+    else if (c < n) a0 = fma(sh_T[r][cl], sh_y[cl], a0);
+  }
+  double s = a0 + a1;
+#pragma unroll
+  for (int off = 8; off >= 1; off >>= 1) s += __shfl_xor(s, off, 16);
+  if (cl == 0 && row < n) out[row] = s;
+}
+
 // ------------------------------------------------------------------------------------------------
 // back-substitution:  dp = -V'^-1 (g_p + sum_i W_i^T dc_{c_i}),  W_i^T dc = B_i^T (A_i dc)
 // SCAL (single-rank fused iteration): the point block's share of the step scalars — sum (s sinv)^2 and sum g s, what k_step_scalars would
@@ -3369,6 +3477,36 @@ struct BoundArgs {
   double* state_out;        // [ncp_pad] ... after it
   double* cam_diag_out;     // [ncp_pad]
 };
+// what a thread of the plain (unbounded) pass carries: ||g_h||^2, ||x_h||^2, ||x||^2, max |g|
+struct ScaleSums { double s0 = 0.0, s1 = 0.0, s2 = 0.0, m = 0.0; };
+// the squared column norm of entry i >= ncp_pad (a point entry); false: padding, which keeps its scale
+__device__ __forceinline__ bool scale_point_diag(long i, const VecLayout& lay, const double* __restrict__ Vblk, const double* __restrict__ cdiag, double* v) {
+  const long k = (i - lay.ncp_pad) / lay.Ppad, p = (i - lay.ncp_pad) % lay.Ppad;
+  if (p >= lay.P) return false;
+  const int q = (k == 0) ? 0 : (k == 1 ? 3 : 5);
+  *v = Vblk[(long)q * lay.Ppad + p];
+  if (cdiag) *v += cdiag[k * lay.Ppad + p];
+  return true;
+}
+// One entry of the plain pass (k_scale_lin, k_reduce_scale_pub: the same arithmetic, so sinv and v1 are the same bits on both routes).
+// live: v is the entry's squared column norm, si its scale so far; else a padding entry (carry: its scale is copied to `sinv`).
+__device__ __forceinline__ void scale_lin_entry(long i, bool live, double v, double si, int first, bool carry, double gi, double xi,
+                                                double* __restrict__ sinv, double* __restrict__ v1, ScaleSums& a) {
+  if (live) {
+    v = sqrt(v);
+    if (first) { if (v == 0.0) v = 1.0; } else v = fmax(v, si);
+    si = v;
+    sinv[i] = si;
+  } else if (carry) {
+    sinv[i] = si;  // padding entries: carried over
+  }
+  const double gh = gi / si;
+  v1[i] = gh / si;
+  a.m = fmax(a.m, fabs(gi));
+  a.s0 += gh * gh;
+  a.s1 += (xi * si) * (xi * si);
+  a.s2 += xi * xi;
+}
 template <int NC, bool BND = false>  // BND: the bounded variant (a kernel of its own: the plain pass measured 8.7 us without the branch, 10.0 with it)
 __global__ void __launch_bounds__(BLOCK)
 k_scale_lin(const double* __restrict__ Upacked, const double* __restrict__ Vblk, const int* __restrict__ param_cam,
@@ -3381,7 +3519,8 @@ k_scale_lin(const double* __restrict__ Upacked, const double* __restrict__ Vblk,
   __shared__ double sh_red[BLOCK / WAVE];
   const long total = lay.total();
   const double* sin = sinv_in ? sinv_in : sinv;
-  double s0 = 0, s1 = 0, s2 = 0, s3 = 0, m = 0;
+  ScaleSums a;
+  double s3 = 0.0;  // C_gg
   for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (long)gridDim.x * BLOCK) {
     double si = sin[i];
     bool live = true;
@@ -3395,7 +3534,7 @@ k_scale_lin(const double* __restrict__ Upacked, const double* __restrict__ Vblk,
       double vv = 1.0, dv = 0.0;
       if (gi < 0.0 && isfinite(hi)) { vv = hi - xi; dv = -1.0; }
       else if (gi > 0.0 && isfinite(lo)) { vv = xi - lo; dv = 1.0; }
-      m = fmax(m, fabs(gi * vv));              // ||g v||_inf (trf.py:298)
+      a.m = fmax(a.m, fabs(gi * vv));          // ||g v||_inf (trf.py:298)
       if (dv != 0.0) vv *= sj;                 // v[dv != 0] *= scale_inv
       const double se = sj / sqrt(vv);         // effective scale_inv = scale_inv / sqrt(v)
       const double dh = gi * dv / sj;          // diag_h = g dv scale  (>= 0)
@@ -3403,9 +3542,9 @@ k_scale_lin(const double* __restrict__ Upacked, const double* __restrict__ Vblk,
       bnd.cam_diag_out[i] = dh * se * se;
       const double gh = gi / se;
       v1[i] = gh / se;
-      s0 += gh * gh;
-      s1 += (xi * se) * (xi * se);
-      s2 += xi * xi;
+      a.s0 += gh * gh;
+      a.s1 += (xi * se) * (xi * se);
+      a.s2 += xi * xi;
       s3 += dh * gh * gh;
       continue;
     }
@@ -3413,38 +3552,141 @@ k_scale_lin(const double* __restrict__ Upacked, const double* __restrict__ Vblk,
       if (i >= lay.ncp) live = false;  // padding keeps scale 1
       else { const int r = param_loc[i]; v = Upacked[param_cam[i] * UP::STRIDE + UP::idx(r, r)]; }
     } else {
-      const long k = (i - lay.ncp_pad) / lay.Ppad, p = (i - lay.ncp_pad) % lay.Ppad;
-      if (p >= lay.P) live = false;
-      else {
-        const int q = (k == 0) ? 0 : (k == 1 ? 3 : 5);
-        v = Vblk[(long)q * lay.Ppad + p];
-        if (cdiag) v += cdiag[k * lay.Ppad + p];
-      }
+      live = scale_point_diag(i, lay, Vblk, cdiag, &v);
     }
-    if (live) {
-      v = sqrt(v);
-      if (first) { if (v == 0.0) v = 1.0; } else v = fmax(v, si);
-      si = v;
-      sinv[i] = si;
-    } else if (sinv_in) {
-      sinv[i] = si;  // padding entries: carried over
-    }
-    const double gi = g[i], xi = x[i];
-    const double gh = gi / si;
-    v1[i] = gh / si;
-    m = fmax(m, fabs(gi));
-    s0 += gh * gh;
-    s1 += (xi * si) * (xi * si);
-    s2 += xi * xi;
+    scale_lin_entry(i, live, v, si, first, sinv_in != nullptr, g[i], x[i], sinv, v1, a);
   }
   double r;
-  r = block_sum(s0, sh_red); if (threadIdx.x == 0) partial[blockIdx.x * 4 + 0] = r;
-  r = block_sum(s1, sh_red); if (threadIdx.x == 0) partial[blockIdx.x * 4 + 1] = r;
-  r = block_sum(s2, sh_red); if (threadIdx.x == 0) partial[blockIdx.x * 4 + 2] = r;
+  r = block_sum(a.s0, sh_red); if (threadIdx.x == 0) partial[blockIdx.x * 4 + 0] = r;
+  r = block_sum(a.s1, sh_red); if (threadIdx.x == 0) partial[blockIdx.x * 4 + 1] = r;
+  r = block_sum(a.s2, sh_red); if (threadIdx.x == 0) partial[blockIdx.x * 4 + 2] = r;
   r = block_sum(s3, sh_red); if (threadIdx.x == 0) partial[blockIdx.x * 4 + 3] = r;  // C_gg (zero without bounds)
-  r = block_max(m, sh_red); if (threadIdx.x == 0) partial_max[blockIdx.x] = r;
+  r = block_max(a.m, sh_red); if (threadIdx.x == 0) partial_max[blockIdx.x] = r;
   if (BND && blockIdx.x == 0)  // padding entries of the state carry over
     for (int i = lay.ncp + threadIdx.x; i < lay.ncp_pad; i += BLOCK) { bnd.state_out[i] = 1.0; bnd.cam_diag_out[i] = 0.0; }
+}
+
+// The plain scale pass INSIDE the launch that reduces a build's camera blocks (single rank, camera-sorted super-chunks, no bounds, no constraint
+// rows: CBA_SCALE_FUSED=0 keeps k_reduce_rows[_pub] + k_scale_lin).  The point entries of the pass need V, g_p, the old scale and x, all complete when
+// the build ends: they are workgroups of their own.  The camera entries need the diagonal of U_c and g_c: a reducing workgroup takes ONE camera
+// (its 27 or 54 packed columns of the 64 a workgroup has), so the workgroup that has summed a camera scales its entries from the sums it still
+// holds in LDS.  (Two six-parameter cameras per workgroup were measured first: the 32 reducing workgroups of cfg4, 221 KB each through one CU
+// while 196 point workgroups saturate the memory system, were the launch's long pole at 13.4 us.)  blockDim = (64, REDUCE_RY); roles in dispatch order:
+//   with_pub: 1 workgroup     the iteration's packet (publish_packet: it needs nothing of this launch and leaves first)
+//   cam_wgs = cameras         column sums in reduce_rows_block's order (U_c and g_c are its bits), then the camera's <= NC entries of the pass
+//   pt_wgs                    entries ncp .. total - 1 (the padding of the camera block and the points), at most four per thread, requested together.
+//                             (cfg4: 1 + 64 + 147 workgroups.  Two workgroups of 1024 threads were not seen to share a CU: with 261 workgroups on
+//                             256 CUs the last five entered 8.4 us late and the launch took 14.9 us.)
+// Every reducing and every point workgroup leaves one row of sums (partial[row][4], the fourth zero) and one of max |g| (partial_max[row]):
+// cam_wgs + pt_wgs rows where k_scale_lin leaves vec_grid(total).  partial_max is NOT the buffer of the trial cost rows, which the packet workgroup
+// reads in this launch.
+template <int NC> struct ScaleFuse {
+  static constexpr int CPW = 1;                              // cameras per reducing workgroup
+  static constexpr int PT_UNROLL = 4;                        // entries per thread of a point workgroup
+  static constexpr int PT_ENTRIES = PT_UNROLL * 64 * REDUCE_RY;
+  __host__ __device__ static int cam_wgs(int n_cams) { return (n_cams + CPW - 1) / CPW; }
+  __host__ __device__ static long pt_wgs(const VecLayout& lay) { return (lay.total() - lay.ncp + PT_ENTRIES - 1) / PT_ENTRIES; }  // >= 1: total > ncp_pad
+};
+struct ScaleArgs {
+  const double* Vblk; VecLayout lay; int first;
+  double* sinv; const double* sinv_in;  // sinv_in != nullptr: as k_scale_lin
+  const double* x; const double* g;     // g: the vector the reduction writes the camera entries of (read here from ncp on)
+  double* v1; double* partial; double* partial_max;
+};
+template <int NC>
+__global__ void __launch_bounds__(64 * REDUCE_RY)
+k_reduce_scale_pub(const double* __restrict__ partial, int nrow, int n_cams, double* __restrict__ out, double* __restrict__ grad_out,
+                   const int* __restrict__ cam_off, const int* __restrict__ cam_np, ScaleArgs sc, int with_pub, PubArgs pub) {
+  CBA_STAMP(ST_REDUCE_PUB);
+  using UP = UPack<NC>;
+  using SF = ScaleFuse<NC>;
+  int wg = (int)blockIdx.x;
+  if (with_pub) {
+    if (wg == 0) { publish_packet(pub); return; }
+    --wg;
+  }
+  __shared__ double sh[REDUCE_RY][64];
+  __shared__ double sh_col[64];
+  __shared__ double sh_s[4][REDUCE_RY];
+  const int tx = threadIdx.x, ty = threadIdx.y;
+  const int n_cam_wgs = SF::cam_wgs(n_cams);
+  const double* __restrict__ xv = sc.x;
+  double* __restrict__ sout = sc.sinv;
+  const double* sin = sc.sinv_in ? sc.sinv_in : sout;
+  double* __restrict__ v1 = sc.v1;
+  ScaleSums a;
+  if (wg < n_cam_wgs) {
+    const int c0 = wg * SF::CPW, ncol = min(SF::CPW, n_cams - c0) * UP::STRIDE;
+    const int width = n_cams * UP::STRIDE, j = c0 * UP::STRIDE + tx;
+    // reduce_rows_block's sum of column j, the same additions in the same order; 32 rows are requested at once where there are as many (a reducing
+    // workgroup has 54 columns and shares the memory system with the point workgroups: four dependent rounds of eight loads were its whole lifetime)
+    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (tx < ncol) {
+      int b = ty;
+      for (; b + 31 * REDUCE_RY < nrow; b += 32 * REDUCE_RY) {
+        double v[32];
+#pragma unroll
+        for (int q = 0; q < 32; ++q) v[q] = partial[(long)(b + q * REDUCE_RY) * width + j];
+#pragma unroll
+        for (int q = 0; q < 32; ++q) acc[q & 7] += v[q];
+      }
+      for (; b + 7 * REDUCE_RY < nrow; b += 8 * REDUCE_RY) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[q] += partial[(long)(b + q * REDUCE_RY) * width + j];
+      }
+      for (; b < nrow; b += REDUCE_RY) acc[0] += partial[(long)b * width + j];
+    }
+    sh[ty][tx] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+    __syncthreads();
+    if (ty == 0) {
+      double tot = 0.0;
+#pragma unroll
+      for (int y = 0; y < REDUCE_RY; ++y) tot += sh[y][tx];
+      sh_col[tx] = tot;
+      if (tx < ncol) {
+        out[j] = tot;
+        const int c = j / UP::STRIDE, r = j % UP::STRIDE - UP::TRI;
+        if (r >= 0 && r < cam_np[c]) grad_out[cam_off[c] + r] = tot;
+      }
+    }
+    __syncthreads();
+    if (ty == 0 && tx < SF::CPW * NC) {  // the cameras' own entries of the pass
+      const int cl = tx / NC, r = tx % NC, c = c0 + cl;
+      if (c < n_cams && r < cam_np[c]) {
+        const long i = cam_off[c] + r;
+        scale_lin_entry(i, true, sh_col[cl * UP::STRIDE + UP::idx(r, r)], sin[i], sc.first, false, sh_col[cl * UP::STRIDE + UP::TRI + r], xv[i], sout, v1, a);
+      }
+    }
+  } else {
+    const double* __restrict__ gv = sc.g;
+    const double* __restrict__ Vblk = sc.Vblk;
+    const long total = sc.lay.total(), stride = ((long)gridDim.x - (with_pub ? 1 : 0) - n_cam_wgs) * (64 * REDUCE_RY);
+    constexpr int UNR = SF::PT_UNROLL;  // a thread's entries are requested together and taken in ascending order; UNR * stride >= total - ncp
+    const long i0 = sc.lay.ncp + (long)(wg - n_cam_wgs) * (64 * REDUCE_RY) + ty * 64 + tx;
+    if (i0 < total) {
+      double v[UNR], si[UNR], gi[UNR], xi[UNR];
+      bool live[UNR];
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const long i = (i0 + u * stride < total) ? i0 + u * stride : i0;  // (beyond the end: the first entry again, not used)
+        v[u] = 0.0;
+        live[u] = i >= sc.lay.ncp_pad && scale_point_diag(i, sc.lay, Vblk, nullptr, &v[u]);
+        si[u] = sin[i]; gi[u] = gv[i]; xi[u] = xv[i];
+      }
+#pragma unroll
+      for (int u = 0; u < UNR; ++u)
+        if (i0 + u * stride < total) scale_lin_entry(i0 + u * stride, live[u], v[u], si[u], sc.first, sc.sinv_in != nullptr, gi[u], xi[u], sout, v1, a);
+    }
+  }
+  // the workgroup's row: sixteen wave sums, added in wave order
+  const double r0 = wave_sum(a.s0), r1 = wave_sum(a.s1), r2 = wave_sum(a.s2), rm = wave_max(a.m);
+  if (tx == 0) { sh_s[0][ty] = r0; sh_s[1][ty] = r1; sh_s[2][ty] = r2; sh_s[3][ty] = rm; }
+  __syncthreads();
+  if (ty == 0 && tx < 4) {
+    double r = 0.0;
+    for (int y = 0; y < REDUCE_RY; ++y) r = (tx == 3) ? fmax(r, sh_s[3][y]) : r + sh_s[tx][y];
+    if (tx == 3) { sc.partial_max[wg] = r; sc.partial[wg * 4 + 3] = 0.0; } else sc.partial[wg * 4 + tx] = r;
+  }
 }
 
 __device__ __forceinline__ double column_sum(const double* __restrict__ partial, int nrow, int width, int col, double* sh) {

@@ -105,6 +105,9 @@ struct cba_problem {
   double *x0 = nullptr, *x = nullptr, *x_new = nullptr, *g = nullptr, *s = nullptr, *sinv = nullptr, *v1 = nullptr, *v2 = nullptr;
   double *V = nullptr, *Upacked = nullptr;
   double *partial = nullptr, *partial4 = nullptr, *partial1 = nullptr;
+  double* partial_gmax = nullptr;  // rows of max |g| of the scale pass (a buffer of its own: the fused pass runs beside the packet workgroup, which reads the trial cost rows in partial1)
+  int scale_rows = 0;              // ... and how many the last pass left (k_scale_lin: vec_grid(total); k_reduce_scale_pub: its reducing and point workgroups)
+  bool scale_fused = true;         // the plain scale pass inside the launch that reduces the camera blocks (k_reduce_scale_pub; CBA_SCALE_FUSED=0: two launches, A/B)
   long partial_width = 0;
   bool want_chol_trace = false;
   long long* chol_trace = nullptr;  // CBA_CHOL_TRACE=1: phase stamps of k_chol_step (tools/chol_trace.py)
@@ -117,6 +120,7 @@ struct cba_problem {
   double* tri = nullptr;   // packed upper triangle of Sacc + b for the exchange of a sharded solve
   double* Xinv = nullptr;  // inverses of the diagonal blocks of the Cholesky factor and, behind them, the side slots of the early update: [chol_xinv_blocks][NB][NB] (k_chol_step)
   double* Tinv = nullptr;  // T = L^-T, built block by block next to the factorisation (inverse role of k_chol_step)
+  bool chol_ends = true;   // the last launch of the factorisation and the backward substitution as one (k_chol_last_apply; CBA_CHOL_ENDS=0: the old sequence, A/B)
   bool chol_early = true;  // k_chol_step<true>: the pending panel update off the critical chain (chol_schedule.h; CBA_CHOL_EARLY=0: the parent's schedule, A/B)
   bool fuse_reg_finalize = true;  // k_reg_finalize in the place of k_reg_reduce + k_schur_finalize where the route allows (CBA_REG_FINALIZE=0: off)
   double* scal = nullptr;  // device scalars
@@ -170,7 +174,7 @@ struct cba_problem {
   int* spec_word = nullptr;        // flags + 4
   bool spec_jv_enqueued = false;   // the speculative linearisation behind the last cba_step has its J.g pass ...
   bool spec_jv_dropped = false;    // ... which the device skipped (packet slot 48)
-  bool spec_scale_ready = false;   // the accepted trial came with its speculative scale pass: partial1 holds the rows of max |g| at the current x
+  bool spec_scale_ready = false;   // the accepted trial came with its speculative scale pass: partial_gmax holds the rows of max |g| at the current x
   long spec_jv_skipped = 0;        // cba_info
   unsigned long long gnorm_seq = 0;  // sequence word of the max |g| the last cba_step's speculation publishes by itself when the solve ends at its trial
   bool gnorm_mailed = false;         // ... and it does: the accepted trial's pass was skipped on the device, or replaced by k_gnorm_pub
@@ -612,8 +616,8 @@ static void drop_plan_task(cba_problem* p);  // (PlanTask is defined with the pl
 // CBA_STAMPS=1 (profiling build): the kernels of the LAST fused iteration in the order they started, with the device's own clock — duration from the
 // first workgroup's entry to the last wave's exit, and the idle time in front of each (previous kernel's last exit -> this kernel's first entry).
 static void dump_stamps(cba_problem* p) {
-  static const char* names[] = {"k_tprep", "k_schur_reg3", "k_reg_reduce (or k_reg_finalize)", "k_schur_finalize", "k_chol_apply", "k_backsub", "k_step_cam", "k_build_cs",
-                                "k_reduce_rows_pub", "k_scale_lin", "k_jv", "k_small_solve"};
+  static const char* names[] = {"k_tprep", "k_schur_reg3", "k_reg_reduce (or k_reg_finalize)", "k_schur_finalize", "k_chol_apply (or k_chol_last_apply)", "k_backsub", "k_step_cam", "k_build_cs",
+                                "k_reduce_rows_pub (or k_reduce_scale_pub)", "k_scale_lin", "k_jv", "k_small_solve"};
   const size_t n = (size_t)STAMP_SLOTS * STAMP_BLOCKS * STAMP_ROW;
   std::vector<long long> h(n);
   long long* null_ptr = nullptr;
@@ -1250,7 +1254,7 @@ static int alloc_solver_buffers(cba_problem* p) {
   p->partial_capacity = (size_t)std::max<long>((long)p->grid * w_build, (long)(p->tile_grid + p->tile_grid / 8 + 1) * std::max(p->tp.rep, 1) * p->tp.tile_elems);
   TRYS(dev_alloc(p, &p->partial, p->partial_capacity));
   // partial4: up to JV_ROWS rows of k_jv followed by up to CON_ROWS rows of k_con_jv (run_jv)
-  TRYS(dev_alloc(p, &p->partial4, (size_t)PARTIAL4_ROWS * 4)); TRYS(dev_alloc(p, &p->partial1, (size_t)2048)); TRYS(dev_alloc(p, &p->partial4b, (size_t)2048 * 4));
+  TRYS(dev_alloc(p, &p->partial4, (size_t)PARTIAL4_ROWS * 4)); TRYS(dev_alloc(p, &p->partial1, (size_t)2048)); TRYS(dev_alloc(p, &p->partial_gmax, (size_t)2048)); TRYS(dev_alloc(p, &p->partial4b, (size_t)2048 * 4));
   TRYS(dev_zeros(p, &p->Sacc, (size_t)ncp * ncp + (size_t)B_SLICES * p->lay.ncp_pad));  // + the rhs accumulator b, B_SLICES rows (k_reg_reduce)
   TRYS(dev_alloc(p, &p->tri, (size_t)ncp * (ncp + 1) / 2 + p->lay.ncp_pad));
   if (!p->eval_only) {
@@ -1317,7 +1321,9 @@ int cba_create(const cba_problem_desc* d, const cba_options* opt, cba_problem** 
   p->loss = d->loss; p->f_scale = d->f_scale;
   if (const char* e = std::getenv("CBA_REG_FINALIZE")) p->fuse_reg_finalize = e[0] != '0';
   if (const char* e = std::getenv("CBA_CHOL_EARLY")) p->chol_early = e[0] != '0';
+  if (const char* e = std::getenv("CBA_CHOL_ENDS")) p->chol_ends = e[0] != '0';
   if (const char* e = std::getenv("CBA_SPEC_SKIP")) p->spec_skip = e[0] != '0';
+  if (const char* e = std::getenv("CBA_SCALE_FUSED")) p->scale_fused = e[0] != '0';
   if (const char* e = std::getenv("CBA_SMALL_SOLVE")) p->small_solve_on = e[0] != '0';
 #ifdef CBA_PROFILING
   p->schur_clock = std::getenv("CBA_SCHUR_CLOCK") != nullptr;
@@ -1533,13 +1539,22 @@ static int launch_cost(cba_problem* p, const double* xvec, const double* tab, in
 // (k_step_cam) adds the camera block, takes the subspace step and prepares the trial point's cameras, and the trial build forms the point
 // entries of the trial point itself — k_step_scalars, k_step_finish / k_step_small and k_trial_update are not launched.
 static bool fused_trial(const cba_problem* p, bool compact) { return compact && p->cs.n_sc && !p->det_m && !p->n_heavy && !p->con.n_con; }
+// The plain scale pass rides in the launch that reduces the camera blocks (k_reduce_scale_pub) on the routes fused_trial names, unbounded.  Fixed-order
+// sums, sharded handles, constraint rows, heavy points and bounded solves (Coleman-Li scaling, k_scale_lin<NC, true>) keep the two launches.
+// (its rows must fit the 2048 of partial4b and partial_gmax: about 2.5 million points; beyond, the two launches)
+template <int NC>
+static bool scale_fusable(const cba_problem* p, bool compact) {
+  return p->scale_fused && fused_trial(p, compact) && !p->bounds_on && !p->cam_scaled && ScaleFuse<NC>::cam_wgs(p->C) + ScaleFuse<NC>::pt_wgs(p->lay) <= 2048;
+}
 
 // Build pass at xvec (camera table tab) into the given outputs; the rho sum lands in scal[cost_slot].
 // trial != nullptr (fused_trial): k_build_cs<.., TRIAL> forms the point entries of xvec = x_new from *trial while it stages them.
+// scale != nullptr (scale_fusable): the plain scale pass at xvec runs inside the launch that reduces the camera blocks (k_reduce_scale_pub), which
+// also writes the camera entries of g whether `compact` or not; its rows: p->scale_rows.
 template <int NC>
 static int run_build_into(cba_problem* p, const double* xvec, const double* tab, double* V, double* g, double* Upacked, int cost_slot,
                           const double* skip = nullptr, bool defer_exchange = false, bool compact = false, int flag_slot = 0,
-                          const TrialSrc* trial = nullptr, const PubArgs* pub = nullptr) {
+                          const TrialSrc* trial = nullptr, const PubArgs* pub = nullptr, const ScaleArgs* scale = nullptr) {
   RoctxRange range("cba:build");
   {
     ScopedTimer t(p, T_BUILD);
@@ -1584,6 +1599,16 @@ static int run_build_into(cba_problem* p, const double* xvec, const double* tab,
     const int w = p->C * UPack<NC>::STRIDE;
     // rows of per-workgroup partial blocks to sum; the global-atomics form of k_build_cs leaves ONE row
     const int u_rows = (p->cs.n_sc && !p->det_m && !p->n_heavy && build_cs_uglob<NC>(p)) ? 1 : p->grid;
+    if (scale) {
+      using SF = ScaleFuse<NC>;
+      const int rows = SF::cam_wgs(p->C) + (int)SF::pt_wgs(p->lay);
+      hipLaunchKernelGGL((k_reduce_scale_pub<NC>), dim3(rows + (pub ? 1 : 0)), dim3(64, REDUCE_RY), 0, p->stream, (const double*)p->partial, u_rows, p->C, Upacked, g,
+                         (const int*)p->cam_off, (const int*)p->cam_np, *scale, pub ? 1 : 0, pub ? *pub : PubArgs{});
+      p->scale_rows = rows;
+      if (!compact)  // (the first linearisation of a solve: nobody sends a packet, the rho sum is taken here)
+        hipLaunchKernelGGL(k_reduce_narrow<false>, dim3(1), dim3(BLOCK), 0, p->stream, p->partial1, p->grid, 1, p->scal + cost_slot);
+      return CBA_OK;
+    }
     if (compact) {  // single-rank fused step: gradient entries written by the row reduction, rho sum by k_publish
       if (pub)  // ... whose packet leaves with one more workgroup of this launch
         hipLaunchKernelGGL(k_reduce_rows_pub, dim3((w + 63) / 64 + 1), dim3(64, REDUCE_RY), 0, p->stream, (const double*)p->partial, u_rows, w, Upacked, g,
@@ -1617,7 +1642,9 @@ static int run_build_into(cba_problem* p, const double* xvec, const double* tab,
 
 template <int NC>
 // the build at the current x flags a non-finite residual in flags[3] (flags[0] belongs to trial points)
-static int run_build(cba_problem* p) { return run_build_into<NC>(p, p->x, p->tab, p->V, p->g, p->Upacked, 8, nullptr, false, false, 3); }
+static int run_build(cba_problem* p, const ScaleArgs* scale = nullptr) {
+  return run_build_into<NC>(p, p->x, p->tab, p->V, p->g, p->Upacked, 8, nullptr, false, false, 3, nullptr, nullptr, scale);
+}
 
 template <int NC>
 static int run_jv(cba_problem* p, int nv, int* rows_out = nullptr, const double* xvec = nullptr, const double* tab = nullptr, const SpecSkip& skip = SpecSkip{}) {
@@ -1650,8 +1677,11 @@ template <int NC>
 static int run_lin_chain(cba_problem* p, bool scalars = true, bool compact = false, double radius = 0.0, bool defer_finish = false) {
   RoctxRange range("cba:linearize");
   p->spec_scale_ready = false; p->gnorm_mailed = false;
+  bool scaled = false;  // the build's reducing launch has run the scale pass as well
   if (!p->have_build) {
-    int rcb = run_build<NC>(p);
+    const ScaleArgs sa{p->V, p->lay, p->first_scale ? 1 : 0, p->sinv, nullptr, p->x, p->g, p->v1, p->partial4b, p->partial_gmax};
+    scaled = scale_fusable<NC>(p, compact);
+    int rcb = run_build<NC>(p, scaled ? &sa : nullptr);
     if (rcb) return rcb;
     p->cost_pending = true;
     p->have_build = true;  // V, g, Upacked belong to the current x until it changes
@@ -1662,12 +1692,12 @@ static int run_lin_chain(cba_problem* p, bool scalars = true, bool compact = fal
     // ||J_h g_h||^2 are there, only the damping depends on the radius the host has just decided
     p->spec_valid = false;
     if (defer_finish) {  // (k_tprep sums the partial rows itself: no launch here)
-      p->lf = LinFin{p->partial4b, p->partial1, p->partial4, vec_grid(p->lay.total()), p->spec_rows_jv, radius, p->scal, p->fz};
+      p->lf = LinFin{p->partial4b, p->partial_gmax, p->partial4, p->scale_rows, p->spec_rows_jv, radius, p->scal, p->fz};
       p->lf_pending = true;
       return CBA_OK;
     }
     ScopedTimer t(p, T_SCALE_SCALARS);
-    hipLaunchKernelGGL(k_lin_finish, dim3(1), dim3(BLOCK), 0, p->stream, p->partial4b, p->partial1, vec_grid(p->lay.total()), p->partial4, p->spec_rows_jv, radius,
+    hipLaunchKernelGGL(k_lin_finish, dim3(1), dim3(BLOCK), 0, p->stream, p->partial4b, p->partial_gmax, p->scale_rows, p->partial4, p->spec_rows_jv, radius,
                        p->scal, p->fz);
     return CBA_OK;
   }
@@ -1692,19 +1722,22 @@ static int run_lin_chain(cba_problem* p, bool scalars = true, bool compact = fal
       auto launch_sl = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(vg), dim3(BLOCK), 0, p->stream, p->Upacked, p->V, p->param_cam, p->param_loc, p->lay,
                            p->first_scale ? 1 : 0, p->sinv, p->con.n_con ? (const double*)p->con.cdiag : (const double*)nullptr, p->x, p->g, p->v1,
-                           p->partial4b, p->partial1, (const double*)nullptr, ba);
+                           p->partial4b, p->partial_gmax, (const double*)nullptr, ba);
       };
-      if (bnd) launch_sl(k_scale_lin<NC, true>); else launch_sl(k_scale_lin<NC, false>);
+      if (!scaled) {
+        if (bnd) launch_sl(k_scale_lin<NC, true>); else launch_sl(k_scale_lin<NC, false>);
+        p->scale_rows = vg;
+      }
       p->first_scale = false;
       int rows_jv = 0;
       int rcj = run_jv<NC>(p, 1, &rows_jv);
       if (rcj) return rcj;
       if (defer_finish) {
-        p->lf = LinFin{p->partial4b, p->partial1, p->partial4, vg, rows_jv, radius, p->scal, p->fz};
+        p->lf = LinFin{p->partial4b, p->partial_gmax, p->partial4, p->scale_rows, rows_jv, radius, p->scal, p->fz};
         p->lf_pending = true;
         return CBA_OK;
       }
-      hipLaunchKernelGGL(k_lin_finish, dim3(1), dim3(BLOCK), 0, p->stream, p->partial4b, p->partial1, vg, p->partial4, rows_jv, radius,
+      hipLaunchKernelGGL(k_lin_finish, dim3(1), dim3(BLOCK), 0, p->stream, p->partial4b, p->partial_gmax, p->scale_rows, p->partial4, rows_jv, radius,
                          p->scal, p->fz);
       return CBA_OK;
     }
@@ -1754,12 +1787,13 @@ static int run_linearize(cba_problem* p, cba_linearization* out) {
 // factors its own matrix with them.  W: (n + 1) x ldw work matrix (rows 0..n-1 the matrix, both triangles; row n a right-hand side), ldw a
 // multiple of 4; Xinv: chol_xinv_blocks(blocks) NB x NB (the inverses and the side slots of the early update); Tinv: n x ldw, zero on entry outside
 // what a call writes (the upper block triangle); flags[2] is raised by a pivot that is not positive; early: the schedule (chol_schedule.h, which also
-// holds the workgroup counts of a launch — the kernel decodes its role from the same functions).  Not part of the C ABI.
+// holds the workgroup counts of a launch — the kernel decodes its role from the same functions).  without_last: see below.  Not part of the C ABI.
 namespace cba {
 __attribute__((visibility("hidden"))) void enqueue_chol_factor(double* W, int n, int ldw, int* flags, long long* trace, double* Xinv, double* Tinv,
-                                                               bool early, hipStream_t stream) {
+                                                               bool early, hipStream_t stream, bool without_last) {
   const int nbk = (n + NB - 1) / NB;
-  for (int k = -1; k < nbk; ++k) {
+  // without_last (the solver, nbk >= 2): launch nbk - 1 is left to the caller's k_chol_last_apply, which also takes the backward substitution
+  for (int k = -1; k < nbk - (without_last ? 1 : 0); ++k) {
     // step k: panel k solved for the blocks below it (and the rhs row), D_k+1 factored; extra workgroups apply the pending rank-NB updates to
     // the blocks right of the current panel and build T
     if (early)
@@ -1777,7 +1811,15 @@ __attribute__((visibility("hidden"))) bool chol_early_from_env() {
 
 static int enqueue_cholesky(cba_problem* p) {
   const int n = p->ncp, nbk = (n + NB - 1) / NB;
-  enqueue_chol_factor(p->Lbuf, n, p->ldw, p->flags, p->chol_trace, p->Xinv, p->Tinv, p->chol_early, p->stream);
+  // (one block: the first and the last launch coincide, the old sequence stays)
+  const bool fold_last = p->chol_ends && nbk >= 2;
+  enqueue_chol_factor(p->Lbuf, n, p->ldw, p->flags, p->chol_trace, p->Xinv, p->Tinv, p->chol_early, p->stream, fold_last);
+  if (fold_last) {
+    const dim3 grid(chol_last_apply_workgroups(nbk));
+    if (p->chol_early) hipLaunchKernelGGL(k_chol_last_apply<true>, grid, dim3(CHOL_THREADS), 0, p->stream, (const double*)p->Lbuf, n, p->ldw, (const double*)p->Xinv, (const double*)p->Tinv, p->s);
+    else hipLaunchKernelGGL(k_chol_last_apply<false>, grid, dim3(CHOL_THREADS), 0, p->stream, (const double*)p->Lbuf, n, p->ldw, (const double*)p->Xinv, (const double*)p->Tinv, p->s);
+    return CBA_OK;
+  }
   hipLaunchKernelGGL(k_chol_apply, dim3(nbk), dim3(APPLY_THREADS), (size_t)n * 8, p->stream, (const double*)p->Tinv, (const double*)p->Lbuf, n, p->ldw, p->s);
   return CBA_OK;
 }
@@ -2116,8 +2158,11 @@ static int step_enqueue(cba_problem* p, double radius, bool compact, unsigned lo
   const PubArgs pub{p->scal, 49, p->flags, p->d_hscal, p->d_hflags, seq, p->partial1, p->grid, 24, p->partial4, ft ? p->grid + 1 : vg, 28,
                     {p->x, p->g, p->sinv_state_c, p->s}, bnd ? p->d_hbcam : (double*)nullptr, p->ncp,
                     spec_test ? p->spec_word : (int*)nullptr, p->ftol, p->xtol, p->cost_pending ? NAN : p->cost_x};
+  // (the speculative scale pass of the trial point, see below, inside the reducing launch where it can be)
+  const bool sf = scale_fusable<NC>(p, compact);
+  const ScaleArgs sa{p->V2, p->lay, 0, p->sinv2, p->sinv, p->x_new, p->g2, p->v1, p->partial4b, p->partial_gmax};
   rc = run_build_into<NC>(p, p->x_new, p->tab_new, p->V2, p->g2, p->U2, 24, p->scal + 42, true, compact, 0, ft ? &tsrc : nullptr,
-                          compact ? &pub : nullptr);  // (the build is skipped when need_host; the reduction and the packet are not)
+                          compact ? &pub : nullptr, sf ? &sa : nullptr);  // (the build is skipped when need_host; the reduction and the packet are not)
   if (rc) return rc;
   if (!compact) return CBA_OK;
   *seq_out = seq;
@@ -2125,18 +2170,19 @@ static int step_enqueue(cba_problem* p, double radius, bool compact, unsigned lo
   // decides and enqueues the next iteration (k_publish -> host -> first kernel of the next cba_step used to be an idle gap per iteration)
   p->spec_enqueued = false; p->spec_jv_enqueued = false;
   {
-    {
+    if (!sf) {
       ScopedTimer t(p, T_SCALE_SCALARS);
       const BoundArgs ba2 = bnd ? BoundArgs{p->lb_dev, p->ub_dev, p->sinv_state_c, p->sinv_state_c2, p->cam_diag2} : BoundArgs{};
       auto launch_sl2 = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(vg), dim3(BLOCK), 0, p->stream, p->U2, p->V2, p->param_cam, p->param_loc, p->lay, 0, p->sinv2,
-                           (const double*)nullptr, p->x_new, p->g2, p->v1, p->partial4b, p->partial1, (const double*)p->sinv, ba2);
+                           (const double*)nullptr, p->x_new, p->g2, p->v1, p->partial4b, p->partial_gmax, (const double*)p->sinv, ba2);
       };
       if (bnd) launch_sl2(k_scale_lin<NC, true>); else launch_sl2(k_scale_lin<NC, false>);
+      p->scale_rows = vg;
     }
     // max |g| of the trial point goes to the host's mailbox by itself where the solve ends there (workgroup 0 of the skipped pass, or a
     // one-workgroup launch in the place of a pass that is not enqueued): cba_gradient_norm finds it waiting
-    const SpecSkip skip{spec_test ? p->spec_word : (const int*)nullptr, p->partial1, vg, p->d_hscal, seq};
+    const SpecSkip skip{spec_test ? p->spec_word : (const int*)nullptr, p->partial_gmax, p->scale_rows, p->d_hscal, seq};
     p->gnorm_seq = seq;
     if (!(p->spec_skip && last_trial)) {
       int rows_jv = 0;
@@ -2242,14 +2288,15 @@ static int run_gradient_norm(cba_problem* p, double* out) {
     p->spec_valid = false;
     ScopedTimer t(p, T_SCALE_SCALARS);
     hipLaunchKernelGGL((k_scale_lin<NC, false>), dim3(vg), dim3(BLOCK), 0, p->stream, p->Upacked, p->V, p->param_cam, p->param_loc, p->lay, p->first_scale ? 1 : 0,
-                       p->sinv, p->con.n_con ? (const double*)p->con.cdiag : (const double*)nullptr, p->x, p->g, p->v1, p->partial4b, p->partial1,
+                       p->sinv, p->con.n_con ? (const double*)p->con.cdiag : (const double*)nullptr, p->x, p->g, p->v1, p->partial4b, p->partial_gmax,
                        (const double*)nullptr, BoundArgs{});
+    p->scale_rows = vg;
     p->first_scale = false;
     p->spec_scale_ready = true;  // (asked again at the same point: the rows are still there)
   }
   {
     ScopedTimer t(p, T_SCALE_SCALARS);
-    hipLaunchKernelGGL(k_reduce_narrow<true>, dim3(1), dim3(BLOCK), 0, p->stream, p->partial1, vg, 1, p->scal + 4);
+    hipLaunchKernelGGL(k_reduce_narrow<true>, dim3(1), dim3(BLOCK), 0, p->stream, p->partial_gmax, p->scale_rows, 1, p->scal + 4);
   }
   const int rc = sync_scalars(p, 16);
   if (rc) return rc;
@@ -2825,6 +2872,16 @@ int cba_get_vector(cba_problem* p, int32_t which, double* out) {
     case CBA_VEC_GRAD: src = p->g; break;
     case CBA_VEC_STEP: src = p->s; break;
     case CBA_VEC_SCALE_INV: src = p->sinv; break;
+    case CBA_VEC_JG_INPUT: src = p->v1; break;
+    case CBA_VEC_SCALE_OWN: {  // k_scale_update's first-call rule on the blocks of the current point, into scratch (v2 is dead between solver calls)
+      if (!p->have_build) return fail(CBA_ERR_INVALID, "cba_get_vector: no linearisation at the current point");
+      const double* cd = p->con.n_con ? (const double*)p->con.cdiag : (const double*)nullptr;
+      const int vg = vec_grid(p->lay.total());
+      if (p->nct == 9) hipLaunchKernelGGL((k_scale_update<9>), dim3(vg), dim3(BLOCK), 0, p->stream, p->Upacked, p->V, p->param_cam, p->param_loc, p->lay, 1, p->v2, cd);
+      else hipLaunchKernelGGL((k_scale_update<6>), dim3(vg), dim3(BLOCK), 0, p->stream, p->Upacked, p->V, p->param_cam, p->param_loc, p->lay, 1, p->v2, cd);
+      src = p->v2;
+      break;
+    }
     default: return fail(CBA_ERR_INVALID, "cba_get_vector: unknown vector %d", which);
   }
   HIPCHK(hipStreamSynchronize(p->stream));

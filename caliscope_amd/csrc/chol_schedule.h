@@ -169,4 +169,37 @@ inline void chol_for_each_action(int nbk, int k, int wg, bool with_inverse, F&& 
   }
 }
 
+// ---- the end of the solver's launch sequence (k_chol_last_apply of cba_kernels.h, enqueue_cholesky of cba_lib.hip; CBA_CHOL_ENDS=0: off) --------------
+// nbk >= 2: launches -1 .. nbk - 2 as above, then ONE launch of nbk workgroups in the place of launch nbk - 1 and the backward substitution
+// (k_chol_apply).  Launch nbk - 1 is the rhs row's panel workgroup, y_last = W_nbk,last X_last^T, and the inverse workgroups (last, j < last) that
+// finish the last block column of T; here workgroup j, block row j of T, forms y_last and T(j, last) PRIVATELY (the same instructions: the parent
+// schedule's pending update P_last-1 of the rhs block included) and goes on to the row sums x_j = sum_{c >= j} T(j, c) y_c.  It writes x only:
+// nothing reads T, y or L after the solve, so the launch has no shared block to race on.
+CHOL_HD inline int chol_last_apply_workgroups(int nbk) { return nbk; }
+
+// f(CholRef) for every block workgroup j of the last launch reads
+template <bool EARLY, class F>
+inline void chol_last_apply_for_each_read(int nbk, int j, F&& f) {
+  const int last = nbk - 1;
+  const auto rd = [&](int buf, int bi, int bj) { f(CholRef{buf, bi, bj}); };
+  rd(CHOL_W, nbk, last); rd(CHOL_XINV, last, 0);                              // y_last
+  if (!EARLY) { rd(CHOL_W, nbk, last - 1); rd(CHOL_W, last, last - 1); }      // ... behind the pending update of the parent schedule
+  if (j < last) {                                                             // T(j, last): the term of panel last - 1, then X_last
+    if (last - 1 != j) rd(CHOL_T, j, last);
+    rd(CHOL_T, j, last - 1); rd(CHOL_W, last, last - 1);
+  } else {
+    rd(CHOL_T, last, last);
+  }
+  for (int c = j; c < last; ++c) { rd(CHOL_T, j, c); rd(CHOL_W, nbk, c); }    // the row sums over the finished columns
+}
+
+// f(CholAct, i, j, m) for what workgroup j does to ITS OWN copy of the rhs block (nbk, last), in program order (every workgroup the same)
+template <bool EARLY, class F>
+inline void chol_last_apply_for_each_action(int nbk, int j, F&& f) {
+  (void)j;
+  const int last = nbk - 1;
+  if (!EARLY) f(CHOL_ACT_APPLY, nbk, last, last - 1);
+  f(CHOL_ACT_SOLVE, nbk, last, last);
+}
+
 }  // namespace cba

@@ -283,7 +283,10 @@ typedef struct {
 int cba_solve(cba_problem* p, const double* x0, const cba_solve_options* opt, double* x_out, cba_result* out);
 
 /* ---- parity hooks / readback -------------------------------------------------------------------- */
-enum { CBA_VEC_X = 0, CBA_VEC_X_NEW = 1, CBA_VEC_GRAD = 2, CBA_VEC_STEP = 3, CBA_VEC_SCALE_INV = 4 };
+enum { CBA_VEC_X = 0, CBA_VEC_X_NEW = 1, CBA_VEC_GRAD = 2, CBA_VEC_STEP = 3, CBA_VEC_SCALE_INV = 4,
+       /* cba_get_vector only: g / scale_inv^2 as the last scale pass left it (the vector of the J.g pass), and the Jacobi scale the normal blocks of
+        * the current point give by themselves, sqrt(diag(J^T J)) with zeros -> 1 (what the monotone maximum of scale_inv is taken against) */
+       CBA_VEC_JG_INPUT = 5, CBA_VEC_SCALE_OWN = 6 };
 
 /* Download a device vector in the reference layout (length n). */
 int cba_get_vector(cba_problem* p, int32_t which, double* out);
