@@ -1,6 +1,8 @@
 """caliscope_amd.reconstruction without a GPU: the routines of csrc/trajectory_math.h in their g++ build (tests/trajectory_native.py)
 against pandas (`_fill_track_gaps`), scipy (`filtfilt`) and the reference's own tables, the whole call through `_solver`, and the
-refusals.  The device kernels call the same routines: tests/test_reconstruction_gpu.py."""
+refusals.  The device kernels call the same routines: tests/test_reconstruction_gpu.py, and on the edge scenes of
+tests/trajectory_scenes.py, which run here too, tests/test_reconstruction_edges_gpu.py."""
+import functools
 from pathlib import Path
 
 import numpy as np
@@ -12,6 +14,7 @@ from caliscope_amd.point_data import ImagePoints, WorldPoints
 from caliscope_amd.reconstruction import filter_coefficients, reconstruct_trajectories, reconstruct_xyz, trajectory_grid
 from caliscope_amd.synthetic import ring_camera_array
 from tests import trajectory_native as N
+from tests import trajectory_scenes as S
 
 TABLES = sorted((Path(__file__).parent / "golden" / "reference_host").glob("tables_*.npz"))
 
@@ -61,6 +64,24 @@ def test_the_filter_equals_scipy_filtfilt_bit_for_bit(order, fps, cutoff, length
     want = filtfilt(*butter(order, cutoff, btype="low", fs=fps, output="ba"), x)
     assert filtered
     assert np.array_equal(N.bits(y), N.bits(want)), float(np.max(np.abs(y - want)) / np.max(np.abs(x)))
+
+
+@pytest.mark.parametrize("order", range(1, 9))
+def test_the_filter_equals_scipy_filtfilt_at_every_order(order):
+    """traj_lfilter_step keeps its state with fixed trip counts and a select per entry, so every order runs other code; the padding
+    and both reflections depend on the order too.  Three pairs of frame rate and cutoff, the fewest samples the order filters, 64
+    and 300."""
+    for fps, cutoff in ((30.0, 6.0), (60.0, 4.0), (120.0, 10.0)):
+        o, b, a, zi = filter_coefficients((fps, cutoff, order))
+        assert o == order and len(b) == len(a) == order + 1 and len(zi) == order
+        want_ba = butter(order, cutoff, btype="low", fs=fps, output="ba")
+        for n in (3 * (order + 1) + 1, 64, 300):
+            rng = np.random.default_rng(1000 * order + n)
+            x = np.cumsum(rng.normal(0, 0.01, n)) + 0.3 * np.sin(np.arange(n) * 0.11) + rng.normal(0, 0.002, n) + 1.5
+            y, filtered = N.filtfilt(x, o, b, a, zi)
+            want = filtfilt(*want_ba, x)
+            assert filtered and not np.array_equal(y, x)
+            assert np.array_equal(N.bits(y), N.bits(want)), (fps, cutoff, n, float(np.max(np.abs(y - want)) / np.max(np.abs(x))))
 
 
 @pytest.mark.parametrize("order", [1, 2, 3, 8])
@@ -161,6 +182,78 @@ def test_the_3d_stages_of_the_whole_call_equal_the_host_chain(xy_gap, xyz_gap, s
     assert list(got.df.columns) == N.WORLD_COLS and solver.calls == 2
     assert np.array_equal(N.keyed(got.df), N.keyed(want.df), equal_nan=True)
     assert np.array_equal(got.df[N.WORLD_COLS[:3]].to_numpy(), N.keyed(got.df)[:, :3].astype(np.int64))  # sorted by (sync, object, keypoint)
+
+
+# ---- the edge scenes of tests/trajectory_scenes.py (on the device: tests/test_reconstruction_edges_gpu.py) --------------------------------
+
+@pytest.mark.parametrize("gap", [0, 3])
+@pytest.mark.parametrize("name", ["WIDE", "LONG"])
+def test_the_edge_scenes_fill_the_grids_of_the_host_chain(name, gap):
+    """Grids bit for bit, the per-frame mean within frame_time_bound, and a frame without a row from any camera NaN here exactly
+    where the pandas mean has no entry (LONG without the 2-D fill has such frames, two of them in a row)."""
+    sc = S.SCENES[name]()
+    ip, cams = sc.image_points, sc.cameras
+    grid = trajectory_grid(ip, cams)
+    got = N.HarnessTrajectorySolver().reconstruct(grid, xy_gap=gap, want_grids=True)
+    xy, ft, mean, filled = N.host_grid(ip, grid, gap)
+    assert np.array_equal(np.isnan(got.xy_filled), np.isnan(xy)) and np.array_equal(np.isnan(got.ft_filled), np.isnan(ft))
+    assert np.array_equal(got.xy_filled, xy, equal_nan=True) and np.array_equal(got.ft_filled, ft, equal_nan=True)
+    if gap:
+        assert np.isnan(xy).sum() < np.isnan(N.host_grid(ip, grid, 0)[0]).sum()
+    empty = np.isnan(mean)
+    assert np.array_equal(np.isnan(got.frame_time), empty)
+    assert np.array_equal(empty, np.isnan(ft).all(axis=0).reshape(grid.n_frames, grid.n_traj).all(axis=1))
+    if name == "LONG" and gap == 0:
+        assert empty.sum() >= 2 and (np.diff(np.flatnonzero(empty)) == 1).any() and empty[[128, 129]].all()
+    if name == "WIDE":
+        assert not empty.any()
+    syncs = (np.arange(grid.n_frames) + grid.sync_min)[~empty]
+    assert np.all(np.abs(got.frame_time[~empty] - mean[~empty]) <= N.frame_time_bound(filled, syncs))
+    views = (~np.isnan(xy[grid.cam_posed.astype(bool), :, 0])).sum(axis=0)
+    assert np.array_equal(got.valid, (views >= 2).astype(np.uint8))
+    assert np.isnan(got.slot_time[got.valid == 0]).all() and np.isfinite(got.slot_time[got.valid == 1]).all()
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_base(name, xy_gap):
+    """The harness's own triangulated table of a scene: what its 3-D stages are compared from."""
+    sc = S.SCENES[name]()
+    return reconstruct_trajectories(sc.image_points, sc.cameras, xy_gap_fill=xy_gap, _solver=N.HarnessTrajectorySolver())
+
+
+@pytest.mark.parametrize("xy_gap,xyz_gap", [(0, 1), (0, 3), (3, 3)])
+@pytest.mark.parametrize("name", ["WIDE", "LONG"])
+def test_the_edge_scenes_fill_the_3d_holes_of_the_host_chain(name, xy_gap, xyz_gap):
+    """On LONG without the 2-D fill the line of the times runs across frames that have no time of their own."""
+    sc = S.SCENES[name]()
+    base = _edge_base(name, xy_gap)
+    want = base.fill_gaps(xyz_gap)
+    assert len(want) > len(base)
+    got = reconstruct_trajectories(sc.image_points, sc.cameras, xy_gap_fill=xy_gap, xyz_gap_fill=xyz_gap, _solver=N.HarnessTrajectorySolver())
+    assert np.array_equal(N.keyed(got.df), N.keyed(want.df)) and np.isfinite(N.keyed(got.df)).all()
+    if name == "LONG" and xy_gap == 0:
+        rows = set(sc.image_points.df["sync_index"])
+        assert len(set(got.df["sync_index"]) - rows) >= 2 and not set(base.df["sync_index"]) - rows
+
+
+@pytest.mark.parametrize("order", [1, 2, 5, 8])
+@pytest.mark.parametrize("name", ["WIDE", "LONG"])
+def test_the_edge_scenes_are_filtered_as_the_host_chain_filters_them(name, order):
+    sc = S.SCENES[name]()
+    unsmoothed = _edge_base(name, S.GAP).fill_gaps(S.GAP)
+    counts = unsmoothed.df.groupby(["object_id", "keypoint_id"]).size().to_numpy()
+    assert np.array_equal(counts, S.samples(sc))
+    want = unsmoothed.smooth(30.0, 6.0, order)
+    got = reconstruct_trajectories(sc.image_points, sc.cameras, xy_gap_fill=S.GAP, xyz_gap_fill=S.GAP, smooth=(30.0, 6.0, order),
+                                   _solver=N.HarnessTrajectorySolver())
+    rows, plain = N.keyed(got.df), N.keyed(unsmoothed.df)
+    assert np.array_equal(N.bits(rows), N.bits(N.keyed(want.df)))
+    traj = (rows[:, 1] * 7 + rows[:, 2]).astype(np.int64)
+    changed = np.array([not np.array_equal(rows[traj == j, 3:6], plain[traj == j, 3:6]) for j in range(len(counts))])
+    assert np.array_equal(changed, counts > 3 * order)
+    if name == "WIDE":
+        assert counts[0] == 3 and counts[84] == 3 * (8 + 1) + 1 and not changed[0] and changed[84] and changed[85]
+        assert np.array_equal(N.bits(rows[traj == 0]), N.bits(plain[traj == 0]))
 
 
 def test_reconstruct_xyz_writes_the_table_or_nothing(scene, tmp_path):

@@ -14,6 +14,7 @@ import pytest
 from caliscope_amd.point_data import ImagePoints, WorldPoints
 from caliscope_amd.reconstruction import DeviceTrajectorySolver, reconstruct_trajectories, reconstruct_xyz, trajectory_grid
 from tests import trajectory_native as N
+from tests.trajectory_native import _compare, _time_bound_after_fill
 
 pytestmark = pytest.mark.gpu
 
@@ -31,18 +32,6 @@ def _host_triangulated(short, xy_gap):
     return filled.df, filled.triangulate(cams)
 
 
-def _compare(got: WorldPoints, want: WorldPoints, time_bound, what):
-    """Keys identical, xyz bit for bit, frame_time within `time_bound` (per row, or one figure)."""
-    a, b = N.keyed(got.df), N.keyed(want.df)
-    assert a.shape == b.shape and np.array_equal(a[:, :3], b[:, :3]), (what, a.shape, b.shape)
-    scale = np.max(np.abs(b[:, 3:6]))
-    print(f"{what}: {len(a)} rows, max |xyz - host| / max|xyz| = {np.max(np.abs(a[:, 3:6] - b[:, 3:6])) / scale:.3e}, "
-          f"max |frame_time - host| = {np.max(np.abs(a[:, 6] - b[:, 6])):.3e} (bound {np.max(time_bound):.3e})")
-    assert np.array_equal(N.bits(a[:, 3:6]), N.bits(b[:, 3:6])), what
-    assert np.all(np.abs(a[:, 6] - b[:, 6]) <= time_bound), what
-    return a
-
-
 @pytest.mark.parametrize("xy_gap", [0, 1, 3])
 def test_fill_and_triangulation_equal_the_host_chain(xy_gap):
     ip, cams, _ = _scene()
@@ -55,13 +44,6 @@ def test_fill_and_triangulation_equal_the_host_chain(xy_gap):
     assert ((50, 0, 2) in key) == (xy_gap >= 1) and ((51, 0, 2) in key) == (xy_gap >= 2)  # triangulable only through the 2-D fill
     assert (5, 0, 1) in key and (6, 0, 1) not in key                                          # one posed + the unposed camera: no row
     assert ((20, 1, 3) in key) == (xy_gap >= 1) and (45, 1, 3) not in key                     # the 30-frame hole
-
-
-def _time_bound_after_fill(filled, want):
-    """The line between two times that are each within B of the host's is within B of the host's line, plus the rounding of its three
-    operations on either side (2^-51 max|t|)."""
-    t = want.df["frame_time"].to_numpy()
-    return np.max(N.frame_time_bound(filled, want.df["sync_index"].to_numpy())) + 2.0**-51 * np.max(np.abs(t))
 
 
 @pytest.mark.parametrize("xy_gap,xyz_gap", [(0, 1), (0, 3), (3, 3)])

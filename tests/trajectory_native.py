@@ -8,6 +8,7 @@ import functools
 import numpy as np
 import pandas as pd
 
+from caliscope_amd.point_data import WorldPoints
 from caliscope_amd.reconstruction import TrajDesc, TrajOut, run_trajectory_call
 from tests.native_build import CSRC, NATIVE, load_native
 
@@ -86,6 +87,32 @@ POSED, UNPOSED = (0, 2, 5), 3                       # cam_ids; camera 2 is a fis
 TRAJ = ((0, 0), (0, 1), (0, 2), (1, 3), (1, 7))     # (object_id, keypoint_id) of trajectory 0..4
 
 
+def _pixels(model, rvec, translation, matrix, dist, xyz):
+    return model(xyz, rvec, translation, matrix, dist)[0]
+
+
+def rig():
+    """(cam_id, CameraData, project) of the four cameras, in the order their rows are generated: four of a ring of five, 72 degrees
+    apart, so that no rotation matrix has exact zeros (products that round); camera 2 is a fisheye, camera 3 has no pose.
+    `project(xyz[n, 3])` gives the pixels [n, 2] of the camera where it stands in the ring, posed or not."""
+    from caliscope_amd.cameras import CameraData, matrix_to_rvec
+    from caliscope_amd.synthetic import ring_camera_array
+    from oracle import camera_model as cm
+
+    ring = ring_camera_array(5).cameras
+    out = []
+    for k, cid in enumerate((0, 2, 5, 3)):
+        src = ring[k]
+        fisheye = cid == 2
+        dist = np.array([0.05, -0.02, 0.004, 0.001]) if fisheye else src.distortions
+        model = cm.project_fisheye if fisheye else cm.project_pinhole
+        posed = cid != UNPOSED
+        camera = CameraData(cam_id=cid, size=src.size, matrix=src.matrix.copy(), distortions=dist.copy(), fisheye=fisheye,
+                            rotation=src.rotation if posed else None, translation=src.translation if posed else None)
+        out.append((cid, camera, functools.partial(_pixels, model, matrix_to_rvec(src.rotation), src.translation, src.matrix, dist)))
+    return out
+
+
 def recording(short: int = 10, seed: int = 5):
     """(ImagePoints, CameraArray, ground truth [70, 5, 3]) — 3 posed cameras and an unposed one, 5 trajectories of 2 objects over 70
     frames from sync index 17 (350 slots).  Rows are taken out so that there are, with f the frame from 0:
@@ -98,25 +125,17 @@ def recording(short: int = 10, seed: int = 5):
     * trajectory 3: gone from every camera for 30 frames (20-49), and again at f 52 (1), 55-57 (3) and 60-63 (4);
     * trajectory 4: seen during the first `short` frames only.
     """
-    from caliscope_amd.cameras import CameraArray, CameraData, matrix_to_rvec
+    from caliscope_amd.cameras import CameraArray
     from caliscope_amd.point_data import ImagePoints
-    from caliscope_amd.synthetic import ring_camera_array
-    from oracle import camera_model as cm
 
     rng = np.random.default_rng(seed)
-    ring = ring_camera_array(5).cameras  # four of five: 72 degrees apart, no rotation matrix with exact zeros (products that round)
-    ids = (0, 2, 5, 3)
     frames = np.arange(N_FRAMES)
     base = np.array([[0.2, 0.1, 0.5], [-0.3, 0.2, 0.8], [0.1, -0.3, 0.3], [0.0, 0.4, 0.9], [-0.2, -0.2, 0.6]])
     phase = 0.09 * frames[:, None, None] + np.arange(5)[None, :, None] + np.array([0.0, 1.3, 2.1])[None, None, :]
     truth = base[None] + 0.15 * np.sin(phase)
     cams, rows = {}, []
-    for k, cid in enumerate(ids):
-        src = ring[k]
-        fisheye = cid == 2
-        dist = np.array([0.05, -0.02, 0.004, 0.001]) if fisheye else src.distortions
-        project = cm.project_fisheye if fisheye else cm.project_pinhole
-        uv = project(truth.reshape(-1, 3), matrix_to_rvec(src.rotation), src.translation, src.matrix, dist)[0].reshape(N_FRAMES, 5, 2)
+    for k, (cid, camera, project) in enumerate(rig()):
+        uv = project(truth.reshape(-1, 3)).reshape(N_FRAMES, 5, 2)
         uv = uv + rng.normal(0.0, 0.3, uv.shape)
         seen = np.ones((N_FRAMES, 5), dtype=bool)
         if cid == 0:
@@ -136,9 +155,7 @@ def recording(short: int = 10, seed: int = 5):
         obj, kp = np.array(TRAJ)[j, 0], np.array(TRAJ)[j, 1]
         rows.append(pd.DataFrame({"sync_index": f + SYNC0, "cam_id": cid, "object_id": obj, "keypoint_id": kp, "img_loc_x": uv[f, j, 0],
                                   "img_loc_y": uv[f, j, 1], "frame_time": (f + SYNC0) / 30.0 + 1e-3 * k}))
-        posed = cid != UNPOSED
-        cams[cid] = CameraData(cam_id=cid, size=src.size, matrix=src.matrix.copy(), distortions=dist.copy(), fisheye=fisheye,
-                               rotation=src.rotation if posed else None, translation=src.translation if posed else None)
+        cams[cid] = camera
     df = pd.concat(rows, ignore_index=True)
     df = df.iloc[rng.permutation(len(df))].reset_index(drop=True)  # the table arrives in no particular order
     return ImagePoints(df), CameraArray(cams), truth
@@ -173,3 +190,22 @@ def host_grid(image_points, grid, xy_gap):
     xy[c, s, 0], xy[c, s, 1], ft[c, s] = df["img_loc_x"].to_numpy(), df["img_loc_y"].to_numpy(), df["frame_time"].to_numpy()
     mean = df.groupby("sync_index")["frame_time"].mean().reindex(np.arange(grid.n_frames) + grid.sync_min).to_numpy()
     return xy, ft, mean, df
+
+
+def _compare(got: WorldPoints, want: WorldPoints, time_bound, what):
+    """Keys identical, xyz bit for bit, frame_time within `time_bound` (per row, or one figure)."""
+    a, b = keyed(got.df), keyed(want.df)
+    assert a.shape == b.shape and np.array_equal(a[:, :3], b[:, :3]), (what, a.shape, b.shape)
+    scale = np.max(np.abs(b[:, 3:6]))
+    print(f"{what}: {len(a)} rows, max |xyz - host| / max|xyz| = {np.max(np.abs(a[:, 3:6] - b[:, 3:6])) / scale:.3e}, "
+          f"max |frame_time - host| = {np.max(np.abs(a[:, 6] - b[:, 6])):.3e} (bound {np.max(time_bound):.3e})")
+    assert np.array_equal(bits(a[:, 3:6]), bits(b[:, 3:6])), what
+    assert np.all(np.abs(a[:, 6] - b[:, 6]) <= time_bound), what
+    return a
+
+
+def _time_bound_after_fill(filled, want):
+    """The line between two times that are each within B of the host's is within B of the host's line, plus the rounding of its three
+    operations on either side (2^-51 max|t|)."""
+    t = want.df["frame_time"].to_numpy()
+    return np.max(frame_time_bound(filled, want.df["sync_index"].to_numpy())) + 2.0**-51 * np.max(np.abs(t))
