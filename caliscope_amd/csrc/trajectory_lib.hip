@@ -1,6 +1,8 @@
 // cba_reconstruct_trajectories of libcaliscope_ba.so (C ABI: include/caliscope_trajectory.h): the 2-D tracks of a whole recording
-// to filled, triangulated, filled and smoothed 3-D trajectories on one dense grid.  What a thread does, and the checks, are
-// trajectory_math.h (shared with tests/native/trajectory_harness.cpp); this file holds the kernels and the entry point.
+// to filled, triangulated, filled and smoothed 3-D trajectories on one dense grid; and cba_reconstruct_trajectories_refined
+// (include/caliscope/trajectory_refine.h), the same call with the robust reprojection refinement of every point in between.  What a
+// thread does, and the checks, are trajectory_math.h and trajectory_refine_math.h (shared with tests/native/trajectory_harness.cpp
+// and trajectory_refine_harness.cpp); this file holds the kernels and the entry points.
 //
 //   k_traj_fill2d       one thread per uploaded row (sorted by camera, trajectory, frame): the row's cell of xy[c][s][2] / ft[c][s],
 //                       and the first min(hole, xy_gap) cells of the hole between it and the next row of its track.  Holes of
@@ -8,6 +10,8 @@
 //                       written twice.  Both grids are NaN (all bits set) before it runs.
 //   k_traj_frame_time   one thread per frame: mean of the times of the frame in a fixed order.
 //   k_traj_triangulate  one thread per slot s = f * n_traj + j; neighbouring threads read neighbouring cells of every camera's grid.
+//   k_traj_refine       (refined call only) one thread per slot, the same access pattern as k_traj_triangulate: Levenberg-Marquardt on the
+//                       slot's point in registers, the views in use in the byte grid view_state[c][s].
 //   k_traj_fill3d       one thread per slot, in place (see traj_fill3d_cell for why that is safe).
 //   k_traj_filtfilt     one thread per (trajectory, coordinate); thread t reads xyz[f][t] and its scratch column scratch[e][t], so
 //                       a wave's loads and stores are contiguous.
@@ -19,6 +23,7 @@
 #include <vector>
 
 #include "trajectory_math.h"
+#include "trajectory_refine_math.h"
 #include "device_call.h"
 
 using namespace cba;
@@ -56,6 +61,18 @@ k_traj_triangulate(int32_t n_cams, int64_t n_traj, int64_t n_slots, const uint8_
 }
 
 __global__ void __launch_bounds__(TRAJ_BLOCK)
+k_traj_refine(int32_t n_cams, int64_t n_slots, const uint8_t* __restrict__ cam_posed, const int32_t* __restrict__ cam_model,
+              const double* __restrict__ cam_intr, const double* __restrict__ cam_P, const double* __restrict__ xy, int loss, double f_scale,
+              int max_iter, double reject_px, int max_reject, int min_views, const uint8_t* __restrict__ valid, double* __restrict__ xyz,
+              uint8_t* view_state, int32_t* __restrict__ views, double* __restrict__ rms_px, double* __restrict__ max_px,
+              int32_t* __restrict__ iterations, uint8_t* __restrict__ status) {
+  const int64_t s = (int64_t)blockIdx.x * TRAJ_BLOCK + threadIdx.x;
+  if (s >= n_slots) return;
+  traj_refine_slot(n_cams, n_slots, s, cam_posed, cam_model, cam_intr, cam_P, xy, loss, f_scale, max_iter, reject_px, max_reject, min_views, valid,
+                   xyz, view_state, views, rms_px, max_px, iterations, status);
+}
+
+__global__ void __launch_bounds__(TRAJ_BLOCK)
 k_traj_fill3d(int64_t n_frames, int64_t n_traj, int64_t n_slots, int max_gap, uint8_t* valid, double* xyz, double* time) {
   const int64_t s = (int64_t)blockIdx.x * TRAJ_BLOCK + threadIdx.x;
   if (s >= n_slots) return;
@@ -72,14 +89,15 @@ k_traj_filtfilt(int64_t n_frames, int64_t n_traj, int order, const double* __res
 
 unsigned blocks(int64_t n) { return (unsigned)((n + TRAJ_BLOCK - 1) / TRAJ_BLOCK); }
 
-}  // namespace
-
-extern "C" int cba_reconstruct_trajectories(const cba_traj_desc* d, int32_t device, cba_traj_out* out) {
-  const char* what = "cba_reconstruct_trajectories";
-  if (!d || !out) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
+// Both entry points.  refined: r and q belong to the call (r is checked, not assumed); otherwise nothing of the refinement is
+// checked, allocated or launched.
+int reconstruct(const char* what, const cba_traj_desc* d, bool refined, const cba_traj_refine* r, int32_t device, cba_traj_out* out,
+                cba_traj_quality* q) {
+  if (!d || !out || (refined && !q)) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
   // everything that does not need the device first: the sizes, the filter, every index the kernels use
   std::string msg;
-  int rc = traj_validate(d, (double)d->memory_limit, msg);  // (memory_limit 0: the free memory is asked for below)
+  // (memory_limit 0: the free memory is asked for below)
+  int rc = refined ? traj_refined_validate(d, r, (double)d->memory_limit, msg) : traj_validate(d, (double)d->memory_limit, msg);
   if (rc) return err(rc, msg);
   const int32_t n_cams = d->n_cams;
   const int64_t n_frames = d->n_frames, n_traj = d->n_traj, n_rows = d->n_rows, n_slots = n_frames * n_traj;
@@ -95,6 +113,14 @@ extern "C" int cba_reconstruct_trajectories(const cba_traj_desc* d, int32_t devi
     for (int64_t i = 0; i < (int64_t)n_cams * n_slots; ++i) {
       if (out->xy_filled) out->xy_filled[2 * i] = out->xy_filled[2 * i + 1] = nan;
       if (out->ft_filled) out->ft_filled[i] = nan;
+      if (refined && q->view_state) q->view_state[i] = VIEW_NONE;
+    }
+    for (int64_t s = 0; refined && s < n_slots; ++s) {
+      if (q->views) q->views[s] = 0;
+      if (q->rms_px) q->rms_px[s] = nan;
+      if (q->max_px) q->max_px[s] = nan;
+      if (q->iterations) q->iterations[s] = 0;
+      if (q->status) q->status[s] = REFINE_NO_POINT;
     }
     return CBA_OK;
   }
@@ -106,8 +132,8 @@ extern "C" int cba_reconstruct_trajectories(const cba_traj_desc* d, int32_t devi
     if (hipMemGetInfo(&free_bytes, &total_bytes) != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": hipMemGetInfo failed");
     memory = (double)free_bytes;
   }
-  if (traj_device_bytes(d) > memory) {
-    rc = traj_validate(d, memory, msg);  // (puts the message together)
+  if (traj_device_bytes(d) + (refined ? traj_refine_device_bytes(d) : 0.0) > memory) {
+    rc = refined ? traj_refined_validate(d, r, memory, msg) : traj_validate(d, memory, msg);  // (puts the message together)
     return err(rc ? rc : CBA_ERR_UNSUPPORTED, msg);
   }
   if (n_slots > (int64_t)0x7fffffff * TRAJ_BLOCK || n_rows > (int64_t)0x7fffffff * TRAJ_BLOCK)
@@ -134,6 +160,13 @@ extern "C" int cba_reconstruct_trajectories(const cba_traj_desc* d, int32_t devi
   const double* da = d->filter_b ? buf.in(d->filter_a, order + 1) : nullptr;
   const double* dzi = d->filter_b ? buf.in(d->filter_zi, order) : nullptr;
   double* dscratch = d->filter_b ? buf.make<double>(n_frames + 2 * traj_pad(order), n_traj, 3) : nullptr;
+  // without the refinement its six buffers stay null
+  uint8_t* dstate = refined ? buf.make<uint8_t>(n_cams, n_slots) : nullptr;
+  int32_t* dviews = refined ? buf.make<int32_t>(n_slots) : nullptr;
+  double* drms = refined ? buf.make<double>(n_slots) : nullptr;
+  double* dmax = refined ? buf.make<double>(n_slots) : nullptr;
+  int32_t* diter = refined ? buf.make<int32_t>(n_slots) : nullptr;
+  uint8_t* dstatus = refined ? buf.make<uint8_t>(n_slots) : nullptr;
   if (buf.status()) return buf.result(what);
 
   // all bits set is a NaN: "no row here"
@@ -145,6 +178,10 @@ extern "C" int cba_reconstruct_trajectories(const cba_traj_desc* d, int32_t devi
   hipLaunchKernelGGL(k_traj_frame_time, dim3(blocks(n_frames)), dim3(TRAJ_BLOCK), 0, 0, n_cams, n_frames, n_traj, n_slots, dft, dframe);
   hipLaunchKernelGGL(k_traj_triangulate, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), 0, 0, n_cams, n_traj, n_slots, dposed, dmodel, dintr, dP, dxy,
                      dframe, d->float32_io ? 1 : 0, dxyz, dvalid, dtime);
+  if (refined)  // (writes every cell of its six buffers)
+    hipLaunchKernelGGL(k_traj_refine, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), 0, 0, n_cams, n_slots, dposed, dmodel, dintr, dP, dxy, (int)r->loss,
+                       r->f_scale, (int)r->max_iter, r->reject_px, (int)r->max_reject, (int)r->min_views, dvalid, dxyz, dstate, dviews, drms, dmax,
+                       diter, dstatus);
   if (d->xyz_gap > 0)
     hipLaunchKernelGGL(k_traj_fill3d, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), 0, 0, n_frames, n_traj, n_slots, (int)d->xyz_gap, dvalid, dxyz, dtime);
   if (d->filter_b)
@@ -157,6 +194,25 @@ extern "C" int cba_reconstruct_trajectories(const cba_traj_desc* d, int32_t devi
   buf.out(out->frame_time, dframe, n_frames);
   buf.out(out->xy_filled, dxy, n_cams, n_slots, 2);
   buf.out(out->ft_filled, dft, n_cams, n_slots);
+  if (refined) {
+    buf.out(q->views, dviews, n_slots);
+    buf.out(q->rms_px, drms, n_slots);
+    buf.out(q->max_px, dmax, n_slots);
+    buf.out(q->iterations, diter, n_slots);
+    buf.out(q->status, dstatus, n_slots);
+    buf.out(q->view_state, dstate, n_cams, n_slots);
+  }
   if (!buf.status()) buf.check(hipDeviceSynchronize());
   return buf.result(what);
+}
+
+}  // namespace
+
+extern "C" int cba_reconstruct_trajectories(const cba_traj_desc* d, int32_t device, cba_traj_out* out) {
+  return reconstruct("cba_reconstruct_trajectories", d, false, nullptr, device, out, nullptr);
+}
+
+extern "C" int cba_reconstruct_trajectories_refined(const cba_traj_desc* d, const cba_traj_refine* refine, int32_t device, cba_traj_out* out,
+                                                    cba_traj_quality* quality) {
+  return reconstruct("cba_reconstruct_trajectories_refined", d, true, refine, device, out, quality);
 }

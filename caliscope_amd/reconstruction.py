@@ -15,8 +15,13 @@ path is tested against.  Differences from that chain, all refusals: two rows of 
 (``static_object_ids``) are not supported.  A trajectory that would reach the filter with ``3 * order < n <= 3 * (order + 1)``
 samples raises ``ValueError`` before anything is launched (scipy raises there in the host chain, after the work is done).
 
+``refine=RefineOptions(...)`` makes ``cba_reconstruct_trajectories_refined`` instead (``caliscope_amd/trajectory_refinement.py``): the
+same launches with the robust reprojection refinement of every point, and the rejection of contradicting views, between the
+triangulation and the 3-D fill.
+
 There is no CPU fallback: without the library or a GPU the call raises ``BackendError``.  ``_solver`` replaces the device call (an
-object with ``reconstruct``, as :class:`DeviceTrajectorySolver`) — the CPU test-suite passes a g++ build of the same routines.
+object with ``reconstruct``, as :class:`DeviceTrajectorySolver`, and for ``refine`` with ``reconstruct_refined``, as
+``DeviceRefinedTrajectorySolver``) — the CPU test-suite passes a g++ build of the same routines.
 """
 
 from __future__ import annotations
@@ -211,19 +216,39 @@ def world_points_of(grid: TrajectoryGrid, result: TrajectoryResult) -> WorldPoin
 
 
 def reconstruct_trajectories(image_points: ImagePoints, camera_array, *, xy_gap_fill: int = 3, xyz_gap_fill: int = 0, smooth=None,
-                             float32_io: bool = True, device_id: int = 0, _solver=None) -> WorldPoints:
+                             float32_io: bool = True, device_id: int = 0, refine=None, return_quality: bool = False, _solver=None):
     """``image_points.fill_gaps(xy_gap_fill).triangulate(camera_array)``, then ``.fill_gaps(xyz_gap_fill)`` and, for
     ``smooth = (fps, cutoff_freq, order)``, ``.smooth(*smooth)`` — in one device call.  A gap of 0 skips that fill, ``smooth=None``
-    the filter.  An empty table, or one without a posed camera, gives an empty table with the ``frame_time`` column."""
+    the filter.  An empty table, or one without a posed camera, gives an empty table with the ``frame_time`` column.
+
+    ``refine`` (a :class:`caliscope_amd.trajectory_refinement.RefineOptions`) makes the call that also refines every triangulated
+    point by its robust reprojection error and drops contradicting views, before the 3-D fill and the filter; the table has the
+    same columns.  ``return_quality=True`` (with ``refine`` only, else ``ValueError``) returns ``(WorldPoints, DataFrame)``, the frame
+    row for row beside the table: its keys, ``n_views``, ``n_rejected``, ``reproj_rms_px``, ``reproj_max_px``, ``status`` and
+    ``rejected_cam_ids``.  ``_solver`` then needs ``reconstruct_refined``."""
+    if return_quality and refine is None:
+        raise ValueError("reconstruct_trajectories: return_quality needs refine (the plain call computes no quality)")
     filt = filter_coefficients(smooth) if smooth is not None else None
-    if len(image_points) == 0:
-        return _empty()
-    grid = trajectory_grid(image_points, camera_array)
-    if not grid.cam_posed.any():
-        return _empty()
-    solver = _solver if _solver is not None else DeviceTrajectorySolver(device_id)
-    result = solver.reconstruct(grid, xy_gap=int(xy_gap_fill), xyz_gap=int(xyz_gap_fill), filt=filt, float32_io=float32_io)
-    return world_points_of(grid, result)
+    if refine is None:
+        if len(image_points) == 0:
+            return _empty()
+        grid = trajectory_grid(image_points, camera_array)
+        if not grid.cam_posed.any():
+            return _empty()
+        solver = _solver if _solver is not None else DeviceTrajectorySolver(device_id)
+        result = solver.reconstruct(grid, xy_gap=int(xy_gap_fill), xyz_gap=int(xyz_gap_fill), filt=filt, float32_io=float32_io)
+        return world_points_of(grid, result)
+    from caliscope_amd import trajectory_refinement as TR
+
+    TR.refine_struct(refine)  # (an unknown loss name is refused for an empty table too)
+    grid = trajectory_grid(image_points, camera_array) if len(image_points) else None
+    if grid is None or not grid.cam_posed.any():
+        world, quality = _empty(), pd.DataFrame(columns=list(TR.QUALITY_COLUMNS))
+    else:
+        solver = _solver if _solver is not None else TR.DeviceRefinedTrajectorySolver(device_id)
+        result, q = solver.reconstruct_refined(grid, refine, xy_gap=int(xy_gap_fill), xyz_gap=int(xyz_gap_fill), filt=filt, float32_io=float32_io)
+        world, quality = world_points_of(grid, result), TR.quality_frame(grid, result, q)
+    return (world, quality) if return_quality else world
 
 
 def reconstruct_xyz(image_points: ImagePoints, camera_array, name: str, output_dir, xy_gap_fill: int = 3, **kw):
