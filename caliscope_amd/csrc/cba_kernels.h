@@ -2195,6 +2195,14 @@ __device__ __forceinline__ double schur_entry(int row, int col, const double* __
   if (row == col) v += lam * sinv[row] * sinv[row] + cam_diag[row];  // cam_diag: zero unless the caller set a bound scaling
   return v;
 }
+// The paired first launch of the dense solve (chol_schedule.h) reads D_0 and U_10 = W_10 from side slots, because one of its workgroups overwrites
+// both blocks of the work matrix in place while the others read them: the producers of the work matrix store entry (row, col) there as well.
+// side_d0 == nullptr: the launch sequence is not paired, nothing is stored.
+__device__ __forceinline__ void chol_side_put(double* __restrict__ side_d0, double* __restrict__ side_u10, int row, int col, double v) {
+  if (!side_d0 || col >= NB || row >= 2 * NB) return;
+  if (row < NB) side_d0[row * NB + col] = v;
+  else side_u10[(row - NB) * NB + col] = v;
+}
 // (Round 6 measured ONE MORE workgroup here that formed the first diagonal block itself and factored it — step k = -1 of the dense solve without its
 // launch: 31 us against 9.5 + 3.5, its 1024 entries being chains of dependent loads; removed again, profiles/r06_experiments.txt.)
 template <int NC>
@@ -2205,7 +2213,8 @@ k_schur_finalize(const double* __restrict__ Sacc, const double* __restrict__ bac
                  const int* __restrict__ param_loc, int ncp, double lam, const double* __restrict__ lam_dev,
                  const double* __restrict__ cam_diag, double* __restrict__ S, double* __restrict__ rhs,
                  double* __restrict__ W, int ldw, const double* __restrict__ red = nullptr, int g = 0, long tile_elems = 0,
-                 const int* __restrict__ group_cam_begin = nullptr, int b_width = 0) {
+                 const int* __restrict__ group_cam_begin = nullptr, int b_width = 0, double* __restrict__ side_d0 = nullptr,
+                 double* __restrict__ side_u10 = nullptr) {
   CBA_STAMP(ST_FINALIZE);
   if (lam_dev) lam = *lam_dev;
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2222,6 +2231,8 @@ k_schur_finalize(const double* __restrict__ Sacc, const double* __restrict__ bac
   S[(long)col * ncp + row] = v;
   W[(long)row * ldw + col] = v;
   W[(long)col * ldw + row] = v;
+  chol_side_put(side_d0, side_u10, row, col, v);
+  chol_side_put(side_d0, side_u10, col, row, v);
 }
 
 // Round 6: k_reg_reduce and k_schur_finalize as ONE launch for the route on which nothing else adds to the reduced system between them (single rank, no
@@ -2243,7 +2254,7 @@ k_reg_finalize(TilePlan tp, const int* __restrict__ tile_wg_begin, const double*
                const double* __restrict__ partial_b, int b_rows, int b_width,
                const double* __restrict__ Upacked, const double* __restrict__ gvec, const double* __restrict__ sinv, double lam,
                const double* __restrict__ lam_dev, const double* __restrict__ cam_diag, double* __restrict__ S, double* __restrict__ rhs,
-               double* __restrict__ W, int ldw) {
+               double* __restrict__ W, int ldw, double* __restrict__ side_d0, double* __restrict__ side_u10) {
   CBA_STAMP(ST_REG_REDUCE);
   using UP = UPack<NC>;
   constexpr int YM = REG_REDUCE_Y_MAX;
@@ -2253,6 +2264,7 @@ k_reg_finalize(TilePlan tp, const int* __restrict__ tile_wg_begin, const double*
   auto put = [&](int row, int col, double v) {
     S[(long)row * ncp + col] = v; S[(long)col * ncp + row] = v;
     W[(long)row * ldw + col] = v; W[(long)col * ldw + row] = v;
+    chol_side_put(side_d0, side_u10, row, col, v); chol_side_put(side_d0, side_u10, col, row, v);
   };
   const int bid = (int)blockIdx.x;
   if (bid >= G * fold_x && bid < G * fold_x + rhs_x) {  // right-hand side
@@ -2380,6 +2392,14 @@ k_reg_finalize(TilePlan tp, const int* __restrict__ tile_wg_begin, const double*
 // every block takes the same sums in the same order, the factor is the parent's to the bit.  U_k,k-1 is read from a SIDE SLOT (behind the
 // inverses in Xinv), not from W, where the critical workgroup replaces it by L_k,k-1 during the same launch; its writer is the workgroup that
 // completed it one launch earlier.  Roles, blocks and counts of both schedules: chol_schedule.h (replayed by tests/native/chol_schedule_check.cpp).
+//
+// The solver's sequence starts with launches -1 and 0 as ONE launch (pair_first; CBA_CHOL_PAIR=0: the two launches): a launch boundary, a round
+// trip and an LDS stage less on the chain.  Nothing is handed over inside the launch: each of its nbk panel workgroups factors D_0 for itself
+// — the same pivot code on the same bits — and multiplies by the X_0 in its own LDS.  The pivot code exists once; the critical workgroup b == 1
+// runs it twice in a loop (D_0, then D_1: the second time through it the instructions are cached).  D_0 and U_10 come from side slots that
+// k_reg_finalize / k_schur_finalize fill next to the work matrix (chol_side_put), because b == 1 overwrites both blocks in place; it alone stores
+// L_00, X_0 and T_00 (idle waves park L_00 in LDS during its diagonal update, X_0 lies in sh_L, and store them during the second factorisation).  Replayed by tests/native/chol_schedule_pair_check.cpp; to the bit against
+// the two launches: tests/test_dense_solve_pair_gpu.py.
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 constexpr int CHOL_THREADS = 512;   // 8 waves; 1024 threads measured slower (register budget halves, the panel solve spills)
 
@@ -2423,7 +2443,7 @@ __device__ __forceinline__ void chol_rank_nb(const double* __restrict__ A, int r
 template <bool EARLY>
 __global__ void __launch_bounds__(CHOL_THREADS)
 k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ flags, long long* __restrict__ trace, double* __restrict__ Xinv,
-            double* __restrict__ Tinv = nullptr) {
+            double* __restrict__ Tinv = nullptr, int pair_first = 0) {
   CBA_STAMP(ST_CHOL_STEP + k + 1);
   __shared__ double sh_red[4][16][17];
   __shared__ double sh_U[NB][NB + 1], sh_X[NB][NB + 1], sh_D[2 * NB][NB + 1];
@@ -2432,7 +2452,9 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
   const int nbk = (n + NB - 1) / NB;
   constexpr int EPT = NB * NB / CHOL_THREADS, ISTEP = CHOL_THREADS / NB;  // elements of a 32 x 32 block per thread
   const int j = tid & 31, i0 = tid >> 5;                  // (i0 + h * ISTEP, j), h < EPT
-  const CholWork wk = chol_decode<EARLY>(nbk, k, (int)blockIdx.x, Tinv != nullptr);
+  // pair_first (EARLY, k == 0): launch -1 runs inside this launch, every workgroup factors D_0 itself (chol_schedule.h, the paired first launch)
+  const bool pair = EARLY && pair_first != 0;
+  const CholWork wk = pair ? chol_pair_decode(nbk, (int)blockIdx.x, Tinv != nullptr) : chol_decode<EARLY>(nbk, k, (int)blockIdx.x, Tinv != nullptr);
 
   if (wk.role == CHOL_INVERSE) {
     // inverse role (Tinv != nullptr, k >= 1): T = L^-T is built next to the factorisation, off its critical path, so that the backward substitution
@@ -2514,7 +2536,8 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
   double* Wb = W + (long)rb * ldw;
   // optional phase stamps of the critical workgroup (b == k + 1), 100 MHz wall clock: CBA_CHOL_TRACE=1
   const bool stamp = trace != nullptr && wk.critical && tid == 0;
-#define CHOL_STAMP(ph) do { if (stamp) trace[(k + 1) * 8 + (ph)] = wall_clock64(); } while (0)
+  int sk = pair ? -1 : k;  // the launch whose phases are being stamped: the paired launch stamps its first factorisation as launch -1
+#define CHOL_STAMP(ph) do { if (stamp) trace[(sk + 1) * 8 + (ph)] = wall_clock64(); } while (0)
   CHOL_STAMP(0);
 
   // everything this thread needs from global, in one round trip
@@ -2531,19 +2554,19 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
   }
   // Step k = -1 (one workgroup: D_0 as loaded) and the look-ahead of every later step run the SAME factorisation code below: two inlined copies were
   // two cold instruction streams per iteration (the first pivot chain through a copy took 8.6 us instead of 5.6)
-  if (k < 0) {
-#pragma unroll
-    for (int h = 0; h < EPT; ++h) sh_D[i0 + h * ISTEP][j] = d_ij[h];
-  } else {
-    const int k0 = k * NB, nbp = min(NB, n - k0);
+  // The paired first launch runs that code twice in ONE loop, first on D_0 from its side slot, privately in every workgroup, then as launch 0's
+  // look-ahead; what launch 0's body needs from global memory is loaded in front of the loop, so that the launch keeps one round trip.
+  const int k0 = max(k, 0) * NB, nbp = min(NB, n - k0);
+  double u_ij[EPT];  // EARLY: U_k+1,k, complete, as the workgroup that completed it left it in side slot k (zero beyond its live rows)
+  v4f64 w_e = {0.0, 0.0, 0.0, 0.0};
+  if (k >= 0) {
 #pragma unroll
     for (int h = 0; h < EPT; ++h) {
       const int i = i0 + h * ISTEP;
       m_ij[h] = (i < rc && j < nbp) ? Wb[(long)i * ldw + k0 + j] : 0.0;
-      l_ij[h] = Xinv[(long)k * NB * NB + i * NB + j];  // X_k = L_kk^-1 (identity-padded), written by the factorisation of D_k
+      // X_k = L_kk^-1 (identity-padded), written by the factorisation of D_k; the paired launch holds D_0 here until its own X_0 is ready
+      l_ij[h] = pair ? side[(long)chol_side_d0(nbk) * NB * NB + i * NB + j] : Xinv[(long)k * NB * NB + i * NB + j];
     }
-    double u_ij[EPT];  // EARLY: U_k+1,k, complete, as the workgroup that completed it left it in side slot k (zero beyond its live rows)
-    v4f64 w_e = {0.0, 0.0, 0.0, 0.0};
     if constexpr (EARLY) {
 #pragma unroll
       for (int h = 0; h < EPT; ++h) {
@@ -2563,7 +2586,18 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
         }
       }
     }
+  }
 
+#pragma nounroll
+  for (int pass = pair ? 0 : 1; pass < 2; ++pass) {
+  if (pass == 0) {  // the paired launch: D_0 (full: nbk >= 2)
+#pragma unroll
+    for (int h = 0; h < EPT; ++h) sh_D[i0 + h * ISTEP][j] = l_ij[h];
+  } else if (k < 0) {
+#pragma unroll
+    for (int h = 0; h < EPT; ++h) sh_D[i0 + h * ISTEP][j] = d_ij[h];
+  } else {
+    sk = k;
     CHOL_STAMP(1);
     if constexpr (!EARLY) {
       // 1. pending update of this block's panel columns by panel k - 1 (all earlier panels were applied by the trailing
@@ -2655,6 +2689,11 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) sh_red[wv][(lane >> 4) + 4 * r][lane & 15] = c[r];
+    } else if (pair && wk.store_first) {
+      // the paired launch, b == 1 (never early: sh_D still holds the factor of D_0, which the second factorisation is about to replace): the idle
+      // waves park L_00 in sh_U, free since the panel solve — X_0 is in sh_L since then — and store both during the second factorisation, where no
+      // barrier waits for the stores (chol_factor_store in two halves)
+      for (int e = tid - 4 * WAVE; e < NB * NB; e += CHOL_THREADS - 4 * WAVE) sh_U[e / NB][e % NB] = sh_D[e / NB][e % NB];
     }
     __syncthreads();
 #pragma unroll
@@ -2673,16 +2712,35 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
   __syncthreads();
   CHOL_STAMP(5);
   if (tid < WAVE) {
-    chol_factor_block(sh_D, rc, flags);
+    chol_factor_block(sh_D, pass == 0 ? NB : rc, flags);
   } else if (EARLY && k < 0 && wk.side_write >= 0) {
     // launch -1: the idle waves copy U_10 = W_10 (column block 0 takes no update) to side slot 0 for the early update of launch 0
     const int live = min(NB, n - NB);  // rows of block 1
     for (int e = tid - WAVE; e < NB * NB; e += CHOL_THREADS - WAVE)
       if (e / NB < live) side[e] = W[(long)(NB + e / NB) * ldw + e % NB];
+  } else if (pair && pass == 1 && wk.store_first && wv >= 4) {
+    // the paired launch, b == 1: L_00, X_0 and T_00 as chol_factor_store writes them (D_0 is a full block), from where they were parked above
+    for (int e = tid - 4 * WAVE; e < NB * NB; e += CHOL_THREADS - 4 * WAVE) {
+      const int i = e / NB, c = e % NB;
+      const double x = sh_L[i][c];
+      if (c <= i) W[(long)i * ldw + c] = sh_U[i][c];
+      Xinv[e] = x;
+      if (Tinv) Tinv[(long)c * ldw + i] = x;  // T_00[c][i] = X[i][c]
+    }
   }
   __syncthreads();
-  chol_factor_store(sh_D, rc, Wb + rb, ldw, Xinv + (long)(k + 1) * NB * NB, tid, CHOL_THREADS, Tinv ? Tinv + (long)rb * ldw + rb : nullptr);
-  CHOL_STAMP(6);
+  if (pass == 0) {
+    // X_0 stays in the workgroup (row NB + c of sh_D is column c of X: the bits launch -1 stored to Xinv); b == 1 alone stores the factor, from
+    // the waves that idle during its diagonal update and its second factorisation
+#pragma unroll
+    for (int h = 0; h < EPT; ++h) l_ij[h] = sh_D[NB + j][i0 + h * ISTEP];
+    CHOL_STAMP(6);
+    if (early) __syncthreads();  // sh_D is reused for U_10 and the private L_10 (workgroup-uniform; b == 1 writes it two barriers later)
+  } else {
+    chol_factor_store(sh_D, rc, Wb + rb, ldw, Xinv + (long)(k + 1) * NB * NB, tid, CHOL_THREADS, Tinv ? Tinv + (long)rb * ldw + rb : nullptr);
+    CHOL_STAMP(6);
+  }
+  }
 #undef CHOL_STAMP
 }
 

@@ -121,6 +121,7 @@ struct cba_problem {
   double* Xinv = nullptr;  // inverses of the diagonal blocks of the Cholesky factor and, behind them, the side slots of the early update: [chol_xinv_blocks][NB][NB] (k_chol_step)
   double* Tinv = nullptr;  // T = L^-T, built block by block next to the factorisation (inverse role of k_chol_step)
   bool chol_ends = true;   // the last launch of the factorisation and the backward substitution as one (k_chol_last_apply; CBA_CHOL_ENDS=0: the old sequence, A/B)
+  bool chol_pair = true;   // launches -1 and 0 of the factorisation as one (chol_schedule.h, the paired first launch; CBA_CHOL_PAIR=0: the old sequence, A/B)
   bool chol_early = true;  // k_chol_step<true>: the pending panel update off the critical chain (chol_schedule.h; CBA_CHOL_EARLY=0: the parent's schedule, A/B)
   bool fuse_reg_finalize = true;  // k_reg_finalize in the place of k_reg_reduce + k_schur_finalize where the route allows (CBA_REG_FINALIZE=0: off)
   double* scal = nullptr;  // device scalars
@@ -612,6 +613,15 @@ int64_t cba_host_plan(int32_t n_points, int64_t n_obs, const int32_t* obs_pt, co
 
 static void drop_plan_task(cba_problem* p);  // (PlanTask is defined with the plans further down)
 
+// the factorisation's first two launches run as one (chol_schedule.h): the kernels that write the work matrix then fill the side slots of D_0 and U_10
+static bool chol_pairs(const cba_problem* p) {
+  return p->chol_pair && chol_pair_applies((p->ncp + NB - 1) / NB, p->chol_early, p->chol_ends);
+}
+static double* chol_side_block(const cba_problem* p, int s) {  // side slot s, or nullptr where the sequence is not paired
+  const int nbk = (p->ncp + NB - 1) / NB;
+  return chol_pairs(p) ? p->Xinv + (size_t)chol_side_slot(nbk, s) * NB * NB : nullptr;
+}
+
 #ifdef CBA_PROFILING
 // CBA_STAMPS=1 (profiling build): the kernels of the LAST fused iteration in the order they started, with the device's own clock — duration from the
 // first workgroup's entry to the last wave's exit, and the idle time in front of each (previous kernel's last exit -> this kernel's first entry).
@@ -652,7 +662,8 @@ static void dump_stamps(cba_problem* p) {
   for (size_t i = first; i < rows.size(); ++i) {
     const Row& r = rows[i];
     char nm[48];
-    if (r.slot >= ST_CHOL_STEP) snprintf(nm, sizeof nm, "k_chol_step k=%d", r.slot - ST_CHOL_STEP - 1); else snprintf(nm, sizeof nm, "%s", names[r.slot]);
+    if (r.slot == ST_CHOL_STEP + 1 && chol_pairs(p)) snprintf(nm, sizeof nm, "k_chol_step k=-1 and 0");
+    else if (r.slot >= ST_CHOL_STEP) snprintf(nm, sizeof nm, "k_chol_step k=%d", r.slot - ST_CHOL_STEP - 1); else snprintf(nm, sizeof nm, "%s", names[r.slot]);
     const double gap = i > first ? (r.t0 - rows[i - 1].t1) * 0.01 : 0.0;
     busy += (r.t1 - r.t0) * 0.01; if (i > first) idle += gap;
     fprintf(stderr, "| %zu | %s | %d | %.2f | %.2f | %.2f / %.2f / %.2f | %.2f |\n", i - first + 1, nm, r.blocks, (r.t1 - r.t0) * 0.01, (r.last_entry - r.t0) * 0.01,
@@ -1322,6 +1333,7 @@ int cba_create(const cba_problem_desc* d, const cba_options* opt, cba_problem** 
   if (const char* e = std::getenv("CBA_REG_FINALIZE")) p->fuse_reg_finalize = e[0] != '0';
   if (const char* e = std::getenv("CBA_CHOL_EARLY")) p->chol_early = e[0] != '0';
   if (const char* e = std::getenv("CBA_CHOL_ENDS")) p->chol_ends = e[0] != '0';
+  if (const char* e = std::getenv("CBA_CHOL_PAIR")) p->chol_pair = e[0] != '0';
   if (const char* e = std::getenv("CBA_SPEC_SKIP")) p->spec_skip = e[0] != '0';
   if (const char* e = std::getenv("CBA_SCALE_FUSED")) p->scale_fused = e[0] != '0';
   if (const char* e = std::getenv("CBA_SMALL_SOLVE")) p->small_solve_on = e[0] != '0';
@@ -1790,13 +1802,17 @@ static int run_linearize(cba_problem* p, cba_linearization* out) {
 // holds the workgroup counts of a launch — the kernel decodes its role from the same functions).  without_last: see below.  Not part of the C ABI.
 namespace cba {
 __attribute__((visibility("hidden"))) void enqueue_chol_factor(double* W, int n, int ldw, int* flags, long long* trace, double* Xinv, double* Tinv,
-                                                               bool early, hipStream_t stream, bool without_last) {
+                                                               bool early, hipStream_t stream, bool without_last, bool pair) {
   const int nbk = (n + NB - 1) / NB;
+  // pair (the solver only; the caller has had the side slots of D_0 and U_10 filled): launch -1 runs inside launch 0
+  pair = pair && chol_pair_applies(nbk, early, without_last);
   // without_last (the solver, nbk >= 2): launch nbk - 1 is left to the caller's k_chol_last_apply, which also takes the backward substitution
-  for (int k = -1; k < nbk - (without_last ? 1 : 0); ++k) {
+  for (int k = chol_first_launch(pair); k < nbk - (without_last ? 1 : 0); ++k) {
     // step k: panel k solved for the blocks below it (and the rhs row), D_k+1 factored; extra workgroups apply the pending rank-NB updates to
     // the blocks right of the current panel and build T
-    if (early)
+    if (pair && k == 0)
+      hipLaunchKernelGGL(k_chol_step<true>, dim3(chol_pair_counts(nbk).total()), dim3(CHOL_THREADS), 0, stream, W, n, ldw, k, flags, trace, Xinv, Tinv, 1);
+    else if (early)
       hipLaunchKernelGGL(k_chol_step<true>, dim3(chol_counts<true>(nbk, k, Tinv != nullptr).total()), dim3(CHOL_THREADS), 0, stream, W, n, ldw, k, flags, trace, Xinv, Tinv);
     else
       hipLaunchKernelGGL(k_chol_step<false>, dim3(chol_counts<false>(nbk, k, Tinv != nullptr).total()), dim3(CHOL_THREADS), 0, stream, W, n, ldw, k, flags, trace, Xinv, Tinv);
@@ -1813,7 +1829,7 @@ static int enqueue_cholesky(cba_problem* p) {
   const int n = p->ncp, nbk = (n + NB - 1) / NB;
   // (one block: the first and the last launch coincide, the old sequence stays)
   const bool fold_last = p->chol_ends && nbk >= 2;
-  enqueue_chol_factor(p->Lbuf, n, p->ldw, p->flags, p->chol_trace, p->Xinv, p->Tinv, p->chol_early, p->stream, fold_last);
+  enqueue_chol_factor(p->Lbuf, n, p->ldw, p->flags, p->chol_trace, p->Xinv, p->Tinv, p->chol_early, p->stream, fold_last, chol_pairs(p));
   if (fold_last) {
     const dim3 grid(chol_last_apply_workgroups(nbk));
     if (p->chol_early) hipLaunchKernelGGL(k_chol_last_apply<true>, grid, dim3(CHOL_THREADS), 0, p->stream, (const double*)p->Lbuf, n, p->ldw, (const double*)p->Xinv, (const double*)p->Tinv, p->s);
@@ -2006,7 +2022,7 @@ static int run_newton_chain(cba_problem* p, double lam, const double* lam_dev, b
       const int tile_x = (p->gsz * p->gsz * NC * NC + 64 * per - 1) / (64 * per), fold_x = (p->gsz * NC * NC + 63) / 64, rhs_x = (p->lay.ncp_pad + 63) / 64;
       hipLaunchKernelGGL((k_reg_finalize<NC>), dim3(p->G * fold_x + rhs_x + p->n_tiles * tile_x), dim3(64, REG_REDUCE_Y_MAX), 0, p->stream, p->tp, p->tile_wg_begin, p->partial,
                          p->cam_off, p->cam_np, ncp, p->n_tiles, p->G, p->reg_reduce_y, fold_x, rhs_x, tile_x, (const double*)p->partial_b, p->grid, p->lay.ncp_pad, p->Upacked, p->g,
-                         p->sinv, lam, lam_dev, p->cam_diag, p->S, p->rhs, p->Lbuf, p->ldw);
+                         p->sinv, lam, lam_dev, p->cam_diag, p->S, p->rhs, p->Lbuf, p->ldw, chol_side_block(p, chol_side_d0((ncp + NB - 1) / NB)), chol_side_block(p, 0));
     } else {
       hipLaunchKernelGGL(k_reg_reduce, dim3(std::max((p->tp.tile_elems + 63) / 64, (p->lay.ncp_pad + 63) / 64), p->n_tiles + B_SLICES), dim3(64, p->reg_reduce_y), 0,
                          p->stream, p->tp, p->tile_wg_begin, p->partial, p->cam_off, p->cam_np, NC, ncp, p->Sacc, p->red, p->n_tiles,
@@ -2040,7 +2056,7 @@ static int run_newton_chain(cba_problem* p, double lam, const double* lam_dev, b
       hipLaunchKernelGGL((k_schur_finalize<NC>), dim3((int)((nn + 255) / 256)), dim3(256), 0, p->stream, p->Sacc,
                          p->Sacc + (size_t)ncp * ncp, p->Upacked, p->g, p->sinv, p->param_cam, p->param_loc, ncp, lam, lam_dev, p->cam_diag, p->S, p->rhs, p->Lbuf, p->ldw,
                          fold_in_finalize ? (const double*)p->red : (const double*)nullptr, p->tp.g, (long)p->tp.tile_elems, (const int*)p->tp.group_cam_begin,
-                         p->lay.ncp_pad);
+                         p->lay.ncp_pad, chol_side_block(p, chol_side_d0((ncp + NB - 1) / NB)), chol_side_block(p, 0));
     }
   }
   int rc = CBA_OK;

@@ -20,6 +20,11 @@
 //   inverse workgroup (i >= k, j < k)      both schedules, k >= 1, where T = L^-T is wanted: block (j, i) of T takes the term of panel k - 1.
 //
 // Either way every block (i, j) receives P_0, P_1, .., P_j-1 once each in ascending order, so the factor is the same to the bit.
+//
+// PAIRED FIRST LAUNCH (CBA_CHOL_PAIR, the default; the solver's call on the early schedule with the folded end, nbk >= 2): launches -1 and 0 are ONE
+// launch of nbk panel workgroups.  Every one factors D_0 PRIVATELY (the same pivot code on the same bits) and takes X_0 from its own LDS, then runs
+// launch 0's body as above; b == 1 alone stores L_00, X_0 and T_00.  D_0 and U_10 are read from side slots (chol_side_d0 and slot 0) that the
+// producers of the work matrix fill, since b == 1 overwrites both blocks in place while the others still read them.  chol_pair_* below.
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -32,9 +37,10 @@ namespace cba {
 
 enum CholRole : int { CHOL_FACTOR0 = 0, CHOL_PANEL = 1, CHOL_TRAILING = 2, CHOL_INVERSE = 3 };
 
-// side slots live behind the nbk + 1 inverses of the diagonal blocks, in the same buffer: [2 (nbk + 1)][NB][NB]
-CHOL_HD inline int chol_xinv_blocks(int nbk) { return 2 * (nbk + 1); }
+// side slots live behind the nbk + 1 inverses of the diagonal blocks, in the same buffer: [2 (nbk + 1) + 1][NB][NB]; the last one is D_0's
+CHOL_HD inline int chol_xinv_blocks(int nbk) { return 2 * (nbk + 1) + 1; }
 CHOL_HD inline int chol_side_slot(int nbk, int s) { return nbk + 1 + s; }  // index of side slot s in units of NB x NB blocks
+CHOL_HD inline int chol_side_d0(int nbk) { return nbk + 1; }               // the side slot that holds D_0 for the paired first launch
 
 struct CholCounts {
   int panel, trailing, inverse;
@@ -60,10 +66,12 @@ CHOL_HD inline CholCounts chol_counts(int nbk, int k, bool with_inverse) {
 //   upd_col      >= 0: the workgroup subtracts P_m(bi, upd_col) for m = upd_first .. upd_first + upd_terms - 1 from block (bi, upd_col)
 //   early        a panel workgroup with the early update (upd_col == k + 1): reads side slot k
 //   side_write   >= 0: the side slot that receives a copy of the block it completed (launch -1: of W_10)
+//   factor_first the paired first launch: the workgroup factors D_0 privately in front of launch 0's body; store_first: and stores L_00, X_0, T_00
 struct CholWork {
   int role, bi, bj;
   bool critical, early;
   int upd_col, upd_first, upd_terms, side_write;
+  bool factor_first, store_first;
 };
 
 template <bool EARLY>
@@ -72,6 +80,7 @@ CHOL_HD inline CholWork chol_decode(int nbk, int k, int wg, bool with_inverse) {
   CholWork w;
   w.critical = false; w.early = false;
   w.upd_col = -1; w.upd_first = 0; w.upd_terms = 0; w.side_write = -1;
+  w.factor_first = false; w.store_first = false;
   if (k < 0) {
     w.role = CHOL_FACTOR0; w.bi = 0; w.bj = 0; w.critical = true;
     if (EARLY && nbk >= 2) w.side_write = 0;
@@ -149,7 +158,8 @@ inline void chol_for_each_access(int nbk, int k, int wg, bool with_inverse, F&& 
 //   CHOL_ACT_APPLY   block (i, j) -= P_m(i, j)
 //   CHOL_ACT_SOLVE   block (i, j), i > j, becomes L_ij = W_ij X_j^T       (m = j)
 //   CHOL_ACT_FACTOR  diagonal block (i, i) is factored                     (m = i)
-enum CholAct : int { CHOL_ACT_APPLY = 0, CHOL_ACT_SOLVE = 1, CHOL_ACT_FACTOR = 2 };
+//   CHOL_ACT_PRIVATE_FACTOR  the paired first launch: a private copy of D_0 is factored, nothing of it is stored   (i = j = m = 0)
+enum CholAct : int { CHOL_ACT_APPLY = 0, CHOL_ACT_SOLVE = 1, CHOL_ACT_FACTOR = 2, CHOL_ACT_PRIVATE_FACTOR = 3 };
 
 // f(CholAct, i, j, m) for every action of workgroup `wg` of launch k (the inverse role has none: it does not touch the factor)
 template <bool EARLY, class F>
@@ -167,6 +177,44 @@ inline void chol_for_each_action(int nbk, int k, int wg, bool with_inverse, F&& 
     f(CHOL_ACT_APPLY, b, b, k);
     if (w.critical) f(CHOL_ACT_FACTOR, b, b, b);
   }
+}
+
+// ---- the paired first launch: launches -1 and 0 as one (see the head of the file) -------------------------------------------------------------------
+CHOL_HD inline bool chol_pair_applies(int nbk, bool early, bool folded_end) { return early && folded_end && nbk >= 2; }
+CHOL_HD inline int chol_first_launch(bool pair) { return pair ? 0 : -1; }  // the k of the first launch of the sequence; pair: it is the paired one
+
+CHOL_HD inline CholCounts chol_pair_counts(int nbk) {
+  CholCounts c;
+  c.panel = nbk; c.trailing = 0; c.inverse = 0;
+  return c;
+}
+
+CHOL_HD inline CholWork chol_pair_decode(int nbk, int wg, bool with_inverse) {
+  CholWork w = chol_decode<true>(nbk, 0, wg, with_inverse);  // launch 0 has panel workgroups only
+  w.factor_first = true;
+  w.store_first = w.critical;
+  return w;
+}
+
+template <class F>
+inline void chol_pair_for_each_access(int nbk, int wg, bool with_inverse, F&& f) {
+  const CholWork w = chol_pair_decode(nbk, wg, with_inverse);
+  f(CholRef{CHOL_SIDE, chol_side_d0(nbk), 0}, false);
+  if (w.store_first) {
+    f(CholRef{CHOL_W, 0, 0}, true); f(CholRef{CHOL_XINV, 0, 0}, true);
+    if (with_inverse) f(CholRef{CHOL_T, 0, 0}, true);
+  }
+  chol_for_each_access<true>(nbk, 0, wg, with_inverse, [&](CholRef r, bool write) {
+    if (!write && r.buf == CHOL_XINV && r.i == 0) return;  // X_0 comes from the workgroup's own LDS
+    f(r, write);
+  });
+}
+
+template <class F>
+inline void chol_pair_for_each_action(int nbk, int wg, bool with_inverse, F&& f) {
+  const CholWork w = chol_pair_decode(nbk, wg, with_inverse);
+  f(w.store_first ? CHOL_ACT_FACTOR : CHOL_ACT_PRIVATE_FACTOR, 0, 0, 0);
+  chol_for_each_action<true>(nbk, 0, wg, with_inverse, f);
 }
 
 // ---- the end of the solver's launch sequence (k_chol_last_apply of cba_kernels.h, enqueue_cholesky of cba_lib.hip; CBA_CHOL_ENDS=0: off) --------------

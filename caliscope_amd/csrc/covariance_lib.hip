@@ -46,7 +46,7 @@
 namespace cba {
 // cba_lib.hip: the launches of the blocked Cholesky on raw device pointers
 __attribute__((visibility("hidden"))) void enqueue_chol_factor(double* W, int n, int ldw, int* flags, long long* trace, double* Xinv, double* Tinv,
-                                                               bool early, hipStream_t stream, bool without_last);
+                                                               bool early, hipStream_t stream, bool without_last, bool pair);
 __attribute__((visibility("hidden"))) bool chol_early_from_env();
 }  // namespace cba
 
@@ -571,7 +571,7 @@ int cba::cov_pipeline(const cba_cov_desc* d, int32_t device, const char* what, b
 
   hipLaunchKernelGGL(k_unc_assemble, blocks((int64_t)ncp * ncp), dim3(COV_BLOCK), 0, 0, ncp, ldw, (const double*)dU, (const double*)dSacc, (const double*)dB, dDinv,
                      dparam_cam, dparam_loc, dW, dscale, dflags);
-  enqueue_chol_factor(dW, ncp, ldw, dflags, nullptr, dXinv, dT, chol_early_from_env(), 0, false);  // (all launches: T is read here)
+  enqueue_chol_factor(dW, ncp, ldw, dflags, nullptr, dXinv, dT, chol_early_from_env(), 0, false, false);  // (all launches, none paired: T and L's diagonal are read here)
   hipLaunchKernelGGL(k_unc_pivots, blocks(ncp), dim3(COV_BLOCK), 0, 0, (int)ncp, ldw, (const double*)dW, dflags);
   hipLaunchKernelGGL(k_unc_ttt, dim3((unsigned)nbk, (unsigned)nbk), dim3(256), 0, 0, (int)ncp, ldw, (const double*)dT, (const double*)dscale, dC);
   buf.check(hipGetLastError());
