@@ -217,8 +217,11 @@ CBA_HD void project_full(const CamTab& c, double X, double Y, double Z, double u
 // (normal-equation blocks, right-hand sides, J v) instead of once per observation — the per-observation kernels then never read J_l (9 of the 36
 // doubles of a camera row, all of which come out of LDS per observation) and skip the 36 flops of the rotation columns.
 //   G (2 x 3) = d(pixel)/dX_c / fx0,   Yr (3) = R X,   B (2 x 3) = G R,   Aint (2 x 3): the free-intrinsics columns (zero unless nparams == 9)
-CBA_HD void project_factors(const CamTab& c, double X, double Y, double Z, double u, double v,
-                            double* e, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3]) {
+// RES = false is the form of a linear loss's second linearisations (k_tprep, k_jv: the residual reaches them only through robust_one's row scale, which
+// is exactly 1.0 there): the same arithmetic for G, Yr, Aint and B in the same order, no u, v, e, and c.cx / c.cy are not read.
+template <bool RES>
+CBA_HD void project_factors_impl(const CamTab& c, double X, double Y, double Z, double u, double v,
+                                 double* e, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3]) {
   const double Y0 = c.R[0] * X + c.R[1] * Y + c.R[2] * Z;
   const double Y1 = c.R[3] * X + c.R[4] * Y + c.R[5] * Z;
   const double Y2 = c.R[6] * X + c.R[7] * Y + c.R[8] * Z;
@@ -229,8 +232,10 @@ CBA_HD void project_factors(const CamTab& c, double X, double Y, double Z, doubl
   Lens L;
   if (c.model != 0.0) lens_fisheye(c.d, x, y, &L); else lens_pinhole(c.d, x, y, &L);
   const double s = c.inv_fx0;
-  e[0] = ((c.cx - u) + c.fx * L.xd) * s;
-  e[1] = ((c.cy - v) + c.fy * L.yd) * s;
+  if constexpr (RES) {
+    e[0] = ((c.cx - u) + c.fx * L.xd) * s;
+    e[1] = ((c.cy - v) + c.fy * L.yd) * s;
+  }
   const double fxs = c.fx * s, fys = c.fy * s;
   const double g00 = fxs * L.dxx * iz, g01 = fxs * L.dxy * iz;
   const double g10 = fys * L.dyx * iz, g11 = fys * L.dyy * iz;
@@ -245,6 +250,14 @@ CBA_HD void project_factors(const CamTab& c, double X, double Y, double Z, doubl
   Aint[0][0] = free_intr ? c.fx0 * L.xd * s : 0.0; Aint[1][0] = free_intr ? c.fy0 * L.yd * s : 0.0;
   Aint[0][1] = free_intr ? fxs * L.xr2 : 0.0;      Aint[1][1] = free_intr ? fys * L.yr2 : 0.0;
   Aint[0][2] = free_intr ? fxs * L.xr4 : 0.0;      Aint[1][2] = free_intr ? fys * L.yr4 : 0.0;
+}
+CBA_HD void project_factors(const CamTab& c, double X, double Y, double Z, double u, double v,
+                            double* e, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3]) {
+  project_factors_impl<true>(c, X, Y, Z, u, v, e, G, Yr, Aint, B);
+}
+// the factors alone (no residual)
+CBA_HD void project_factors(const CamTab& c, double X, double Y, double Z, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3]) {
+  project_factors_impl<false>(c, X, Y, Z, 0.0, 0.0, nullptr, G, Yr, Aint, B);
 }
 
 // scipy's robust-loss treatment of ONE scalar residual r (least_squares.py:169-237, common.py:720-731).

@@ -422,6 +422,32 @@ __device__ __forceinline__ double obs_factors(const CamTab& c_lds, double X, dou
   }
   return rho;
 }
+// The factors alone, for a LINEAR loss (k_tprep<.., LIN>, k_jv<.., LIN>): the row scale is exactly 1.0 there and the second linearisations use nothing
+// else of the residual, so no pixel is loaded, cx and cy stay in the table (25 of 36 doubles) and G, Yr, Aint, B come out bit for bit as above.
+__device__ __forceinline__ void obs_factors(const CamTab& c_lds, double X, double Y, double Z, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3]) {
+  CamTab c;
+  {
+    const double* src = reinterpret_cast<const double*>(&c_lds);
+    double* dst = reinterpret_cast<double*>(&c);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) dst[i] = src[i];          // R, t
+    dst[21] = src[21]; dst[22] = src[22];                  // fx, fy
+#pragma unroll
+    for (int i = 25; i < 35; ++i) dst[i] = src[i];         // d .. nparams
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  project_factors(c, X, Y, Z, G, Yr, Aint, B);
+  // The generic form's robust-loss branches end the basic block here.  Without them the compiler contracts and re-associates ACROSS this point (the
+  // sums B and Yr end in are folded into the multiply-adds of chol3_fwd and of the right-hand side: other roundings, other bits in the records): the
+  // factors pass through an empty asm, which costs no instruction and which the compiler cannot see through.
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { asm("" : "+v"(G[r][k])); asm("" : "+v"(B[r][k])); asm("" : "+v"(Aint[r][k])); }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) asm("" : "+v"(Yr[k]));
+}
 
 template <int NC> struct UPack {
   static constexpr int TRI = NC * (NC + 1) / 2;
@@ -980,7 +1006,8 @@ __device__ __forceinline__ void publish_gnorm(const SpecSkip& sk) {
 __global__ void __launch_bounds__(BLOCK) k_gnorm_pub(SpecSkip sk) { publish_gnorm(sk); }
 
 // J.v for one or two vectors: partial[b][0..2] = sum |Jv1|^2, <Jv1,Jv2>, |Jv2|^2
-template <int NC, int NV, bool CAMG = false>
+// LIN: the handle's loss is linear (chosen per launch, run_jv) — the pixels are not loaded and `loss`, `f_scale`, obs_u, obs_v are not read
+template <int NC, int NV, bool CAMG = false, bool LIN = false>
 __global__ void __launch_bounds__(BLOCK)
 k_jv(const double* __restrict__ obs_u, const double* __restrict__ obs_v, const int* __restrict__ obs_cam,
      const int* __restrict__ obs_pt, long n_obs, const double* __restrict__ xvec, VecLayout lay,
@@ -1029,9 +1056,13 @@ k_jv(const double* __restrict__ obs_u, const double* __restrict__ obs_v, const i
   // loads the trip has just issued (the rule found at schur_reg3_body).
   struct Rec { int cam, pt; double u, v; };
   struct Gat { double X, Y, Z, a, b, c, d, e, f; };
-  constexpr int LOADS = 4 + (NV == 2 ? 9 : 6);  // vector-memory instructions a trip issues
+  constexpr int LOADS = (LIN ? 2 : 4) + (NV == 2 ? 9 : 6);  // vector-memory instructions a trip issues
   const long stride = (long)gridDim.x * BLOCK, last = n_obs - 1;
-  auto load_rec = [&](long i) { Rec r; const long k = min(i, last); r.cam = obs_cam[k]; r.pt = obs_pt[k]; r.u = obs_u[k]; r.v = obs_v[k]; return r; };
+  auto load_rec = [&](long i) {
+    Rec r; const long k = min(i, last); r.cam = obs_cam[k]; r.pt = obs_pt[k];
+    if constexpr (LIN) { r.u = r.v = 0.0; } else { r.u = obs_u[k]; r.v = obs_v[k]; }
+    return r;
+  };
   auto load_gat = [&](int pt) {
     Gat g;
     g.X = px[pt]; g.Y = px[lay.Ppad + pt]; g.Z = px[2 * lay.Ppad + pt];
@@ -1039,7 +1070,10 @@ k_jv(const double* __restrict__ obs_u, const double* __restrict__ obs_v, const i
     if (NV == 2) { g.d = p2[pt]; g.e = p2[lay.Ppad + pt]; g.f = p2[2 * lay.Ppad + pt]; } else { g.d = g.e = g.f = 0.0; }
     return g;
   };
-  auto launder_rec = [](Rec& r) { asm volatile("" : "+v"(r.cam), "+v"(r.pt), "+v"(r.u), "+v"(r.v)); };
+  auto launder_rec = [](Rec& r) {
+    asm volatile("" : "+v"(r.cam), "+v"(r.pt));
+    if constexpr (!LIN) asm volatile("" : "+v"(r.u), "+v"(r.v));
+  };
   auto launder_gat = [](Gat& g) {
     asm volatile("" : "+v"(g.X), "+v"(g.Y), "+v"(g.Z), "+v"(g.a), "+v"(g.b), "+v"(g.c));
     if (NV == 2) asm volatile("" : "+v"(g.d), "+v"(g.e), "+v"(g.f));
@@ -1059,7 +1093,8 @@ k_jv(const double* __restrict__ obs_u, const double* __restrict__ obs_v, const i
     const int cam = rc.cam;
     double e[2], G[2][3], Yr[3], Aint[2][3], B[2][3];
     const CamTab& ctj = cam_of<CAMG>(sh_tab, tab, cam);
-    obs_factors(ctj, gc.X, gc.Y, gc.Z, rc.u, rc.v, loss, f_scale, e, G, Yr, Aint, B);
+    if constexpr (LIN) obs_factors(ctj, gc.X, gc.Y, gc.Z, G, Yr, Aint, B);
+    else obs_factors(ctj, gc.X, gc.Y, gc.Z, rc.u, rc.v, loss, f_scale, e, G, Yr, Aint, B);
     const double* vc = sh_v + (int)ctj.pad[0];  // (= cam_off[cam], from the table row that is being read anyway): w (3), v_t (3), v_i (3, nine-parameter cameras)
     auto jv = [&](const double* q, double px0, double px1, double px2, double* o0, double* o1) {
       // m = w x Y + v_t;  row r: G_r . m + B_r . v_p (+ A_intr,r . v_i)
@@ -1235,7 +1270,9 @@ __device__ __forceinline__ double lin_finish_block(const LinFin& lf, double (*sh
   return sh_out[0];
 }
 
-template <int NC, int DETM = 0, bool CAMG = false, bool LINF = false>
+// LIN: the handle's loss is linear (chosen per launch, run_newton_chain) — the pixels are not loaded and `loss`, `f_scale`, obs_u, obs_v are not read.
+// Launched for six-parameter kernels only: k_tprep<9, .., LIN> measured slower than the generic form (cba_lib.hip: LIN_FORM).
+template <int NC, int DETM = 0, bool CAMG = false, bool LINF = false, bool LIN = false>
 __global__ void __launch_bounds__(BLOCK, DETM == 0 ? 2 : 1)  // (two workgroups per CU = two waves per SIMD: 256 registers; the fixed-order variants take more and run one)
 k_tprep(const double* __restrict__ obs_u, const double* __restrict__ obs_v, const int* __restrict__ obs_cam,
         const int* __restrict__ obs_pt, const int* __restrict__ chunk_start, int n_chunks,
@@ -1298,7 +1335,14 @@ k_tprep(const double* __restrict__ obs_u, const double* __restrict__ obs_v, cons
     if constexpr (FULL) load_rest(q, pt);
     return q;
   };
-  auto launder_obs = [](ObsRec& r) { asm volatile("" : "+v"(r.u), "+v"(r.v), "+v"(r.cam), "+v"(r.pt)); };
+  auto load_rec = [&](int i) {  // the record in flight: camera and point alone under a linear loss
+    if constexpr (LIN) return ObsRec{0.0, 0.0, obs_cam[i], obs_pt[i]};
+    else return load_obs(obs_u, obs_v, obs_cam, obs_pt, i);
+  };
+  auto launder_obs = [](ObsRec& r) {
+    if constexpr (!LIN) asm volatile("" : "+v"(r.u), "+v"(r.v));
+    asm volatile("" : "+v"(r.cam), "+v"(r.pt));
+  };
   auto launder_ops = [](PtOps& q) {
     asm volatile("" : "+v"(q.X), "+v"(q.Y), "+v"(q.Z));
     if constexpr (FULL) {
@@ -1317,9 +1361,9 @@ k_tprep(const double* __restrict__ obs_u, const double* __restrict__ obs_v, cons
     o0 = chunk_start[ch]; o1 = chunk_start[ch + 1];
     const int c1 = min(ch + stride, last_chunk);
     no0 = chunk_start[c1]; no1 = chunk_start[c1 + 1];
-    cur = load_obs(obs_u, obs_v, obs_cam, obs_pt, min(o0 + (int)threadIdx.x, last_obs));
+    cur = load_rec(min(o0 + (int)threadIdx.x, last_obs));
     if constexpr (PIPE) {
-      if constexpr (FULL) nx = load_obs(obs_u, obs_v, obs_cam, obs_pt, min(no0 + (int)threadIdx.x, last_obs));
+      if constexpr (FULL) nx = load_rec(min(no0 + (int)threadIdx.x, last_obs));
       else nx.pt = obs_pt[min(no0 + (int)threadIdx.x, last_obs)];
       ops = load_ops(cur.pt);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1338,10 +1382,11 @@ k_tprep(const double* __restrict__ obs_u, const double* __restrict__ obs_v, cons
     ObsRec nn = {0.0, 0.0, 0, 0};
     if constexpr (PIPE && !FULL) {  // the rest of the next chunk's record, and the point index of the chunk after next
       const int k1 = min(no0 + (int)threadIdx.x, last_obs);
-      nx.u = obs_u[k1]; nx.v = obs_v[k1]; nx.cam = obs_cam[k1];
+      if constexpr (!LIN) { nx.u = obs_u[k1]; nx.v = obs_v[k1]; }
+      nx.cam = obs_cam[k1];
       nn.pt = obs_pt[min(nno0 + (int)threadIdx.x, last_obs)];
     } else {
-      nn = load_obs(obs_u, obs_v, obs_cam, obs_pt, min((PIPE ? nno0 : no0) + (int)threadIdx.x, last_obs));  // record of the chunk after next (PIPE) / of the next
+      nn = load_rec(min((PIPE ? nno0 : no0) + (int)threadIdx.x, last_obs));  // record of the chunk after next (PIPE) / of the next
     }
     if constexpr (PIPE) __builtin_amdgcn_sched_barrier(0);
     const int i = o0 + threadIdx.x;
@@ -1362,7 +1407,8 @@ k_tprep(const double* __restrict__ obs_u, const double* __restrict__ obs_v, cons
       // factored linearisation (round 6): T = A^T Z = [J_l^T [Y]x Q ; Q ; T_intr] with Q = G^T Z — the record never held the top rows, and their share
       // of the right-hand side, J_l^T (Y x (Q y)), is accumulated WITHOUT its J_l^T (applied once per camera when the workgroup writes its row out)
       double e[2], G[2][3], Yr[3], Aint[2][3], B[2][3], Z[2][3];
-      obs_factors(ct, X, Yw, Zw, cur.u, cur.v, loss, f_scale, e, G, Yr, Aint, B);
+      if constexpr (LIN) obs_factors(ct, X, Yw, Zw, G, Yr, Aint, B);
+      else obs_factors(ct, X, Yw, Zw, cur.u, cur.v, loss, f_scale, e, G, Yr, Aint, B);
       const int np = (int)ct.nparams;
       double Vd[6], L[6];
 #pragma unroll

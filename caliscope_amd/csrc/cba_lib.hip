@@ -121,6 +121,7 @@ struct cba_problem {
   double* Xinv = nullptr;  // inverses of the diagonal blocks of the Cholesky factor and, behind them, the side slots of the early update: [chol_xinv_blocks][NB][NB] (k_chol_step)
   double* Tinv = nullptr;  // T = L^-T, built block by block next to the factorisation (inverse role of k_chol_step)
   bool chol_ends = true;   // the last launch of the factorisation and the backward substitution as one (k_chol_last_apply; CBA_CHOL_ENDS=0: the old sequence, A/B)
+  bool linear_pass = true;  // a linear loss runs k_tprep and k_jv in their LIN form, which loads no pixels (CBA_LINEAR_PASS=0: the generic kernels, A/B)
   bool chol_pair = true;   // launches -1 and 0 of the factorisation as one (chol_schedule.h, the paired first launch; CBA_CHOL_PAIR=0: the old sequence, A/B)
   bool chol_early = true;  // k_chol_step<true>: the pending panel update off the critical chain (chol_schedule.h; CBA_CHOL_EARLY=0: the parent's schedule, A/B)
   bool fuse_reg_finalize = true;  // k_reg_finalize in the place of k_reg_reduce + k_schur_finalize where the route allows (CBA_REG_FINALIZE=0: off)
@@ -669,6 +670,13 @@ static void dump_stamps(cba_problem* p) {
     fprintf(stderr, "| %zu | %s | %d | %.2f | %.2f | %.2f / %.2f / %.2f | %.2f |\n", i - first + 1, nm, r.blocks, (r.t1 - r.t0) * 0.01, (r.last_entry - r.t0) * 0.01,
             r.life_min * 0.01, r.life_sum / r.blocks * 0.01, r.life_max * 0.01, gap);
   }
+  // the J.g pass of an earlier iteration (the last iteration of a solve enqueues none; its neighbours' stamps have been overwritten: no idle time)
+  for (size_t i = 0; i < first; ++i) {
+    const Row& r = rows[i];
+    if (r.slot != ST_JV) continue;
+    fprintf(stderr, "| (earlier) | %s | %d | %.2f | %.2f | %.2f / %.2f / %.2f | - |\n", names[r.slot], r.blocks, (r.t1 - r.t0) * 0.01,
+            (r.last_entry - r.t0) * 0.01, r.life_min * 0.01, r.life_sum / r.blocks * 0.01, r.life_max * 0.01);
+  }
   if (first < rows.size())
     fprintf(stderr, "%zu kernels, %.1f us inside kernels, %.1f us between them, %.1f us from the first entry to the last exit\n", rows.size() - first, busy, idle,
             (rows.back().t1 - rows[first].t0) * 0.01);
@@ -760,6 +768,12 @@ static int raise_lds_ceiling(const void* fn, size_t bytes) {
   have = bytes;
   return CBA_OK;
 }
+
+// k_tprep and k_jv run in their LIN form: asked at every launch, because cba_set_loss changes the loss of a live handle.  Six-parameter kernels only
+// (LIN_FORM<NC>): the nine-parameter k_tprep measured SLOWER without the pixels (cfg5: 535 - 541 us against 495 - 507), and where
+// LIN_FORM is false the launch sites below name the generic instantiation twice.
+template <int NC> constexpr bool LIN_FORM = NC == 6;
+template <int NC> static bool linear_pass_now(const cba_problem* p) { return LIN_FORM<NC> && p->linear_pass && p->loss == LOSS_LINEAR; }
 
 template <typename K>
 static int allow_lds(K kernel, size_t bytes) {
@@ -1078,20 +1092,33 @@ static int configure_kernels(cba_problem* p) {
     if ((rc = allow_lds(k_tprep<NC, 3>, lds_tprep<NC>(p)))) return rc;
     if ((rc = allow_lds(k_tprep<NC, 5>, lds_tprep<NC>(p)))) return rc;
     if ((rc = allow_lds(k_tprep<NC, 8>, lds_tprep<NC>(p)))) return rc;
+    if ((rc = allow_lds(k_tprep<NC, 3, false, false, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
+    if ((rc = allow_lds(k_tprep<NC, 5, false, false, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
+    if ((rc = allow_lds(k_tprep<NC, 8, false, false, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
     if constexpr (NC == 6) {
       if ((rc = allow_lds(k_build<NC, 16>, lds_build<NC>(p)))) return rc;
       if ((rc = allow_lds(k_tprep<NC, 16>, lds_tprep<NC>(p)))) return rc;
+      if ((rc = allow_lds(k_tprep<NC, 16, false, false, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
     }
   }
   if ((rc = allow_lds(k_jv<NC, 1>, lds_jv(p, 1)))) return rc;
   if ((rc = allow_lds(k_jv<NC, 2>, lds_jv(p, 2)))) return rc;
   if ((rc = allow_lds(k_jv<NC, 1, true>, lds_jv(p, 1)))) return rc;
   if ((rc = allow_lds(k_jv<NC, 2, true>, lds_jv(p, 2)))) return rc;
+  // (the LIN forms of a linear loss: the loss of a handle can change, cba_set_loss, so both are made ready)
+  if ((rc = allow_lds(k_jv<NC, 1, false, LIN_FORM<NC>>, lds_jv(p, 1)))) return rc;
+  if ((rc = allow_lds(k_jv<NC, 2, false, LIN_FORM<NC>>, lds_jv(p, 2)))) return rc;
+  if ((rc = allow_lds(k_jv<NC, 1, true, LIN_FORM<NC>>, lds_jv(p, 1)))) return rc;
+  if ((rc = allow_lds(k_jv<NC, 2, true, LIN_FORM<NC>>, lds_jv(p, 2)))) return rc;
   if ((rc = allow_lds(k_schur_reg3<NC, RegCfg<NC>::SPLIT, RegCfg<NC>::MINW>, Reg3Cfg<NC>::LDS_BYTES))) return rc;
   if ((rc = allow_lds(k_tprep<NC>, lds_tprep<NC>(p)))) return rc;
   if ((rc = allow_lds(k_tprep<NC, 0, true>, lds_tprep<NC>(p)))) return rc;
   if ((rc = allow_lds(k_tprep<NC, 0, false, true>, lds_tprep<NC>(p)))) return rc;
   if ((rc = allow_lds(k_tprep<NC, 0, true, true>, lds_tprep<NC>(p)))) return rc;
+  if ((rc = allow_lds(k_tprep<NC, 0, false, false, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
+  if ((rc = allow_lds(k_tprep<NC, 0, true, false, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
+  if ((rc = allow_lds(k_tprep<NC, 0, false, true, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
+  if ((rc = allow_lds(k_tprep<NC, 0, true, true, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
   if ((rc = allow_lds(k_backsub<NC>, lds_backsub(p)))) return rc;
   if ((rc = allow_lds(k_backsub<NC, true>, lds_backsub(p)))) return rc;
   if ((rc = allow_lds(k_backsub<NC, false, true>, lds_backsub(p)))) return rc;
@@ -1111,6 +1138,8 @@ static int configure_kernels(cba_problem* p) {
     }
   }
   {
+    // (asked of the generic kernel for every loss: the grid decides how ||J v||^2 is cut into partial sums, and a linear loss's LIN form, which needs
+    // no more registers, has to leave the same bits)
     int per_cu = p->tab_global ? resident_per_cu(k_jv<NC, 1, true>, lds_jv(p, 1), 2) : resident_per_cu(k_jv<NC, 1>, lds_jv(p, 1), 2);
     if (const char* e = std::getenv("CBA_JV_WGS")) per_cu = std::max(1, std::min(std::atoi(e), 8));
     p->jv_grid = (int)std::max<long>(1, std::min<long>((p->N + BLOCK - 1) / BLOCK, (long)p->cus * per_cu));
@@ -1334,6 +1363,7 @@ int cba_create(const cba_problem_desc* d, const cba_options* opt, cba_problem** 
   if (const char* e = std::getenv("CBA_CHOL_EARLY")) p->chol_early = e[0] != '0';
   if (const char* e = std::getenv("CBA_CHOL_ENDS")) p->chol_ends = e[0] != '0';
   if (const char* e = std::getenv("CBA_CHOL_PAIR")) p->chol_pair = e[0] != '0';
+  if (const char* e = std::getenv("CBA_LINEAR_PASS")) p->linear_pass = e[0] != '0';
   if (const char* e = std::getenv("CBA_SPEC_SKIP")) p->spec_skip = e[0] != '0';
   if (const char* e = std::getenv("CBA_SCALE_FUSED")) p->scale_fused = e[0] != '0';
   if (const char* e = std::getenv("CBA_SMALL_SOLVE")) p->small_solve_on = e[0] != '0';
@@ -1670,7 +1700,10 @@ static int run_jv(cba_problem* p, int nv, int* rows_out = nullptr, const double*
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds_jv(p, nv), p->stream, p->obs_u, p->obs_v, p->obs_cam, p->obs_pt,
                        p->N, xvec, p->lay, tab, p->cam_off, p->C, p->loss, p->f_scale, p->v1, p->v2, p->partial4, skip);
   };
-  if (nv == 1) { if (p->tab_global) launch_jv(k_jv<NC, 1, true>); else launch_jv(k_jv<NC, 1>); }
+  if (linear_pass_now<NC>(p)) {
+    if (nv == 1) { if (p->tab_global) launch_jv(k_jv<NC, 1, true, LIN_FORM<NC>>); else launch_jv(k_jv<NC, 1, false, LIN_FORM<NC>>); }
+    else { if (p->tab_global) launch_jv(k_jv<NC, 2, true, LIN_FORM<NC>>); else launch_jv(k_jv<NC, 2, false, LIN_FORM<NC>>); }
+  } else if (nv == 1) { if (p->tab_global) launch_jv(k_jv<NC, 1, true>); else launch_jv(k_jv<NC, 1>); }
   else { if (p->tab_global) launch_jv(k_jv<NC, 2, true>); else launch_jv(k_jv<NC, 2>); }
   int rows = grid;
   if (con_rows) {
@@ -1985,7 +2018,16 @@ static int run_newton_chain(cba_problem* p, double lam, const double* lam_dev, b
                            p->chunk_start, p->n_chunks, p->x, p->lay, p->tab, p->cam_off, p->C, p->loss, p->f_scale, lam, lam_dev, p->V, p->g,
                            p->sinv, p->Trec, p->partial_b, p->flags, p->det, linf ? p->lf : LinFin{});
       };
-      switch (p->det_m) {
+      if (linear_pass_now<NC>(p)) switch (p->det_m) {  // the LIN forms: no pixel loads
+        case 3: launch_tprep(k_tprep<NC, 3, false, false, LIN_FORM<NC>>); break;
+        case 5: launch_tprep(k_tprep<NC, 5, false, false, LIN_FORM<NC>>); break;
+        case 8: launch_tprep(k_tprep<NC, 8, false, false, LIN_FORM<NC>>); break;
+        case 16: { if constexpr (NC == 6) launch_tprep(k_tprep<NC, 16, false, false, LIN_FORM<NC>>); } break;
+        default:
+          if (linf) { if (p->tab_global) launch_tprep(k_tprep<NC, 0, true, true, LIN_FORM<NC>>); else launch_tprep(k_tprep<NC, 0, false, true, LIN_FORM<NC>>); }
+          else if (p->tab_global) launch_tprep(k_tprep<NC, 0, true, false, LIN_FORM<NC>>); else launch_tprep(k_tprep<NC, 0, false, false, LIN_FORM<NC>>);
+          break;
+      } else switch (p->det_m) {
         case 3: launch_tprep(k_tprep<NC, 3>); break;
         case 5: launch_tprep(k_tprep<NC, 5>); break;
         case 8: launch_tprep(k_tprep<NC, 8>); break;
