@@ -3,7 +3,7 @@ of the per-recording stage, the uncertainty report and the reliability report ar
 package stays as cheap)."""
 
 _EXPORTS = {"reconstruct_trajectories": "caliscope_amd.reconstruction", "reconstruct_xyz": "caliscope_amd.reconstruction",
-            "RefineOptions": "caliscope_amd.trajectory_refinement",
+            "RefineOptions": "caliscope_amd.trajectory_refinement", "CovarianceOptions": "caliscope_amd.trajectory_uncertainty",
             "UncertaintyReport": "caliscope_amd.uncertainty", "DeviceUncertainty": "caliscope_amd.uncertainty",
             "ReliabilityReport": "caliscope_amd.reliability", "DeviceReliability": "caliscope_amd.reliability"}
 
