@@ -660,31 +660,48 @@ class CaptureVolume:
                              _known_map=new_row[obj].astype(np.int32))
 
     # -- parameter uncertainty (caliscope_amd/uncertainty.py; the reference has none) ----------------------------------------------
-    def parameter_uncertainty(self, *, refine_intrinsics: bool = False, loss: str = "linear", f_scale: float | None = None, _solver=None):
+    def parameter_uncertainty(self, *, refine_intrinsics: bool = False, loss: str = "linear", f_scale: float | None = None,
+                              include_constraints: bool = False, pixel_sigma: float = 1.0, _solver=None):
         """How well the matched observations determine every posed camera and every world point at the volume's current parameters
         (meaningful after ``optimize()`` with the same ``refine_intrinsics`` and ``loss``): an
         :class:`~caliscope_amd.uncertainty.UncertaintyReport` in the inner-constraint gauge from one device call.  ``f_scale`` is in
         residual units and defaults to ``pixel_f_scale()``.  World points with fewer than two matched observations take no part and
-        have NaN rows in ``point_cov`` / ``point_std``.  A volume with constraints raises ``CalibrationError``: constraint rows couple
-        points and fix the scale, which this version does not model.  ``_solver`` replaces the device call (tests)."""
+        have NaN rows in ``point_cov`` / ``point_std``.  A volume with constraints raises ``CalibrationError`` unless
+        ``include_constraints=True``: then the rows of its ``ConstraintSet`` are rows of the adjustment, weighted
+        ``(pixel_sigma / f_median) / sigma`` as ``optimize()`` weights them (meaningful after ``optimize()`` with the same
+        ``pixel_sigma``).  They couple the points of a board and fix the scale: the report has ``gauge_dim == 6``, and a world point
+        takes part if it has two matched observations or is named by a row.  ``_solver`` replaces the device call (tests)."""
         from caliscope_amd.uncertainty import DeviceUncertainty, build_report
 
-        par, args, used, _, _ = self._free_network_arguments("parameter_uncertainty", "covariance", refine_intrinsics)
+        arrays = self._build_constraint_arrays() if include_constraints and self.constraints is not None else None
+        par, args, used, _, _ = self._free_network_arguments("parameter_uncertainty", "covariance", refine_intrinsics,
+                                                             constraint_groups=None if arrays is None else arrays[:2], allow_constraints=include_constraints)
         backend = _solver or DeviceUncertainty()
-        result = backend.parameter_covariance(*args, loss=loss, f_scale=self.pixel_f_scale() if f_scale is None else float(f_scale))
+        f_scale = self.pixel_f_scale() if f_scale is None else float(f_scale)
+        if arrays is None:
+            result = backend.parameter_covariance(*args, loss=loss, f_scale=f_scale)
+        else:
+            groups_a, groups_b, distances, sigmas = arrays
+            f_median = float(np.median([cam.matrix[0, 0] for cam in self.camera_array.posed_cameras.values()]))
+            new_row = np.cumsum(used, dtype=np.int64) - 1  # the rows of the call: the world points that take part
+            result = backend.parameter_covariance_constrained(*args, new_row[groups_a].astype(np.int32), new_row[groups_b].astype(np.int32), distances,
+                                                              (pixel_sigma / f_median) / sigmas, loss=loss, f_scale=f_scale)
         if not used.all():  # back to the rows of world_points
             point_cov = np.full((len(self.world_points), 3, 3), np.nan)
             point_cov[used] = result.point_cov
             object.__setattr__(result, "point_cov", point_cov)
         return build_report(result, [blk.cam_id for blk in par.blocks], args[1], args[3])
 
-    def _free_network_arguments(self, method: str, what: str, refine_intrinsics: bool):
+    def _free_network_arguments(self, method: str, what: str, refine_intrinsics: bool, constraint_groups=None, allow_constraints: bool = False):
         """What ``parameter_uncertainty`` and ``observation_reliability`` hand their device call: ``(parameterisation, the eight
         positional arguments, used world points (mask), image-point row of every observation of the call, its world-point row)``.
-        Matched observations of world points with at least two of them; a volume with constraints raises ``CalibrationError``."""
-        if self.constraints is not None:
+        Matched observations of world points with at least two of them; a volume with constraints raises ``CalibrationError``
+        unless ``allow_constraints``.  ``constraint_groups`` (groups_a, groups_b): a world point one of them names takes part too,
+        whatever its observations."""
+        if self.constraints is not None and not allow_constraints:
+            hint = "  parameter_uncertainty(include_constraints=True) keeps the rows in the adjustment." if method == "parameter_uncertainty" else ""
             raise CalibrationError(f"{method} handles volumes without constraints: distance constraints couple points and fix the "
-                                   f"scale of the gauge.  Build the volume without its ConstraintSet to get the reprojection-only {what}.")
+                                   f"scale of the gauge.  Build the volume without its ConstraintSet to get the reprojection-only {what}.{hint}")
         mask, camera_indices, image_coords, obj_indices = self._matched_arrays()
         if int(mask.sum()) == 0:
             raise ValueError(f"No matched observations for {method}")
@@ -696,6 +713,9 @@ class CaptureVolume:
             cam_x[i, : blk.n_params] = x[off : off + blk.n_params]
         views = np.bincount(obj_indices, minlength=len(self.world_points))
         used = views >= 2
+        if constraint_groups is not None:
+            for grp in constraint_groups:
+                used[np.asarray(grp).reshape(-1)] = True
         if not used.any():
             raise ValueError("No world point has two matched observations")
         new_row = np.cumsum(used, dtype=np.int64) - 1

@@ -27,6 +27,10 @@ constexpr int COV_POINT_THREADS = 64; // one wave per point
 constexpr int COV_MAX_NCP = 1152;     // the blocked Cholesky's limit (csrc/cba_kernels.h)
 // A pivot of the Jacobi-scaled St (unit diagonal) or D at or below this is "not safely positive": the inverse would have no correct digit.
 constexpr double COV_PIVOT_TINY = 1e-13;
+// Points of one connected component of the constraint graph (cba_parameter_covariance_constrained): the component's V~ lives in LDS as a
+// packed lower triangle, 162 * 163 / 2 doubles = 105.6 KB of the 160 KiB a workgroup has.  54 is the inner-corner count of a 10 x 7 board.
+constexpr int COV_COMPONENT_CAP = 54;
+constexpr int COV_GAUGE_RIGID = 6;    // translation (3), rotation (3): the gauge of a problem with distance rows (they fix the scale)
 
 // inverse of a row-major 3 x 3 by the adjugate; false when the determinant vanishes
 CBA_HD bool cov_inv3(const double* m, double* o) {
@@ -42,7 +46,8 @@ CBA_HD bool cov_inv3(const double* m, double* o) {
 
 // Gauge rows of a camera, N[9][7]: rvec rows -Jl^-1 R in the rotation columns; tvec rows -R in the translation columns and t in the
 // scale column; intrinsics (and the rows 6..8 of a six-parameter camera) zero.
-CBA_HD void cov_gauge_cam(const CamTab& c, double (*N)[COV_GAUGE]) {
+// (G = 6: without the scale column)
+template <int G> CBA_HD void cov_gauge_cam(const CamTab& c, double (*N)[G]) {
   double Ji[9];
   if (!cov_inv3(c.Jl, Ji)) {  // (Jl is singular at |rvec| = 2 pi only: outside the rvec range of a pose)
 #pragma unroll
@@ -51,7 +56,7 @@ CBA_HD void cov_gauge_cam(const CamTab& c, double (*N)[COV_GAUGE]) {
 #pragma unroll
   for (int r = 0; r < 9; ++r)
 #pragma unroll
-    for (int j = 0; j < COV_GAUGE; ++j) N[r][j] = 0.0;
+    for (int j = 0; j < G; ++j) N[r][j] = 0.0;
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -60,14 +65,16 @@ CBA_HD void cov_gauge_cam(const CamTab& c, double (*N)[COV_GAUGE]) {
       N[3 + r][j] = -c.R[3 * r + j];
     }
 #pragma unroll
-  for (int r = 0; r < 3; ++r) N[3 + r][6] = c.t[r];
+  for (int r = 0; r < 3; ++r)
+    if (G > 6) N[3 + r][G - 1] = c.t[r];
 }
 
 // Gauge rows of a point, N[3][7] = [I | -[X]x | X]
-CBA_HD void cov_gauge_point(double X, double Y, double Z, double (*N)[COV_GAUGE]) {
-  N[0][0] = 1.0; N[0][1] = 0.0; N[0][2] = 0.0; N[0][3] = 0.0; N[0][4] = Z;   N[0][5] = -Y;  N[0][6] = X;
-  N[1][0] = 0.0; N[1][1] = 1.0; N[1][2] = 0.0; N[1][3] = -Z;  N[1][4] = 0.0; N[1][5] = X;   N[1][6] = Y;
-  N[2][0] = 0.0; N[2][1] = 0.0; N[2][2] = 1.0; N[2][3] = Y;   N[2][4] = -X;  N[2][5] = 0.0; N[2][6] = Z;
+template <int G> CBA_HD void cov_gauge_point(double X, double Y, double Z, double (*N)[G]) {
+  N[0][0] = 1.0; N[0][1] = 0.0; N[0][2] = 0.0; N[0][3] = 0.0; N[0][4] = Z;   N[0][5] = -Y;
+  N[1][0] = 0.0; N[1][1] = 1.0; N[1][2] = 0.0; N[1][3] = -Z;  N[1][4] = 0.0; N[1][5] = X;
+  N[2][0] = 0.0; N[2][1] = 0.0; N[2][2] = 1.0; N[2][3] = Y;   N[2][4] = -X;  N[2][5] = 0.0;
+  if (G > 6) { N[0][G - 1] = X; N[1][G - 1] = Y; N[2][G - 1] = Z; }
 }
 
 // One observation: residual and Jacobian blocks (project_full), both rows scaled for the robust loss (robust_one per scalar residual,
@@ -128,25 +135,25 @@ CBA_HD bool cov_point_vinv(const double* V, double* Vi) {
 }
 
 // Z = V^-1 Np (3 x 7) of a point
-CBA_HD void cov_point_z(const double* Vi, const double* X, double (*Z)[COV_GAUGE]) {
-  double N[3][COV_GAUGE];
+template <int G> CBA_HD void cov_point_z(const double* Vi, const double* X, double (*Z)[G]) {
+  double N[3][G];
   cov_gauge_point(X[0], X[1], X[2], N);
 #pragma unroll
   for (int p = 0; p < 3; ++p)
 #pragma unroll
-    for (int j = 0; j < COV_GAUGE; ++j) Z[p][j] = cov_sym3(Vi, p, 0) * N[0][j] + cov_sym3(Vi, p, 1) * N[1][j] + cov_sym3(Vi, p, 2) * N[2][j];
+    for (int j = 0; j < G; ++j) Z[p][j] = cov_sym3(Vi, p, 0) * N[0][j] + cov_sym3(Vi, p, 1) * N[1][j] + cov_sym3(Vi, p, 2) * N[2][j];
 }
 
-// the dense part of a point's covariance: V^-1 + Z F Z^T (xx xy xz yy yz zz); F row-major 7 x 7, symmetric
-CBA_HD void cov_point_base(const double* Vi, const double (*Z)[COV_GAUGE], const double* F, double* P) {
-  double ZF[3][COV_GAUGE];
+// the dense part of a point's covariance: V^-1 + Z F Z^T (xx xy xz yy yz zz); F row-major G x G, symmetric
+template <int G> CBA_HD void cov_point_base(const double* Vi, const double (*Z)[G], const double* F, double* P) {
+  double ZF[3][G];
 #pragma unroll
   for (int p = 0; p < 3; ++p)
 #pragma unroll
-    for (int k = 0; k < COV_GAUGE; ++k) {
+    for (int k = 0; k < G; ++k) {
       double s = 0.0;
 #pragma unroll
-      for (int j = 0; j < COV_GAUGE; ++j) s += Z[p][j] * F[j * COV_GAUGE + k];
+      for (int j = 0; j < G; ++j) s += Z[p][j] * F[j * G + k];
       ZF[p][k] = s;
     }
   int e = 0;
@@ -156,7 +163,7 @@ CBA_HD void cov_point_base(const double* Vi, const double (*Z)[COV_GAUGE], const
     for (int q = p; q < 3; ++q) {
       double s = Vi[e];
 #pragma unroll
-      for (int k = 0; k < COV_GAUGE; ++k) s += ZF[p][k] * Z[q][k];
+      for (int k = 0; k < G; ++k) s += ZF[p][k] * Z[q][k];
       P[e++] = s;
     }
 }
@@ -174,7 +181,10 @@ struct CovPlan {
 // Every check of the header, and the plan.  0 or a CBA_ERR_* with `msg` naming the offender (`call`: the entry point the message starts with).
 // `canonical`: the observations of a point are ordered by (camera, bits of u, bits of v, input position) instead of by input position alone,
 // so that the sorted table, and with CBA_DETERMINISTIC=1 every bit computed from it, does not depend on the order of the caller's rows.
-inline int cov_validate(const cba_cov_desc* d, CovPlan& plan, std::string& msg, const char* call = "cba_parameter_covariance", bool canonical = false) {
+// With constraint rows (covariance_constraint_plan.h): `gauge` = 6, `in_row[p]` != 0 for a point some row of positive weight names (it needs
+// no second observation: its component determines it) and `n_con` such rows, which count in the degrees of freedom.
+inline int cov_validate(const cba_cov_desc* d, CovPlan& plan, std::string& msg, const char* call = "cba_parameter_covariance", bool canonical = false,
+                        int gauge = COV_GAUGE, const uint8_t* in_row = nullptr, int64_t n_con = 0) {
   const std::string what = std::string(call) + ": ";
   auto fail = [&](int code, const std::string& m) { msg = what + m; return code; };
   if (d->n_cams <= 0) return fail(CBA_ERR_INVALID, "n_cams must be positive, got " + std::to_string(d->n_cams));
@@ -206,9 +216,11 @@ inline int cov_validate(const cba_cov_desc* d, CovPlan& plan, std::string& msg, 
   for (int32_t c = 0; c < d->n_cams; ++c)
     if (cam_rows[(size_t)c] == 0) return fail(CBA_ERR_INVALID, "camera " + std::to_string(c) + " has no observation");
   for (int64_t p = 0; p < d->n_points; ++p)
-    if (plan.pt_start[(size_t)p + 1] < 2) return fail(CBA_ERR_INVALID, "point " + std::to_string(p) + " has " + std::to_string(plan.pt_start[(size_t)p + 1]) + " observation(s): two are needed");
-  plan.dof = 2 * d->n_obs - ((int64_t)plan.ncp() + 3 * d->n_points) + COV_GAUGE;
-  if (plan.dof <= 0) return fail(CBA_ERR_INVALID, "dof = 2 n_obs - n_params + 7 = " + std::to_string(plan.dof) + " is not positive");
+    if (plan.pt_start[(size_t)p + 1] < 2 && !(in_row && in_row[(size_t)p])) return fail(CBA_ERR_INVALID, "point " + std::to_string(p) + " has " + std::to_string(plan.pt_start[(size_t)p + 1]) + " observation(s): two are needed");
+  plan.dof = 2 * d->n_obs - ((int64_t)plan.ncp() + 3 * d->n_points) + gauge + n_con;
+  if (plan.dof <= 0)
+    return fail(CBA_ERR_INVALID, std::string(n_con ? "dof = 2 n_obs + n_con - n_params + " : "dof = 2 n_obs - n_params + ") + std::to_string(gauge) + " = " +
+                                     std::to_string(plan.dof) + " is not positive");
   for (int64_t p = 0; p < d->n_points; ++p) plan.pt_start[(size_t)p + 1] += plan.pt_start[(size_t)p];
   std::vector<int64_t> next(plan.pt_start.begin(), plan.pt_start.end() - 1);
   plan.order.resize((size_t)d->n_obs);
@@ -267,9 +279,9 @@ inline bool cov_spd_inverse(std::vector<double>& M, int n) {
   return true;
 }
 
-// E = C B D^-1 (n x 7) and F = D^-1 (B^T C B) D^-1 - D^-1 (7 x 7) from C (n x n), B (n x 7), D^-1 (7 x 7), all row-major
+// E = C B D^-1 (n x G) and F = D^-1 (B^T C B) D^-1 - D^-1 (G x G) from C (n x n), B (n x G), D^-1 (G x G), all row-major; G the gauge width
+template <int G = COV_GAUGE>
 inline void cov_gauge_terms(int n, const double* C, const double* B, const double* Dinv, std::vector<double>& E, std::vector<double>& F) {
-  constexpr int G = COV_GAUGE;
   std::vector<double> CB((size_t)n * G, 0.0);
   for (int r = 0; r < n; ++r)
     for (int c = 0; c < n; ++c) {

@@ -33,6 +33,15 @@ struct CovPipeline {
   const std::vector<double>* B_host;     // [ncp][7]
   const std::vector<double>* Dinv_host;  // [7][7]
   double sigma0_sq, cost;
+  // cba_parameter_covariance_constrained (covariance_lib.hip alone reads these; cov_pipeline itself always has gauge = 7, no lists, no entries)
+  int gauge;                   // columns of B, D^-1 and of a point's Z: 7, or 6 with constraint rows
+  const int32_t* free_list;    // device: the points in no constraint row, or nullptr for "every point"
+  int64_t n_free;
+  const int32_t* con_list;     // device: the points of the constraint components
+  int64_t n_con_pts;
+  const int64_t* entry_start;  // device [n_points + 1]: a constrained point's (component camera, Y block) entries
+  const int32_t* entry_cam;    // device [entries]
+  const double* Yc;            // device [entries][27]
 };
 
 __attribute__((visibility("hidden"))) int cov_pipeline(const cba_cov_desc* d, int32_t device, const char* what, bool canonical,

@@ -9,7 +9,10 @@ from a 3 x 3 formula per point.  :meth:`CaptureVolume.parameter_uncertainty` is 
 :class:`UncertaintyReport`: per camera the covariance of its parameters, of its centre (world units) and the standard deviation of
 its orientation (degrees), per world point its covariance.  The reference computes no covariance.
 
-Scope: volumes without distance constraints (constraint rows couple points and fix the scale).
+Scope: reprojection rows, and with ``parameter_covariance_constrained`` (``include/caliscope/uncertainty_constrained.h``) the
+rigid-distance rows of a ``ConstraintSet`` too: the rows couple the points of a board (one connected component per board in a frame,
+at most 54 points each) and fix the scale, so the gauge then has six columns (``gauge_dim == 6``) and the rows count in ``dof``.
+``CaptureVolume.parameter_uncertainty(include_constraints=True)`` takes that path; observation reliability does not have it yet.
 
 There is no CPU fallback: without the library or a GPU the call raises ``BackendError``.  ``_solver`` of the method replaces the
 device call (an object with ``parameter_covariance``, as :class:`DeviceUncertainty`) — the CPU test-suite passes a g++ build of the
@@ -43,15 +46,25 @@ class CovOut(C.Structure):
                 ("dof", _lib.c_int64_p), ("cost", _lib.c_double_p)]
 
 
+class CovConstraints(C.Structure):
+    _fields_ = [("n_con", C.c_int32), ("groups_a", _lib.c_int32_p), ("groups_b", _lib.c_int32_p), ("distances", _lib.c_double_p),
+                ("weights", _lib.c_double_p)]
+
+
 UNCERTAINTY_SIGNATURES = {
     "cba_parameter_covariance": (C.c_int, [C.POINTER(CovDesc), C.c_int32, C.POINTER(CovOut)]),
+}
+# include/caliscope/uncertainty_constrained.h
+CONSTRAINED_UNCERTAINTY_SIGNATURES = {
+    "cba_parameter_covariance_constrained": (C.c_int, [C.POINTER(CovDesc), C.POINTER(CovConstraints), C.c_int32, C.POINTER(CovOut)]),
 }
 
 
 @dataclass(frozen=True)
 class CovarianceResult:
     """What one ``parameter_covariance`` call returns: ``cam_cov`` (n_cams, 9, 9) with the upper-left nparams x nparams used,
-    ``cam_cov_full`` (ncp, ncp), ``point_cov`` (n_points, 3, 3), ``cam_offsets`` (n_cams + 1) into the rows of ``cam_cov_full``."""
+    ``cam_cov_full`` (ncp, ncp), ``point_cov`` (n_points, 3, 3), ``cam_offsets`` (n_cams + 1) into the rows of ``cam_cov_full``.
+    ``gauge_dim`` is 7 (translation, rotation, scale) or, with ``n_constraint_rows`` > 0 distance rows of positive weight, 6."""
 
     cam_cov: np.ndarray
     cam_cov_full: np.ndarray
@@ -60,6 +73,8 @@ class CovarianceResult:
     sigma0_sq: float
     dof: int
     cost: float
+    gauge_dim: int = 7
+    n_constraint_rows: int = 0
 
 
 def check_covariance_arguments(cam_model, cam_nparams, cam_const, cam_x, points, obs_cam, obs_pt, obs_uv, loss, f_scale):
@@ -85,9 +100,37 @@ def check_covariance_arguments(cam_model, cam_nparams, cam_const, cam_x, points,
                 obs_uv=obs_uv, loss=LOSSES[loss], f_scale=float(f_scale))
 
 
-def run_covariance_call(call, args: dict, what: str, last_error) -> CovarianceResult:
+def check_constraint_arguments(groups_a, groups_b, distances, weights):
+    """The constraint rows of a ``parameter_covariance_constrained`` call in the layout of ``cba_cov_constraints``, as a dict
+    (``ValueError`` for arrays of the wrong shape or mismatched lengths; the range of every index and the sign and finiteness of every
+    weight and distance are the library's check).  All ``None``: no rows."""
+    if groups_a is None and groups_b is None and distances is None and weights is None:
+        return None
+    if groups_a is None or groups_b is None or distances is None or weights is None:
+        raise ValueError("parameter_covariance_constrained: groups_a, groups_b, distances and weights go together")
+    groups_a = np.ascontiguousarray(groups_a, dtype=np.int32)
+    groups_b = np.ascontiguousarray(groups_b, dtype=np.int32)
+    distances = np.ascontiguousarray(distances, dtype=np.float64).reshape(-1)
+    weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    n_con = len(distances)
+    if groups_a.shape != (n_con, 4) or groups_b.shape != (n_con, 4) or len(weights) != n_con:
+        raise ValueError(f"parameter_covariance_constrained: groups_a and groups_b must be ({n_con}, 4) and weights ({n_con},), got "
+                         f"{groups_a.shape}, {groups_b.shape}, {weights.shape}")
+    return dict(groups_a=groups_a, groups_b=groups_b, distances=distances, weights=weights)
+
+
+def constraint_struct(con: dict | None):
+    """``cba_cov_constraints`` over the arrays of ``check_constraint_arguments`` (the dict keeps them alive), or None."""
+    if con is None:
+        return None
+    return CovConstraints(n_con=len(con["distances"]), groups_a=_lib.ptr(con["groups_a"]), groups_b=_lib.ptr(con["groups_b"]),
+                          distances=_lib.ptr(con["distances"]), weights=_lib.ptr(con["weights"]))
+
+
+def run_covariance_call(call, args: dict, what: str, last_error, n_constraint_rows: int = 0) -> CovarianceResult:
     """Fill ``cba_cov_desc`` / ``cba_cov_out`` from checked arguments, run ``call(desc_ref, out_ref) -> code`` and collect the result
-    (shared by the device binding and the test harness: same structures, same error type and message)."""
+    (shared by the device binding and the test harness: same structures, same error type and message).  ``n_constraint_rows``: the
+    distance rows of positive weight the call was given; any makes the gauge six-dimensional."""
     n_cams, n_points = len(args["cam_model"]), len(args["points"])
     widths = np.where((args["cam_nparams"] == 6) | (args["cam_nparams"] == 9), args["cam_nparams"], 0).astype(np.int64)  # (others: refused by the call)
     offsets = np.concatenate([[0], np.cumsum(widths)])
@@ -107,7 +150,7 @@ def run_covariance_call(call, args: dict, what: str, last_error) -> CovarianceRe
     for (a, b), e in zip(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)), range(6)):
         full[:, a, b] = full[:, b, a] = point_cov[:, e]
     return CovarianceResult(cam_cov=cam_cov, cam_cov_full=cam_cov_full, point_cov=full, cam_offsets=offsets, sigma0_sq=float(sigma0_sq[0]),
-                            dof=int(dof[0]), cost=float(cost[0]))
+                            dof=int(dof[0]), cost=float(cost[0]), gauge_dim=6 if n_constraint_rows else 7, n_constraint_rows=int(n_constraint_rows))
 
 
 class DeviceUncertainty:
@@ -123,6 +166,19 @@ class DeviceUncertainty:
         lib = _lib.bind(_lib.load(), UNCERTAINTY_SIGNATURES)
         return run_covariance_call(lambda d, o: lib.cba_parameter_covariance(d, self.device_id, o), args, "cba_parameter_covariance",
                                    lambda: _lib.last_error(lib))
+
+    def parameter_covariance_constrained(self, cam_model, cam_nparams, cam_const, cam_x, points, obs_cam, obs_pt, obs_uv, groups_a, groups_b,
+                                         distances, weights, *, loss="linear", f_scale=1.0) -> CovarianceResult:
+        """The same with the rigid-distance rows ``weights * (|mean points[groups_a] - mean points[groups_b]| - distances)`` in the
+        Jacobian (six gauge columns); see ``include/caliscope/uncertainty_constrained.h``.  Without a row of positive weight it is
+        ``parameter_covariance``."""
+        args = check_covariance_arguments(cam_model, cam_nparams, cam_const, cam_x, points, obs_cam, obs_pt, obs_uv, loss, f_scale)
+        con = check_constraint_arguments(groups_a, groups_b, distances, weights)
+        struct = constraint_struct(con)
+        lib = _lib.bind(_lib.load(), CONSTRAINED_UNCERTAINTY_SIGNATURES)
+        n_rows = 0 if con is None else int(np.count_nonzero(con["weights"] > 0))
+        return run_covariance_call(lambda d, o: lib.cba_parameter_covariance_constrained(d, C.byref(struct) if struct is not None else None, self.device_id, o),
+                                   args, "cba_parameter_covariance_constrained", lambda: _lib.last_error(lib), n_constraint_rows=n_rows)
 
 
 # ---- first-order propagation on the host ------------------------------------------------------------------------------------------------
@@ -179,7 +235,9 @@ class UncertaintyReport:
     """Parameter uncertainty of a calibration in the inner-constraint gauge (the covariance of smallest trace among all gauges:
     no camera or point is held fixed).  ``sigma0`` is the a-posteriori standard deviation of unit weight in residual units
     (pixels / fx) under the loss of the call, ``dof`` the degrees of freedom 2 n_obs - n_params + 7.  ``point_cov[i]`` /
-    ``point_std[i]`` belong to row ``i`` of the volume's world points."""
+    ``point_std[i]`` belong to row ``i`` of the volume's world points.  With the distance rows of a ``ConstraintSet`` in the adjustment
+    (``n_constraint_rows`` > 0) the scale is no gauge direction: ``gauge_dim`` is 6 and ``dof`` = 2 n_obs + n_constraint_rows -
+    n_params + 6."""
 
     sigma0: float
     dof: int
@@ -188,6 +246,8 @@ class UncertaintyReport:
     point_std: np.ndarray
     cam_cov_full: np.ndarray
     gauge: str = "inner"
+    gauge_dim: int = 7
+    n_constraint_rows: int = 0
 
     def worst_cameras(self, n: int = 3) -> list:
         """The ``n`` cameras with the largest centre uncertainty, worst first: ``(cam_id, position_std, rotation_std_deg)``."""
@@ -213,8 +273,9 @@ def build_report(result: CovarianceResult, cam_ids, cam_nparams, cam_x) -> Uncer
                                                  rotation_std_deg=float(np.degrees(np.sqrt(max(rot_var, 0.0)))), **free)
     point_std = np.sqrt(np.maximum(np.einsum("ijj->ij", result.point_cov), 0.0))
     return UncertaintyReport(sigma0=float(np.sqrt(max(result.sigma0_sq, 0.0))), dof=result.dof, cameras=cameras, point_cov=result.point_cov,
-                             point_std=point_std, cam_cov_full=result.cam_cov_full)
+                             point_std=point_std, cam_cov_full=result.cam_cov_full, gauge_dim=result.gauge_dim, n_constraint_rows=result.n_constraint_rows)
 
 
-__all__ = ["DeviceUncertainty", "CovarianceResult", "CameraUncertainty", "UncertaintyReport", "check_covariance_arguments", "run_covariance_call",
-           "build_report", "centre_jacobian", "rotation_and_left_jacobian", "UNCERTAINTY_SIGNATURES", "LOSSES"]
+__all__ = ["DeviceUncertainty", "CovarianceResult", "CameraUncertainty", "UncertaintyReport", "check_covariance_arguments", "check_constraint_arguments",
+           "constraint_struct", "run_covariance_call", "build_report", "centre_jacobian", "rotation_and_left_jacobian", "UNCERTAINTY_SIGNATURES",
+           "CONSTRAINED_UNCERTAINTY_SIGNATURES", "LOSSES"]

@@ -57,8 +57,8 @@ typedef struct {
  * Jacobi scaling, the solver's blocked FP64-MFMA Cholesky that builds T = L^-T beside the factor, an MFMA product T T^T, and a
  * workgroup per point for the 3 x 3 formula.  D (7 x 7) is inverted on the host between two launches.
  *
- * Scope: reprojection rows only.  A volume with distance constraints couples points and fixes the scale: not handled here (the
- * Python seam refuses it).
+ * Scope: reprojection rows only.  A volume with distance constraints couples points and fixes the scale: not handled by this entry
+ * point but by the one of uncertainty_constrained.h, which leaves everything here as it is.
  *
  * Reproducibility: U, the cost, B, D and the Schur complement are added with floating-point atomics in the order of arrival, so
  * every output varies in its last bits from run to run (relative to the norm of its block: a few ulp times the condition of St).
