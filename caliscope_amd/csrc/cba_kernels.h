@@ -2116,11 +2116,10 @@ k_tri_pack(double* __restrict__ Sacc, double* __restrict__ tri, int ncp, int dir
 }
 
 // ------------------------------------------------------------------------------------------------
-// Dense solve of the reduced camera system  S dc = rhs  (n <= 1152) by blocked Cholesky, NB = 32.
+// Dense solve of the reduced camera system  S dc = rhs  (n <= 1152) by blocked Cholesky, NB wide (32: chol_schedule.h).
 // The work matrix is (n+1) x ldw, row-major: rows 0..n-1 hold S, row n holds rhs^T.  Row n is "below" every
 // diagonal block, so the panel solves of the factorisation turn it into y^T = (L^-1 rhs)^T for free — the forward
 // substitution needs no kernel of its own; L^T x = y becomes x = T y with T = L^-T built beside the factorisation (k_chol_apply).
-constexpr int NB = 32;
 
 // broadcast lane `src` (wave-uniform) of a double through SGPRs: two v_readlane_b32, no LDS round trip
 __device__ __forceinline__ double readlane_f64(double v, int src) {

@@ -30,6 +30,7 @@
 
 #include "../../include/caliscope_ba.h"
 #include "cba_kernels.h"
+#include "chol_factor.h"
 #include "schur_plan.h"
 #include "host_plan.h"
 #include "wg_binding.h"
@@ -1828,14 +1829,14 @@ static int run_linearize(cba_problem* p, cba_linearization* out) {
 // iteration keeps the host a whole iteration ahead of the device, plain launches are the faster form (round 3, per iteration: cfg2 139 against
 // 149 us, cfg4 645 against 654 — the kernel behind a graph launch starts ~10 us late), and the graph is gone (round 4).
 //
-// The factorisation launches take raw device pointers: cba_parameter_covariance (covariance_lib.hip, which declares the function again)
+// The factorisation launches take raw device pointers: cba_parameter_covariance (covariance_lib.hip, through the declarations of chol_factor.h)
 // factors its own matrix with them.  W: (n + 1) x ldw work matrix (rows 0..n-1 the matrix, both triangles; row n a right-hand side), ldw a
 // multiple of 4; Xinv: chol_xinv_blocks(blocks) NB x NB (the inverses and the side slots of the early update); Tinv: n x ldw, zero on entry outside
 // what a call writes (the upper block triangle); flags[2] is raised by a pivot that is not positive; early: the schedule (chol_schedule.h, which also
 // holds the workgroup counts of a launch — the kernel decodes its role from the same functions).  without_last: see below.  Not part of the C ABI.
 namespace cba {
-__attribute__((visibility("hidden"))) void enqueue_chol_factor(double* W, int n, int ldw, int* flags, long long* trace, double* Xinv, double* Tinv,
-                                                               bool early, hipStream_t stream, bool without_last, bool pair) {
+void enqueue_chol_factor(double* W, int n, int ldw, int* flags, long long* trace, double* Xinv, double* Tinv, bool early, hipStream_t stream,
+                         bool without_last, bool pair) {  // (hidden: chol_factor.h)
   const int nbk = (n + NB - 1) / NB;
   // pair (the solver only; the caller has had the side slots of D_0 and U_10 filled): launch -1 runs inside launch 0
   pair = pair && chol_pair_applies(nbk, early, without_last);
@@ -1852,7 +1853,7 @@ __attribute__((visibility("hidden"))) void enqueue_chol_factor(double* W, int n,
   }
 }
 // CBA_CHOL_EARLY=0 for callers without a handle (cba_parameter_covariance), read per call
-__attribute__((visibility("hidden"))) bool chol_early_from_env() {
+bool chol_early_from_env() {
   const char* e = std::getenv("CBA_CHOL_EARLY");
   return !(e && e[0] == '0');
 }

@@ -35,6 +35,10 @@
 
 namespace cba {
 
+// Block width of the factorisation: the one definition.  k_chol_step and its neighbours (cba_kernels.h), the solver's work matrix (cba_lib.hip)
+// and the covariance's own buffers and k_unc_ttt grid (covariance_lib.hip) all size themselves with it.
+constexpr int NB = 32;
+
 enum CholRole : int { CHOL_FACTOR0 = 0, CHOL_PANEL = 1, CHOL_TRAILING = 2, CHOL_INVERSE = 3 };
 
 // side slots live behind the nbk + 1 inverses of the diagonal blocks, in the same buffer: [2 (nbk + 1) + 1][NB][NB]; the last one is D_0's

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "chol_schedule.h"
 #include "covariance_math.h"
 #include "../../include/caliscope/uncertainty_constrained.h"
 
@@ -50,6 +51,14 @@ struct CovConPlan {
 inline bool cov_fixed_order_requested() {
   const char* e = std::getenv("CBA_DETERMINISTIC");
   return e && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0');
+}
+
+// The refusals only a call with constraint rows knows (the others: cov_msg_* of covariance_math.h), each text once
+inline std::string cov_con_msg_fixed_order(const std::string& what) {
+  return what + ": CBA_DETERMINISTIC=1 with constraint rows: the fixed-order sums are not built for the component kernel";
+}
+inline std::string cov_con_msg_component(const std::string& what, int64_t first_point) {
+  return what + ": the constraint component of point " + std::to_string(first_point) + ": its observations and rows do not determine its points (no positive pivot)";
 }
 
 // 0 or a CBA_ERR_* with `msg` naming the offender.  plan.n_rows == 0 afterwards: the call is the unconstrained one.
@@ -182,7 +191,7 @@ inline size_t cov_con_lds_doubles(int max_m) {
 // Bytes of device memory the call allocates: the buffers of the unconstrained call (six gauge columns) and the tables and stores of the rows,
 // the components and the entries.  As a double: a size beyond 2^63 must still compare.
 inline double cov_con_device_bytes(const cba_cov_desc* d, int32_t ncp, const CovConPlan& plan) {
-  const double n_cams = d->n_cams, n_obs = (double)d->n_obs, n_points = (double)d->n_points, G = COV_GAUGE_RIGID, NBW = 32;
+  const double n_cams = d->n_cams, n_obs = (double)d->n_obs, n_points = (double)d->n_points, G = COV_GAUGE_RIGID, NBW = NB;
   const double ldw = std::ceil(ncp / NBW) * NBW, nbk = ldw / NBW;
   double b = 0.0;
   b += n_cams * (4 + 4 + 8 * 12 + 8 * MAX_NC + 8 * 48) + 4;                     // models, offsets, constants, parameters, tables

@@ -1,7 +1,8 @@
 // cba_parameter_covariance of libcaliscope_ba.so (C ABI: include/caliscope/uncertainty.h): the covariance of every camera's parameters and
 // of every point in the inner-constraint gauge, sigma0^2 pinv(J^T J), from the bordered system with points and multipliers eliminated.
-// The formulas, the per-element arithmetic, the checks and the host-side small matrices are covariance_math.h (shared with
-// tests/native/covariance_harness.cpp); this file holds the kernels and the entry point.  Everything is FP64.
+// The formulas, the per-element arithmetic, the checks, the refusal texts and the host-side small matrices are covariance_math.h (shared with
+// tests/native/covariance_replay.h, the one host replay of this pipeline that the harnesses of the CPU suite run); this file holds the kernels
+// and the entry points.  Everything is FP64.
 //
 //   k_unc_cam        one thread per camera: the CamTab of ba_math.h and the camera's gauge rows, written into B (B starts as Nc).
 //   k_unc_obs        one thread per observation, in point order: project_full + robust_one, the W block A^T B and B^T B stored per
@@ -54,20 +55,13 @@
 #include "covariance_constraint_plan.h"
 #include "covariance_pipeline.h"
 #include "device_call.h"
+#include "chol_factor.h"
 #include "chol_schedule.h"
-
-namespace cba {
-// cba_lib.hip: the launches of the blocked Cholesky on raw device pointers
-__attribute__((visibility("hidden"))) void enqueue_chol_factor(double* W, int n, int ldw, int* flags, long long* trace, double* Xinv, double* Tinv,
-                                                               bool early, hipStream_t stream, bool without_last, bool pair);
-__attribute__((visibility("hidden"))) bool chol_early_from_env();
-}  // namespace cba
 
 using namespace cba;
 
 namespace {
 
-constexpr int NB = 32;  // block width of the Cholesky (cba_kernels.h)
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 enum CovFlag : int { F_POINT = 0, F_DIAG = 1, F_CHOL = 2, F_TINY = 3, F_WHICH = 4, F_COMP = 5, F_COMP_WHICH = 6, N_FLAGS = 8 };
 
@@ -310,17 +304,18 @@ k_unc_d(int64_t n_points, const double* __restrict__ points, const double* __res
     }
 }
 
-// fixed order: thread e < 28 adds the waves' rows of D in order, thread 28 the cameras' shares of the cost
+// fixed order: thread e < COV_D_SUMS (28) adds the waves' rows of D in order, the thread behind them the cameras' shares of the cost
+constexpr int COV_D_SUMS = COV_GAUGE * (COV_GAUGE + 1) / 2;  // the upper triangle of D, as k_unc_d<COV_GAUGE> leaves it per wave
 __global__ void __launch_bounds__(64)
 k_unc_fixed_sums(const double* __restrict__ rows, int n_rows, const double* __restrict__ cam_cost, int32_t n_cams, double* __restrict__ D, double* __restrict__ cost) {
   const int e = threadIdx.x;
-  if (e < 28) {
+  if (e < COV_D_SUMS) {
     double v = 0.0;
-    for (int i = 0; i < n_rows; ++i) v += rows[(int64_t)i * 28 + e];
+    for (int i = 0; i < n_rows; ++i) v += rows[(int64_t)i * COV_D_SUMS + e];
     int j = 0, rest = e;
     while (rest >= COV_GAUGE - j) { rest -= COV_GAUGE - j; ++j; }
     D[j * COV_GAUGE + j + rest] = v;
-  } else if (e == 28) {
+  } else if (e == COV_D_SUMS) {
     double v = 0.0;
     for (int32_t c = 0; c < n_cams; ++c) v += cam_cost[c];
     *cost = v;
@@ -689,8 +684,7 @@ int cov_pipeline_run(const cba_cov_desc* d, int32_t device, const char* what, bo
   CovPlan plan;
   int rc = cov_validate(d, plan, msg, what, canonical, G, con ? con->in_row.data() : nullptr, con ? con->n_rows : 0);
   if (rc) return err(rc, msg);
-  if (con && cov_fixed_order_requested())
-    return err(CBA_ERR_UNSUPPORTED, std::string(what) + ": CBA_DETERMINISTIC=1 with constraint rows: the fixed-order sums are not built for the component kernel");
+  if (con && cov_fixed_order_requested()) return err(CBA_ERR_UNSUPPORTED, cov_con_msg_fixed_order(what));
   rc = select_device(device, what);
   if (rc) return rc;
   const int32_t n_cams = d->n_cams, ncp = plan.ncp();
@@ -736,7 +730,7 @@ int cov_pipeline_run(const cba_cov_desc* d, int32_t device, const char* what, bo
   const bool fixed_order = !con && cov_fixed_order_requested();  // (as caliscope_amd/engine_cache.py reads it)
   const int64_t d_blocks_all = (n_points + COV_BLOCK - 1) / COV_BLOCK;
   const int d_grid = (int)(d_blocks_all < COV_D_BLOCKS ? d_blocks_all : COV_D_BLOCKS), d_rows = d_grid * (COV_BLOCK / 64);
-  double* dD_rows = fixed_order ? buf.make<double>(d_rows, 28) : nullptr;
+  double* dD_rows = fixed_order ? buf.make<double>(d_rows, COV_D_SUMS) : nullptr;
   double* dcam_cost = fixed_order ? buf.make<double>(n_cams) : nullptr;
   double* dXinv = buf.make<double>(chol_xinv_blocks(nbk), NB * NB);  // the inverses of the diagonal blocks and the side slots of the early update
   // the tables of the constraint components and what their kernels store
@@ -816,17 +810,13 @@ int cov_pipeline_run(const cba_cov_desc* d, int32_t device, const char* what, bo
   buf.out(D.data(), (const double*)dD, G * G + 1);
   buf.out(flags.data(), (const int*)dflags, N_FLAGS);
   if (buf.status()) return buf.result(what);
-  if (flags[F_POINT])
-    return err(CBA_ERR_NUMERIC, std::string(what) + ": point " + std::to_string(flags[F_WHICH] - 1) + ": its observations do not determine it (rays parallel or not finite)");
-  if (flags[F_COMP])
-    return err(CBA_ERR_NUMERIC, std::string(what) + ": the constraint component of point " + std::to_string(flags[F_COMP_WHICH] - 1) +
-                                    ": its observations and rows do not determine its points (no positive pivot)");
+  if (flags[F_POINT]) return err(CBA_ERR_NUMERIC, cov_msg_point(what, flags[F_WHICH] - 1));
+  if (flags[F_COMP]) return err(CBA_ERR_NUMERIC, cov_con_msg_component(what, flags[F_COMP_WHICH] - 1));
   const double cost = D[G * G];
   D.resize(G * G);
   for (int j = 0; j < G; ++j)
     for (int m = j + 1; m < G; ++m) D[(size_t)m * G + j] = D[(size_t)j * G + m];
-  if (!std::isfinite(cost) || !cov_spd_inverse(D, G))
-    return err(CBA_ERR_NUMERIC, std::string(what) + ": the points do not fix the " + (G == COV_GAUGE ? "seven" : "six") + " gauge directions (all on one line, or not finite)");
+  if (!std::isfinite(cost) || !cov_spd_inverse(D, G)) return err(CBA_ERR_NUMERIC, cov_msg_gauge(what, G));
   const double sigma0_sq = 2.0 * cost / (double)plan.dof;
   const double* dDinv = buf.in(D.data(), G * G);
   if (buf.status()) return buf.result(what);
@@ -842,9 +832,7 @@ int cov_pipeline_run(const cba_cov_desc* d, int32_t device, const char* what, bo
   buf.out(C.data(), (const double*)dC, ncp, ncp);
   buf.out(B.data(), (const double*)dB, ncp, G);
   if (buf.status()) return buf.result(what);
-  if (flags[F_DIAG] || flags[F_CHOL] || flags[F_TINY])
-    return err(CBA_ERR_NUMERIC, std::string(what) + ": the reduced camera system is not positive definite beyond the gauge (a pivot is not safely positive): "
-                                                    "the scene does not determine every camera parameter");
+  if (flags[F_DIAG] || flags[F_CHOL] || flags[F_TINY]) return err(CBA_ERR_NUMERIC, cov_msg_not_pd(what));
   const CovPipeline pipe = {&plan, n_cams, ncp, n_obs, n_points, dorder, dpt_start, dcam_sorted, dcam_off, dtab, dpoints, dobs_uv, dY, dVinv, dZ, dC,
                             &C, &B, &D, sigma0_sq, cost, G, dfree, n_free, cd.pts, con ? (int64_t)con->pts.size() : 0, cd.entry_start, dentry_cam, cd.Yc};
   return finish(pipe);
@@ -853,12 +841,10 @@ int cov_pipeline_run(const cba_cov_desc* d, int32_t device, const char* what, bo
 // The point blocks, the checks of the results and the caller's arrays: what both entry points do with the pipeline's C.
 template <int G>
 int cov_outputs(const CovPipeline& pipe, const char* what, cba_cov_out* out) {
-    const CovPlan& plan = *pipe.plan;
-    const int32_t n_cams = pipe.n_cams, ncp = pipe.ncp;
+    const int32_t ncp = pipe.ncp;
     const int64_t n_points = pipe.n_points;
     const std::vector<double>& C = *pipe.C_host;
-    const size_t n_S = (size_t)ncp * ncp;
-    const double sigma0_sq = pipe.sigma0_sq, cost = pipe.cost;
+    const double sigma0_sq = pipe.sigma0_sq;
     Buffers buf;
     std::vector<double> point_cov;
     if (out->point_cov) {
@@ -879,24 +865,13 @@ int cov_outputs(const CovPipeline& pipe, const char* what, cba_cov_out* out) {
       buf.out(point_cov.data(), (const double*)dout, n_points, 6);
       if (buf.status()) return buf.result(what);
       for (double v : point_cov)
-        if (!std::isfinite(v)) return err(CBA_ERR_NUMERIC, std::string(what) + ": a point covariance is not finite");
+        if (!std::isfinite(v)) return err(CBA_ERR_NUMERIC, cov_msg_not_finite(what, "point"));
     }
     for (double v : C)
-      if (!std::isfinite(v)) return err(CBA_ERR_NUMERIC, std::string(what) + ": a camera covariance is not finite");
+      if (!std::isfinite(v)) return err(CBA_ERR_NUMERIC, cov_msg_not_finite(what, "camera"));
     // outputs, written only now: a failed call leaves the caller's arrays alone
     if (out->point_cov) std::copy(point_cov.begin(), point_cov.end(), out->point_cov);
-    if (out->cam_cov_full)
-      for (size_t i = 0; i < n_S; ++i) out->cam_cov_full[i] = sigma0_sq * C[i];
-    if (out->cam_cov)
-      for (int32_t c = 0; c < n_cams; ++c) {
-        const int32_t off = plan.cam_off[(size_t)c], np = plan.cam_off[(size_t)c + 1] - off;
-        for (int r = 0; r < MAX_NC; ++r)
-          for (int q = 0; q < MAX_NC; ++q)
-            out->cam_cov[((size_t)c * MAX_NC + r) * MAX_NC + q] = (r < np && q < np) ? sigma0_sq * C[(size_t)(off + r) * ncp + off + q] : 0.0;
-      }
-    if (out->sigma0_sq) *out->sigma0_sq = sigma0_sq;
-    if (out->dof) *out->dof = plan.dof;
-    if (out->cost) *out->cost = cost;
+    cov_write_outputs(*pipe.plan, C, sigma0_sq, pipe.cost, out);
     return CBA_OK;
 }
 

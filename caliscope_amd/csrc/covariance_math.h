@@ -1,7 +1,7 @@
 // Per-element arithmetic and host-side checks of cba_parameter_covariance (include/caliscope/uncertainty.h): the gauge columns of a
 // camera and of a point, the Jacobian products of one observation, the 3 x 3 pieces of one point, and on the host the validation with
-// the point-sorted order, the inverse of the 7 x 7 gauge matrix D and the rank-7 terms of the point formula.  Compiled by hipcc into
-// covariance_lib.hip and by g++ into tests/native/covariance_harness.cpp.
+// the point-sorted order, the inverse of the 7 x 7 gauge matrix D, the rank-7 terms of the point formula, the refusal texts and the
+// camera outputs.  Compiled by hipcc into covariance_lib.hip and by g++ into tests/native/covariance_replay.h (the harnesses of the tests).
 //
 // Notation (header): H = J^T J = [[U, W], [W^T, V]], N = [Nc; Np] with J N = 0, D = Np^T V^-1 Np, B = Nc - W V^-1 Np,
 // St = U - W V^-1 W^T + B D^-1 B^T, C = St^-1, Z_i = V_i^-1 Np_i, Y_a = W_a V_i^-1 (camera block of observation a, 9 x 3),
@@ -239,6 +239,40 @@ inline int cov_validate(const cba_cov_desc* d, CovPlan& plan, std::string& msg, 
     }
   }
   return CBA_OK;
+}
+
+// The numeric refusals of the calls, each text once: the library and the host replay of the tests (tests/native/covariance_replay.h) say
+// them through these, and the CPU and GPU tests match on them.  `what`: the entry point the message starts with.
+inline std::string cov_msg_point(const std::string& what, int64_t p) {
+  return what + ": point " + std::to_string(p) + ": its observations do not determine it (rays parallel or not finite)";
+}
+inline std::string cov_msg_gauge(const std::string& what, int gauge) {
+  return what + ": the points do not fix the " + (gauge == COV_GAUGE ? "seven" : "six") + " gauge directions (all on one line, or not finite)";
+}
+inline std::string cov_msg_not_pd(const std::string& what) {
+  return what + ": the reduced camera system is not positive definite beyond the gauge (a pivot is not safely positive): "
+                "the scene does not determine every camera parameter";
+}
+inline std::string cov_msg_not_finite(const std::string& what, const char* which) {  // which: "point" or "camera"
+  return what + ": a " + which + " covariance is not finite";
+}
+
+// The camera outputs and the scalars of a call from C = St^-1 (n x n, both triangles): sigma0^2 C into cam_cov_full, its diagonal blocks
+// zero-padded to nine wide into cam_cov.  A NULL output is left out.
+inline void cov_write_outputs(const CovPlan& plan, const std::vector<double>& C, double sigma0_sq, double cost, cba_cov_out* out) {
+  const int32_t n_cams = (int32_t)plan.cam_off.size() - 1, ncp = plan.ncp();
+  if (out->cam_cov_full)
+    for (size_t i = 0; i < C.size(); ++i) out->cam_cov_full[i] = sigma0_sq * C[i];
+  if (out->cam_cov)
+    for (int32_t c = 0; c < n_cams; ++c) {
+      const int32_t off = plan.cam_off[(size_t)c], np = plan.cam_off[(size_t)c + 1] - off;
+      for (int r = 0; r < MAX_NC; ++r)
+        for (int q = 0; q < MAX_NC; ++q)
+          out->cam_cov[((size_t)c * MAX_NC + r) * MAX_NC + q] = (r < np && q < np) ? sigma0_sq * C[(size_t)(off + r) * ncp + off + q] : 0.0;
+    }
+  if (out->sigma0_sq) *out->sigma0_sq = sigma0_sq;
+  if (out->dof) *out->dof = plan.dof;
+  if (out->cost) *out->cost = cost;
 }
 
 // In-place inverse of a symmetric positive definite n x n (row-major, both triangles) by Cholesky after a symmetric Jacobi scaling;

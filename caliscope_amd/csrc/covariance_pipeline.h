@@ -3,6 +3,7 @@
 // lists them) and the numeric refusals on the way.  `finish` runs while the device buffers of the call are alive and returns the call's
 // code; whatever it allocates it owns.  Nothing is written to a caller's array before `finish` does so.  `canonical` is cov_validate's: the
 // order of a point's observations in the sorted table (cba_parameter_covariance keeps the input order, as it always has).
+// tests/native/covariance_replay.h is this pipeline on the host for the CPU suite (CovReplay mirrors CovPipeline): a step added here is added there.
 #pragma once
 #include <cstdint>
 #include <functional>

@@ -125,7 +125,7 @@ extern "C" int cba_observation_reliability(const cba_cov_desc* d, int32_t device
   if (!d || !out) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
   return cov_pipeline(d, device, what, true, [&](const CovPipeline& pipe) -> int {
     for (double v : *pipe.C_host)
-      if (!std::isfinite(v)) return err(CBA_ERR_NUMERIC, std::string(what) + ": a camera covariance is not finite");
+      if (!std::isfinite(v)) return err(CBA_ERR_NUMERIC, cov_msg_not_finite(what, "camera"));
     const int64_t n_obs = pipe.n_obs;
     Buffers buf;
     double* dr = buf.make<double>(n_obs, 3);

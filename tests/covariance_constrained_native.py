@@ -2,7 +2,7 @@
 (tests/native/covariance_constrained_harness.cpp), a `_solver` hook on it, and what the tests of the constrained covariance share: the
 scenes, the float64 eigenvalue pseudo-inverse of the oracle's J^T J with the constraint rows in J and SIX eigenvalues zeroed (the
 reference), the bordered formula with a dense V~^-1 in numpy (the second CPU formulation) and the comparison by the rule of
-tests.covariance_native.check_against_pinv with six for seven."""
+tests.covariance_native.check_result_against_pinv with six for seven; the row scaling, the pseudo-inverse and that rule are its helpers."""
 from __future__ import annotations
 
 import ctypes as C
@@ -231,25 +231,8 @@ def robust_jacobian(sc, loss="linear", f_scale=1.0):
     ga, gb, dist, w = sc["con"]
     J = joint_jacobian(sc["x"], sc["par"], sc["cam"], sc["uv"], sc["obj"], ga, gb, dist, w).toarray()
     f = joint_residuals(sc["x"], sc["par"], sc["cam"], sc["uv"], sc["obj"], ga, gb, dist, w)
-    if loss == "linear":
-        return J, 0.5 * float(f @ f), np.ones(len(f)), f
-    assert loss == "soft_l1"
-    z = (f / f_scale) ** 2
-    t = 1.0 + z
-    rho0, rho1, rho2 = 2.0 * (np.sqrt(t) - 1.0), t ** -0.5, -0.5 * t ** -1.5
-    js = np.sqrt(np.maximum(rho1 + 2.0 * rho2 * z, np.finfo(float).eps))
-    return J * js[:, None], 0.5 * f_scale ** 2 * float(rho0.sum()), js, f
-
-
-def pinv_blocks(J, ncp):
-    """(pinv(J^T J)_cc, the 3 x 3 diagonal blocks of pinv(J^T J)_pp, eigenvalues ascending) by eigh with the SIX smallest eigenvalues zeroed."""
-    lam, Q = np.linalg.eigh(J.T @ J)
-    inv = np.zeros_like(lam)
-    inv[6:] = 1.0 / lam[6:]
-    P = (Q * inv) @ Q.T
-    n_pts = (J.shape[1] - ncp) // 3
-    pp = np.stack([P[ncp + 3 * i: ncp + 3 * i + 3, ncp + 3 * i: ncp + 3 * i + 3] for i in range(n_pts)])
-    return P[:ncp, :ncp], pp, lam
+    js, cost = cn.robust_row_scale(f, loss, f_scale)
+    return J * js[:, None], cost, js, f
 
 
 def bordered_blocks(J, N6, ncp):
@@ -278,7 +261,7 @@ def _reference(key, loss, f_scale):
     sc = key_scene(key)
     J, cost, js, f = robust_jacobian(sc, loss, f_scale)
     ncp = sc["par"].n_camera_params
-    cc, pp, lam = pinv_blocks(J, ncp)
+    cc, pp, lam = cn.pinv_blocks(J, ncp, gauge=6)
     N6 = cn.gauge_matrix(sc["par"], sc["x"])[:, :6]
     bc, bp = bordered_blocks(J, N6, ncp)
     dof = J.shape[0] - J.shape[1] + 6
@@ -293,26 +276,8 @@ def reference(key, loss="linear", f_scale=1.0):
 
 
 def check_against_pinv(result, key, loss="linear", f_scale=1.0, report=print):
-    """The tolerance rule of tests.covariance_native.check_against_pinv with six for seven: exactly six eigenvalues below 1e-12 lambda_max; the
-    two CPU formulations agree to 1e-8; the code under test differs from the pinv by at most ten times their disagreement, with a floor of 1e-12,
-    relative to the block-wise max-norm; dof equal, cost and sigma0^2 to 1e-12 relative.  Returns the measured figures."""
-    ref = reference(key, loss, f_scale)
-    lam = ref["lam"]
-    assert int(np.sum(lam < 1e-12 * lam[-1])) == 6, lam[:9] / lam[-1]
-    assert ref["dis_c"] <= 1e-8 and ref["dis_p"] <= 1e-8, (ref["dis_c"], ref["dis_p"])
-    s2 = ref["sigma0_sq"]
-    err_c = cn._rel(result.cam_cov_full, s2 * ref["cc"])
-    err_p = cn._rel_blocks(result.point_cov, s2 * ref["pp"])
-    figures = dict(key=key, loss=loss, dis_c=ref["dis_c"], dis_p=ref["dis_p"], err_c=err_c, err_p=err_p, lam7=float(lam[6] / lam[-1]))
-    report(figures)
-    assert result.gauge_dim == 6 and result.n_constraint_rows == int(np.count_nonzero(key_scene(key)["con"][3] > 0))
-    assert result.dof == ref["dof"]
-    assert abs(result.cost - ref["cost"]) <= 1e-12 * ref["cost"] and abs(result.sigma0_sq - s2) <= 1e-12 * s2
-    assert err_c <= max(10.0 * ref["dis_c"], 1e-12), figures
-    assert err_p <= max(10.0 * ref["dis_p"], 1e-12), figures
-    par = key_scene(key)["par"]
-    for i, (blk, off) in enumerate(zip(par.blocks, par.camera_param_offsets)):  # the per-camera blocks are those of the full matrix
-        n = blk.n_params
-        assert np.array_equal(result.cam_cov[i, :n, :n], result.cam_cov_full[off: off + n, off: off + n])
-        assert not result.cam_cov[i, n:].any() and not result.cam_cov[i, :, n:].any()
-    return figures
+    """tests.covariance_native.check_result_against_pinv with six null directions for a scene of this module, and: the call reports six gauge
+    columns and the rows of positive weight.  Returns the measured figures."""
+    sc = key_scene(key)
+    assert result.gauge_dim == 6 and result.n_constraint_rows == int(np.count_nonzero(sc["con"][3] > 0))
+    return cn.check_result_against_pinv(result, reference(key, loss, f_scale), sc["par"], 6, report, key=key, loss=loss)

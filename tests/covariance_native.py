@@ -148,28 +148,33 @@ def planar_degenerate_scene():
 
 
 # ---- the two CPU formulations -----------------------------------------------------------------------------------------------------------
-def robust_jacobian(sc, loss="linear", f_scale=1.0):
-    """(J dense, cost, sigma0^2 dof) with the oracle's residuals and Jacobian, rows scaled as scipy's least_squares scales them."""
-    from oracle.residuals import joint_jacobian, joint_residuals
-
-    par, x = sc["par"], sc["x"]
-    J = joint_jacobian(x, par, sc["cam"], sc["uv"], sc["obj"]).toarray()
-    f = joint_residuals(x, par, sc["cam"], sc["uv"], sc["obj"])
+def robust_row_scale(f, loss="linear", f_scale=1.0):
+    """(js, cost) of residuals f: the factor scipy's least_squares scales every row of J by for the loss (ones for the linear loss), and
+    the cost 0.5 sum rho."""
     if loss == "linear":
-        return J, 0.5 * float(f @ f)
+        return np.ones(len(f)), 0.5 * float(f @ f)
     assert loss == "soft_l1"
     z = (f / f_scale) ** 2
     t = 1.0 + z
     rho0, rho1, rho2 = 2.0 * (np.sqrt(t) - 1.0), t ** -0.5, -0.5 * t ** -1.5
-    js = np.sqrt(np.maximum(rho1 + 2.0 * rho2 * z, np.finfo(float).eps))
-    return J * js[:, None], 0.5 * f_scale ** 2 * float(rho0.sum())
+    return np.sqrt(np.maximum(rho1 + 2.0 * rho2 * z, np.finfo(float).eps)), 0.5 * f_scale ** 2 * float(rho0.sum())
 
 
-def pinv_blocks(J, ncp):
-    """(pinv(J^T J)_cc, the 3 x 3 diagonal blocks of pinv(J^T J)_pp, eigenvalues ascending) by eigh with the 7 smallest eigenvalues zeroed."""
+def robust_jacobian(sc, loss="linear", f_scale=1.0):
+    """(J dense, cost) with the oracle's residuals and Jacobian, rows scaled as scipy's least_squares scales them."""
+    from oracle.residuals import joint_jacobian, joint_residuals
+
+    par, x = sc["par"], sc["x"]
+    J = joint_jacobian(x, par, sc["cam"], sc["uv"], sc["obj"]).toarray()
+    js, cost = robust_row_scale(joint_residuals(x, par, sc["cam"], sc["uv"], sc["obj"]), loss, f_scale)
+    return J * js[:, None], cost
+
+
+def pinv_blocks(J, ncp, gauge=7):
+    """(pinv(J^T J)_cc, the 3 x 3 diagonal blocks of pinv(J^T J)_pp, eigenvalues ascending) by eigh with the ``gauge`` smallest eigenvalues zeroed."""
     lam, Q = np.linalg.eigh(J.T @ J)
     inv = np.zeros_like(lam)
-    inv[7:] = 1.0 / lam[7:]
+    inv[gauge:] = 1.0 / lam[gauge:]
     P = (Q * inv) @ Q.T
     n_pts = (J.shape[1] - ncp) // 3
     pp = np.stack([P[ncp + 3 * i: ncp + 3 * i + 3, ncp + 3 * i: ncp + 3 * i + 3] for i in range(n_pts)])
@@ -260,26 +265,31 @@ def reference(key, loss="linear", f_scale=1.0):
     return _reference(key, loss, float(f_scale))
 
 
-def check_against_pinv(result, key, loss="linear", f_scale=1.0, report=print):
-    """The tolerance rule: exactly seven eigenvalues below 1e-12 lambda_max; the two CPU formulations agree to 1e-8 (the scene is
-    strong enough to test with: a weak one cannot widen the tolerance); the code under test differs from the pinv by at most ten times their disagreement, with a floor of
-    1e-12, relative to the block-wise max-norm.  Returns the measured figures."""
-    ref = reference(key, loss, f_scale)
+def check_result_against_pinv(result, ref, par, gauge, report=print, **labels):
+    """The tolerance rule, for a reference of ``gauge`` null directions (7, or 6 with constraint rows: tests/covariance_constrained_native.py):
+    exactly ``gauge`` eigenvalues below 1e-12 lambda_max; the two CPU formulations agree to 1e-8 (the scene is strong enough to test with: a
+    weak one cannot widen the tolerance); the code under test differs from the pinv by at most ten times their disagreement, with a floor of
+    1e-12, relative to the block-wise max-norm; dof equal, cost and sigma0^2 to 1e-12 relative; the per-camera blocks are those of the full
+    matrix, zero-padded.  Returns the measured figures (``labels`` in front; the first eigenvalue behind the gauge as lam<gauge + 1>)."""
     lam = ref["lam"]
-    assert int(np.sum(lam < 1e-12 * lam[-1])) == 7, lam[:9] / lam[-1]
+    assert int(np.sum(lam < 1e-12 * lam[-1])) == gauge, lam[:9] / lam[-1]
     assert ref["dis_c"] <= 1e-8 and ref["dis_p"] <= 1e-8, (ref["dis_c"], ref["dis_p"])
     s2 = ref["sigma0_sq"]
     err_c = _rel(result.cam_cov_full, s2 * ref["cc"])
     err_p = _rel_blocks(result.point_cov, s2 * ref["pp"])
-    figures = dict(key=key, loss=loss, dis_c=ref["dis_c"], dis_p=ref["dis_p"], err_c=err_c, err_p=err_p, lam8=float(lam[7] / lam[-1]))
+    figures = dict(**labels, dis_c=ref["dis_c"], dis_p=ref["dis_p"], err_c=err_c, err_p=err_p, **{f"lam{gauge + 1}": float(lam[gauge] / lam[-1])})
     report(figures)
     assert result.dof == ref["dof"]
     assert abs(result.cost - ref["cost"]) <= 1e-12 * ref["cost"] and abs(result.sigma0_sq - s2) <= 1e-12 * s2
     assert err_c <= max(10.0 * ref["dis_c"], 1e-12), figures
     assert err_p <= max(10.0 * ref["dis_p"], 1e-12), figures
-    par = key_scene(key)["par"]
     for i, (blk, off) in enumerate(zip(par.blocks, par.camera_param_offsets)):  # the per-camera blocks are those of the full matrix
         n = blk.n_params
         assert np.array_equal(result.cam_cov[i, :n, :n], result.cam_cov_full[off: off + n, off: off + n])
         assert not result.cam_cov[i, n:].any() and not result.cam_cov[i, :, n:].any()
     return figures
+
+
+def check_against_pinv(result, key, loss="linear", f_scale=1.0, report=print):
+    """check_result_against_pinv for a scene of this module (seven null directions).  Returns the measured figures."""
+    return check_result_against_pinv(result, reference(key, loss, f_scale), key_scene(key)["par"], 7, report, key=key, loss=loss)

@@ -1,7 +1,7 @@
 """Rigs, reference and metrics for the tests of the dense camera-system solve S s_c = rhs (tests/test_dense_solve_cases.py on the CPU,
 tests/test_dense_solve_gpu.py on the device).
 
-The sweep puts the camera-parameter count ncp at the edges of the solve's 32-wide blocks (csrc/cba_kernels.h: NB = 32, k_small_solve up to
+The sweep puts the camera-parameter count ncp at the edges of the solve's 32-wide blocks (NB of csrc/chol_schedule.h; csrc/cba_kernels.h: k_small_solve up to
 SMALL_N = 96, k_chol_step + k_chol_apply beyond or under CBA_SMALL_SOLVE=0): last blocks of 1, 2, 3, 4, 30, 31 and 32 live rows, 1 to 11 blocks,
 and mixed rigs of nine-parameter pinhole and six-parameter fisheye cameras whose offsets are no multiples of nine, so that block boundaries fall
 inside cameras of either width.  Scenes are those of tests/helpers.small_problem: 300 points, min(n_cams, 6) views per point, linear loss.
@@ -16,7 +16,7 @@ import functools
 
 import numpy as np
 
-NB, SMALL_N = 32, 96  # csrc/cba_kernels.h
+NB, SMALL_N = 32, 96  # csrc/chol_schedule.h, csrc/cba_kernels.h
 U53 = 2.0 ** -53
 LAMS = (1e-3, 1e-7, 1e-10)
 

@@ -18,7 +18,7 @@ from caliscope_amd.synthetic import make_scene, project_pinhole_bc5
 
 CHUNK = 256        # observations per chunk (csrc/cba_kernels.h CHUNK)
 CS_MAX_PTS = 512   # point ids per super-chunk of k_build_cs (csrc/cba_kernels.h CS_MAX_PTS)
-NB = 32            # pivot block of the small-component Cholesky (csrc/cba_kernels.h NB)
+NB = 32            # pivot block of the small-component Cholesky (csrc/chol_schedule.h NB)
 CON_SMALL_M = 2 * NB
 CON_SMALL_LDS = 120 * 1024
 
