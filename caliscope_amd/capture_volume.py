@@ -699,7 +699,7 @@ class CaptureVolume:
         unless ``allow_constraints``.  ``constraint_groups`` (groups_a, groups_b): a world point one of them names takes part too,
         whatever its observations."""
         if self.constraints is not None and not allow_constraints:
-            hint = "  parameter_uncertainty(include_constraints=True) keeps the rows in the adjustment." if method == "parameter_uncertainty" else ""
+            hint = f"  {method}(include_constraints=True) keeps the rows in the adjustment."
             raise CalibrationError(f"{method} handles volumes without constraints: distance constraints couple points and fix the "
                                    f"scale of the gauge.  Build the volume without its ConstraintSet to get the reprojection-only {what}.{hint}")
         mask, camera_indices, image_coords, obj_indices = self._matched_arrays()
@@ -726,34 +726,55 @@ class CaptureVolume:
 
     # -- reliability of the observations (caliscope_amd/reliability.py; the reference has a percentile cut only) ---------------------
     def observation_reliability(self, *, refine_intrinsics: bool = False, loss: str = "linear", f_scale: float | None = None, delta0: float = 4.13,
-                                _solver=None):
+                                include_constraints: bool = False, pixel_sigma: float = 1.0, _solver=None):
         """How strongly the other observations control every matched observation at the volume's current parameters (meaningful after
         ``optimize()`` with the same ``refine_intrinsics`` and ``loss``), and how far its residual is from what the adjustment allows: a
         :class:`~caliscope_amd.reliability.ReliabilityReport` from one device call, aligned to the rows of ``image_points``.  Rows that
         take no part (unmatched, or on a world point with fewer than two matched observations) are NaN.  ``f_scale`` is in residual
         units and defaults to ``pixel_f_scale()``; ``delta0`` is the non-centrality behind ``mdb_px`` (4.13: Baarda's value for a
-        significance of 0.1 % and a power of 80 %, a convention).  Reprojection rows only: a volume with constraints raises
-        ``CalibrationError``.  Under a robust loss ``w`` is an approximation.  ``_solver`` replaces the device call (tests)."""
+        significance of 0.1 % and a power of 80 %, a convention).  A volume with constraints raises ``CalibrationError`` unless
+        ``include_constraints=True``: then the rows of its ``ConstraintSet`` are rows of the adjustment, weighted
+        ``(pixel_sigma / f_median) / sigma`` as ``optimize()`` and ``parameter_uncertainty(include_constraints=True)`` weight them, a
+        world point named by a row takes part whatever its observations, the report has ``gauge_dim == 6`` and its ``constraint_*``
+        arrays judge every constraint instance (``_constraint_instances()``'s order).  Under a robust loss ``w`` is an approximation.
+        ``_solver`` replaces the device call (tests)."""
         from caliscope_amd.reliability import DeviceReliability, build_report
 
-        par, args, _, rows, obs_world = self._free_network_arguments("observation_reliability", "reliability report", refine_intrinsics)
+        arrays = self._build_constraint_arrays() if include_constraints and self.constraints is not None else None
+        par, args, used, rows, obs_world = self._free_network_arguments("observation_reliability", "reliability report", refine_intrinsics,
+                                                                        constraint_groups=None if arrays is None else arrays[:2],
+                                                                        allow_constraints=include_constraints)
         backend = _solver or DeviceReliability()
-        result = backend.observation_reliability(*args, loss=loss, f_scale=self.pixel_f_scale() if f_scale is None else float(f_scale))
+        f_scale = self.pixel_f_scale() if f_scale is None else float(f_scale)
+        weights, instances = None, ()
+        if arrays is None:
+            result = backend.observation_reliability(*args, loss=loss, f_scale=f_scale)
+        else:
+            groups_a, groups_b, distances, sigmas = arrays
+            f_median = float(np.median([cam.matrix[0, 0] for cam in self.camera_array.posed_cameras.values()]))
+            new_row = np.cumsum(used, dtype=np.int64) - 1  # the rows of the call: the world points that take part
+            weights = (pixel_sigma / f_median) / sigmas
+            result = backend.observation_reliability_constrained(*args, new_row[groups_a].astype(np.int32), new_row[groups_b].astype(np.int32), distances,
+                                                                 weights, loss=loss, f_scale=f_scale)
+            instances = [(c, si) for c, si, _, _ in self._constraint_instances()]
         return build_report(result, rows, len(self.image_points._df), args[2][args[5], 0], [blk.cam_id for blk in par.blocks], args[5], obs_world,
-                            len(self.world_points), delta0=delta0)
+                            len(self.world_points), delta0=delta0, constraint_weights=weights, constraint_instances=instances)
 
     def filter_by_w_test(self, alpha: float = 0.001, *, refine_intrinsics: bool = False, loss: str = "linear", f_scale: float | None = None,
-                         _solver=None) -> "CaptureVolume":
+                         include_constraints: bool = False, pixel_sigma: float = 1.0, _solver=None) -> "CaptureVolume":
         """One pass of data snooping (Baarda's w-test): the observations whose standardised residual contradicts the adjustment at the
         two-sided significance ``alpha`` go, judged by ``observation_reliability()`` at the volume's current parameters.  A blunder
         smears onto the other observations of its point, so per world point at most ONE observation is removed: the one with the
         largest ``|w|``, if that exceeds the critical value, and never if the point would be left with fewer than two matched views.
         Unlike ``filter_outliers`` nothing goes from a volume in which nothing is wrong beyond the share ``alpha`` predicts.  The
         volume is assembled from the row mask as ``filter_outliers`` assembles it (unmatched rows go, world points left without an
-        observation are pruned, ``optimization_status`` is None).  For the next pass re-optimise the result and call again."""
+        observation are pruned, ``optimization_status`` is None).  For the next pass re-optimise the result and call again.
+        ``include_constraints`` / ``pixel_sigma`` as in ``observation_reliability``: the observations are then judged in the adjustment
+        with the distance rows; constraint rows are reported there and never removed here."""
         from caliscope_amd.reliability import critical_value, snooping_mask
 
-        report = self.observation_reliability(refine_intrinsics=refine_intrinsics, loss=loss, f_scale=f_scale, _solver=_solver)
+        report = self.observation_reliability(refine_intrinsics=refine_intrinsics, loss=loss, f_scale=f_scale, include_constraints=include_constraints,
+                                              pixel_sigma=pixel_sigma, _solver=_solver)
         mask, _, _, obj_indices = self._matched_arrays()
         views = np.bincount(obj_indices, minlength=len(self.world_points))
         keep = snooping_mask(report.max_abs_w[mask], obj_indices, views, critical_value(alpha))

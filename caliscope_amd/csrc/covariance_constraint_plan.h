@@ -25,6 +25,7 @@ namespace cba {
 
 struct CovConPlan {
   int64_t n_rows = 0;               // kept rows (weight > 0)
+  int64_t n_caller = 0;             // the caller's rows (n_con)
   int32_t n_comp = 0;               // components with at least one row
   int32_t max_m = 0;                // points of the largest component
   std::vector<int64_t> row_src;     // [n_rows] the caller's row, grouped by component
@@ -71,6 +72,7 @@ inline int cov_con_components(int64_t n_points, const cba_cov_constraints* con, 
   if (!con || con->n_con == 0) return CBA_OK;
   if (con->n_con < 0) return fail(CBA_ERR_INVALID, "n_con must not be negative, got " + std::to_string(con->n_con));
   if (!con->groups_a || !con->groups_b || !con->distances || !con->weights) return fail(CBA_ERR_INVALID, "null constraint array");
+  plan.n_caller = con->n_con;
   std::vector<int64_t> kept;
   for (int64_t r = 0; r < con->n_con; ++r) {
     const double w = con->weights[r], dd = con->distances[r];
@@ -206,6 +208,20 @@ inline double cov_con_device_bytes(const cba_cov_desc* d, int32_t ncp, const Cov
   b += (n_points + 1) * 8 + (double)plan.n_entries() * (4 + 8 * 27);            // entries: camera and Y block
   b += n_points * 8 * 6 + 8.0 * ncp * G;                                        // the point pass: output and E
   return b;
+}
+
+// cameras of the component that the most cameras see (cov_con_tables done)
+inline int64_t cov_con_max_cams(const CovConPlan& plan) {
+  int64_t m = 0;
+  for (int32_t k = 0; k < plan.n_comp; ++k) m = std::max(m, plan.comp_cam[(size_t)k + 1] - plan.comp_cam[(size_t)k]);
+  return m;
+}
+
+// What cba_observation_reliability_constrained allocates on top: s_j, the caller's row and the component of every row, the G store laid out as
+// Yc, v (nine doubles per camera of the widest component, per row), seven doubles per observation, three per constraint row of the caller, the counts
+inline double cov_con_reliability_bytes(const cba_cov_desc* d, const CovConPlan& plan) {
+  return (double)plan.n_rows * (8 + 8 + 4 + 8.0 * 9 * (double)cov_con_max_cams(plan)) + (double)plan.n_entries() * 8 * 27 + (double)d->n_obs * 8 * 7 +
+         (double)plan.n_caller * 8 * 3 + 8 * 3;
 }
 
 // CBA_OK, or CBA_ERR_UNSUPPORTED with `msg` when the call needs more than `limit` bytes

@@ -55,6 +55,7 @@
 #include "covariance_constraint_plan.h"
 #include "covariance_pipeline.h"
 #include "device_call.h"
+#include "reliability_constraint_math.h"
 #include "chol_factor.h"
 #include "chol_schedule.h"
 
@@ -500,6 +501,7 @@ struct ConDev {
   const int32_t* obs_loc;
   const int64_t* entry_start; // [n_points + 1]
   double* Yc;                 // [entries][27] Y_c[:, i] of a constrained point i and a camera c of its component
+  double* row_s;              // [n_rows] |X c_j^T|^2 for cba_observation_reliability_constrained, or nullptr: not formed
 };
 
 // one thread per kept constraint row: residual, robust scaling, the scaled Jacobian entries (u and the slots' coefficients), rho into the cost
@@ -530,6 +532,7 @@ k_unc_con_rows(ConDev cd, const double* __restrict__ points, int loss, double f_
 //   4. per camera c that sees the component: pa = W_c,k^T (n x 9, from the stored W blocks), pb = X pa, B_c -= W_c,k Z_k (atomics),
 //      pa = Y_c^T = X^T pb to the entry store, Schur(c, c') -= Y_c W_c',k^T for the component's cameras c' >= c, upper triangle: one atomic per
 //      entry of a block (the sum over the observations of c' is formed by the entry's thread).
+// With cd.row_s (cba_observation_reliability_constrained) between 2. and 3.: a wave per row j, lanes over the entries of q = X c_j^T, s_j = |q|^2 by shuffles.
 // A pivot that is not safely positive raises F_COMP with the component's first point; every branch on it is uniform (all threads read the pivot from LDS).
 constexpr int COV_COMP_THREADS = 256;
 __global__ void __launch_bounds__(COV_COMP_THREADS)
@@ -605,6 +608,22 @@ k_unc_component(ConDev cd, const int64_t* __restrict__ pt_start, const int32_t* 
     for (int i = j + t; i < n; i += NT) Vt[cov_tri(i, j)] = i == j ? xjj : cov_tri_inverse_entry(Vt, i, j, col, xjj);
     __syncthreads();
   }
+  if (cd.row_s) {  // (uniform; Vt is X from here to the end)
+    for (int64_t r = r0 + (t >> 6); r < r0 + n_rows; r += NT / 64) {
+      int32_t loc[8];
+      double coef[8];
+#pragma unroll
+      for (int s = 0; s < 8; ++s) { loc[s] = cd.row_loc[r * 8 + s]; coef[s] = cd.row_coef[r * 8 + s]; }
+      const double u[3] = {cd.row_u[r * 3], cd.row_u[r * 3 + 1], cd.row_u[r * 3 + 2]};
+      double acc = 0.0;
+      for (int i = t & 63; i < n; i += 64) {
+        const double q = rel_con_x_row(Vt, i, loc, coef, u);
+        acc += q * q;
+      }
+      acc = wave_sum(acc);
+      if ((t & 63) == 0) cd.row_s[r] = acc;
+    }
+  }
   // 3.
   for (int i = t; i < m; i += NT) {
     const int64_t p = pts[i];
@@ -677,8 +696,10 @@ k_unc_component(ConDev cd, const int64_t* __restrict__ pt_start, const int32_t* 
 
 // Everything up to C with G gauge columns.  `con` (G = 6 only): the components of the constraint rows (cov_con_components, at least one row);
 // its tables are completed here, once the observations are sorted.  nullptr (G = 7): the launches of the unconstrained call, as they always were.
+// `reliability` (with `con`): the caller is cba_observation_reliability_constrained; its stores count in the memory check and k_unc_component leaves row_s.
 template <int G>
-int cov_pipeline_run(const cba_cov_desc* d, int32_t device, const char* what, bool canonical, CovConPlan* con, const std::function<int(const CovPipeline&)>& finish) {
+int cov_pipeline_run(const cba_cov_desc* d, int32_t device, const char* what, bool canonical, CovConPlan* con, const std::function<int(const CovPipeline&)>& finish,
+                     bool reliability = false) {
   // every index the kernels use, checked on the host before anything reaches the device
   std::string msg;
   CovPlan plan;
@@ -693,7 +714,7 @@ int cov_pipeline_run(const cba_cov_desc* d, int32_t device, const char* what, bo
     cov_con_tables(plan, d->obs_cam, n_cams, n_points, *con);
     size_t free_bytes = 0, total_bytes = 0;
     if (hipMemGetInfo(&free_bytes, &total_bytes) != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": hipMemGetInfo failed");
-    rc = cov_con_memory_check(cov_con_device_bytes(d, ncp, *con), (double)free_bytes, msg, what);
+    rc = cov_con_memory_check(cov_con_device_bytes(d, ncp, *con) + (reliability ? cov_con_reliability_bytes(d, *con) : 0.0), (double)free_bytes, msg, what);
     if (rc) return err(rc, msg);
   }
   const int nbk = (ncp + NB - 1) / NB, ldw = nbk * NB;  // the work matrix and T padded to whole blocks: k_unc_ttt reads without bounds
@@ -737,6 +758,7 @@ int cov_pipeline_run(const cba_cov_desc* d, int32_t device, const char* what, bo
   ConDev cd = {};
   const int32_t* dfree = nullptr;
   const int32_t* dentry_cam = nullptr;
+  const int64_t* drow_src = nullptr;
   int64_t n_free = n_points;
   if (con) {
     n_free = (int64_t)con->free_pts.size();
@@ -759,6 +781,10 @@ int cov_pipeline_run(const cba_cov_desc* d, int32_t device, const char* what, bo
     cd.Yc = buf.make<double>(con->n_entries(), 3 * MAX_NC);
     dfree = buf.in(con->free_pts.data(), con->free_pts.size());
     dentry_cam = buf.in(con->entry_cam.data(), con->entry_cam.size());
+    if (reliability) {
+      cd.row_s = buf.make<double>(con->n_rows);
+      drow_src = buf.in(con->row_src.data(), con->n_rows);
+    }
   }
   // zeroed in one block: the work matrix [ldw + 1][ldw] and T [ldw][ldw] (first: their rows are read sixteen bytes at a time), U [n_cams][81],
   // Schur [ncp][ncp], D [G][G], cost [1], flags
@@ -834,7 +860,8 @@ int cov_pipeline_run(const cba_cov_desc* d, int32_t device, const char* what, bo
   if (buf.status()) return buf.result(what);
   if (flags[F_DIAG] || flags[F_CHOL] || flags[F_TINY]) return err(CBA_ERR_NUMERIC, cov_msg_not_pd(what));
   const CovPipeline pipe = {&plan, n_cams, ncp, n_obs, n_points, dorder, dpt_start, dcam_sorted, dcam_off, dtab, dpoints, dobs_uv, dY, dVinv, dZ, dC,
-                            &C, &B, &D, sigma0_sq, cost, G, dfree, n_free, cd.pts, con ? (int64_t)con->pts.size() : 0, cd.entry_start, dentry_cam, cd.Yc};
+                            &C, &B, &D, sigma0_sq, cost, G, dfree, n_free, cd.pts, con ? (int64_t)con->pts.size() : 0, cd.entry_start, dentry_cam, cd.Yc,
+                            con, con ? con->n_rows : 0, cd.row_pt, cd.row_u, cd.row_coef, cd.row_dist, cd.row_weight, drow_src, cd.row_s, cd.comp_row, cd.comp_cam, cd.cams};
   return finish(pipe);
 }
 
@@ -880,6 +907,18 @@ int cov_outputs(const CovPipeline& pipe, const char* what, cba_cov_out* out) {
 // covariance_pipeline.h: everything up to C, shared with cba_observation_reliability (reliability_lib.hip)
 int cba::cov_pipeline(const cba_cov_desc* d, int32_t device, const char* what, bool canonical, const std::function<int(const CovPipeline&)>& finish) {
   return cov_pipeline_run<COV_GAUGE>(d, device, what, canonical, nullptr, finish);
+}
+
+// the same with the constraint rows, for cba_observation_reliability_constrained; without a row of positive weight: cov_pipeline itself
+int cba::cov_pipeline_constrained(const cba_cov_desc* d, const cba_cov_constraints* constraints, int32_t device, const char* what, bool canonical,
+                                  const std::function<int(const CovPipeline&)>& finish) {
+  if (d->n_points <= 0 || d->n_points > INT32_MAX) return cov_pipeline(d, device, what, canonical, finish);  // (refused there)
+  std::string msg;
+  CovConPlan con;
+  const int rc = cov_con_components(d->n_points, constraints, con, msg, what);
+  if (rc) return err(rc, msg);
+  if (con.n_rows == 0) return cov_pipeline(d, device, what, canonical, finish);
+  return cov_pipeline_run<COV_GAUGE_RIGID>(d, device, what, canonical, &con, finish, true);
 }
 
 extern "C" int cba_parameter_covariance(const cba_cov_desc* d, int32_t device, cba_cov_out* out) {

@@ -4,14 +4,20 @@
 // code; whatever it allocates it owns.  Nothing is written to a caller's array before `finish` does so.  `canonical` is cov_validate's: the
 // order of a point's observations in the sorted table (cba_parameter_covariance keeps the input order, as it always has).
 // tests/native/covariance_replay.h is this pipeline on the host for the CPU suite (CovReplay mirrors CovPipeline): a step added here is added there.
+// cov_pipeline_constrained is the same with the rows of cba_parameter_covariance_constrained (six gauge columns; without a row of positive
+// weight it IS cov_pipeline) for cba_observation_reliability_constrained: it also has k_unc_component leave s_j = |X c_j^T|^2 per row and hands
+// on the device tables of the rows.  Those steps (s_j, and everything behind C) are replayed in tests/native/reliability_constrained_replay.h.
 #pragma once
 #include <cstdint>
 #include <functional>
 #include <vector>
 
 #include "covariance_math.h"
+#include "../../include/caliscope/uncertainty_constrained.h"
 
 namespace cba {
+
+struct CovConPlan;  // covariance_constraint_plan.h
 
 struct CovPipeline {
   const CovPlan* plan;  // order, pt_start, cam_off, dof (host)
@@ -43,9 +49,24 @@ struct CovPipeline {
   const int64_t* entry_start;  // device [n_points + 1]: a constrained point's (component camera, Y block) entries
   const int32_t* entry_cam;    // device [entries]
   const double* Yc;            // device [entries][27]
+  // cov_pipeline_constrained with rows (reliability_lib.hip reads these; otherwise null / 0): the kept rows, grouped by component
+  const CovConPlan* con;       // host plan
+  int64_t n_rows;
+  const int32_t* row_pt;       // device [n_rows][8]
+  const double* row_u;         // device [n_rows][3]
+  const double* row_coef;      // device [n_rows][8]
+  const double* row_dist;      // device [n_rows]
+  const double* row_weight;    // device [n_rows]
+  const int64_t* row_src;      // device [n_rows] the caller's row
+  const double* row_s;         // device [n_rows] |X c_j^T|^2
+  const int64_t* comp_row;     // device [n_comp + 1]
+  const int64_t* comp_cam;     // device [n_comp + 1] into cams
+  const int32_t* cams;         // device: the cameras that see a component, ascending
 };
 
 __attribute__((visibility("hidden"))) int cov_pipeline(const cba_cov_desc* d, int32_t device, const char* what, bool canonical,
                                                        const std::function<int(const CovPipeline&)>& finish);
+__attribute__((visibility("hidden"))) int cov_pipeline_constrained(const cba_cov_desc* d, const cba_cov_constraints* constraints, int32_t device, const char* what,
+                                                                   bool canonical, const std::function<int(const CovPipeline&)>& finish);
 
 }  // namespace cba

@@ -11,7 +11,11 @@ standardised residual ``w_j = f_j / (sigma0 sqrt(r_j))`` of Baarda's / Pope's da
 The reference's only outlier tool cuts a fixed share of the raw reprojection errors, and the raw residual of a weakly controlled
 observation is small however wrong the observation is.
 
-Scope: reprojection rows only (volumes without distance constraints).  Under a robust loss ``J`` and the residuals are the scaled ones
+Scope: reprojection rows, and with ``observation_reliability_constrained`` (``include/caliscope/reliability_constrained.h``,
+``csrc/reliability_constraint_math.h``; ``include_constraints=True`` of the two methods) the rigid-distance rows of a ``ConstraintSet`` too:
+they are rows of ``J`` like any other, the gauge then has six columns, and every constraint row gets its own redundancy number, ``w``
+and smallest detectable error — a wrong board dimension is a blunder in a constraint row.  Components of at most 54 points, as
+``parameter_covariance_constrained``.  Under a robust loss ``J`` and the residuals are the scaled ones
 scipy forms and ``w`` is an approximation.  One removal per world point per pass: a blunder smears onto the other observations of its
 point.
 
@@ -22,14 +26,14 @@ call (an object with ``observation_reliability``, as :class:`DeviceReliability`)
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, field, replace
 from statistics import NormalDist
 
 import numpy as np
 
 from caliscope_amd import _lib
 from caliscope_amd.exceptions import BackendError
-from caliscope_amd.uncertainty import CovDesc, check_covariance_arguments
+from caliscope_amd.uncertainty import CovConstraints, CovDesc, check_constraint_arguments, check_covariance_arguments, constraint_struct
 
 REL_R_TINY = 1e-10  # csrc/reliability_math.h
 DELTA0 = 4.13       # Baarda's non-centrality for alpha0 = 0.1 % and beta0 = 80 %: a convention, not a measurement
@@ -45,11 +49,23 @@ RELIABILITY_SIGNATURES = {
 }
 
 
+class RelConOut(C.Structure):
+    _fields_ = [("redundancy", _lib.c_double_p), ("w", _lib.c_double_p), ("residual", _lib.c_double_p), ("n_uncontrolled", _lib.c_int64_p)]
+
+
+# include/caliscope/reliability_constrained.h
+RELIABILITY_CONSTRAINED_SIGNATURES = {
+    "cba_observation_reliability_constrained": (C.c_int, [C.POINTER(CovDesc), C.POINTER(CovConstraints), C.c_int32, C.POINTER(RelOut), C.POINTER(RelConOut)]),
+}
+
+
 @dataclass(frozen=True)
 class ReliabilityResult:
     """What one ``observation_reliability`` call returns, rows in the order of the call's observations: ``redundancy`` (n_obs, 2, 2) the
     blocks ``R_oo`` (not clamped), ``w`` (n_obs, 2) with NaN where ``r_j <= REL_R_TINY``, ``residual`` (n_obs, 2) in residual units
-    (pixels / fx0), scaled for the loss."""
+    (pixels / fx0), scaled for the loss.  ``observation_reliability_constrained`` adds, in the order of the call's constraint rows (NaN for
+    a row of weight 0): ``constraint_redundancy``, ``constraint_w`` and ``constraint_residual`` (n_con,), the last being
+    ``weight * (length - distance)`` scaled for the loss; ``gauge_dim`` is 6 when a row of positive weight took part, else 7."""
 
     redundancy: np.ndarray
     w: np.ndarray
@@ -58,6 +74,23 @@ class ReliabilityResult:
     dof: int
     cost: float
     n_uncontrolled: int
+    gauge_dim: int = 7
+    constraint_redundancy: np.ndarray | None = None
+    constraint_w: np.ndarray | None = None
+    constraint_residual: np.ndarray | None = None
+    n_constraints_uncontrolled: int = 0
+
+
+def run_reliability_constrained_call(call, args: dict, con: dict | None, what: str, last_error) -> ReliabilityResult:
+    """``run_reliability_call`` for ``call(desc_ref, out_ref, con_out_ref) -> code`` with the constraint rows of
+    ``check_constraint_arguments`` (shared by the device binding and the test harness)."""
+    n_con = 0 if con is None else len(con["distances"])
+    cr, cw, cf, cbad = np.full(n_con, np.nan), np.full(n_con, np.nan), np.full(n_con, np.nan), np.zeros(1, dtype=np.int64)
+    con_out = RelConOut(redundancy=_lib.ptr(cr), w=_lib.ptr(cw), residual=_lib.ptr(cf), n_uncontrolled=_lib.ptr(cbad))
+    res = run_reliability_call(lambda d, o: call(d, o, C.byref(con_out)), args, what, last_error)
+    n_rows = 0 if con is None else int(np.count_nonzero(con["weights"] > 0))
+    return replace(res, gauge_dim=6 if n_rows else 7, constraint_redundancy=cr, constraint_w=cw, constraint_residual=cf,
+                   n_constraints_uncontrolled=int(cbad[0]))
 
 
 def run_reliability_call(call, args: dict, what: str, last_error) -> ReliabilityResult:
@@ -96,6 +129,19 @@ class DeviceReliability:
         return run_reliability_call(lambda d, o: lib.cba_observation_reliability(d, self.device_id, o), args, "cba_observation_reliability",
                                     lambda: _lib.last_error(lib))
 
+    def observation_reliability_constrained(self, cam_model, cam_nparams, cam_const, cam_x, points, obs_cam, obs_pt, obs_uv, groups_a, groups_b,
+                                            distances, weights, *, loss="linear", f_scale=1.0) -> ReliabilityResult:
+        """The same with the rigid-distance rows ``weights * (|mean points[groups_a] - mean points[groups_b]| - distances)`` in the
+        adjustment, and the redundancy, ``w`` and scaled residual of every such row; see ``include/caliscope/reliability_constrained.h``.
+        Without a row of positive weight it is ``observation_reliability`` (``gauge_dim == 7``, the constraint arrays NaN)."""
+        args = check_covariance_arguments(cam_model, cam_nparams, cam_const, cam_x, points, obs_cam, obs_pt, obs_uv, loss, f_scale)
+        con = check_constraint_arguments(groups_a, groups_b, distances, weights)
+        struct = constraint_struct(con)
+        lib = _lib.bind(_lib.load(), RELIABILITY_CONSTRAINED_SIGNATURES)
+        return run_reliability_constrained_call(
+            lambda d, o, c: lib.cba_observation_reliability_constrained(d, C.byref(struct) if struct is not None else None, self.device_id, o, c), args, con,
+            "cba_observation_reliability_constrained", lambda: _lib.last_error(lib))
+
 
 def critical_value(alpha: float) -> float:
     """The two-sided critical value of the standard normal distribution at significance ``alpha`` (3.29 for 0.1 %)."""
@@ -115,7 +161,13 @@ class ReliabilityReport:
     rows), ``residual_px`` (n, 2) the residuals (scaled for the loss) in pixels, ``mdb_px`` (n, 2) the smallest blunder detectable with
     Baarda's ``delta0``: ``delta0 sigma0 fx / sqrt(r)``, infinite for an uncontrolled row.  ``camera_redundancy`` maps a cam_id to the
     mean ``r`` over its rows, ``point_redundancy`` (n_world_points,) is the mean ``r`` per world point (NaN for a point that took no
-    part).  Under a robust loss ``w`` is an approximation."""
+    part).  Under a robust loss ``w`` is an approximation.
+
+    With ``include_constraints=True`` the distance rows of the volume's ``ConstraintSet`` took part (``gauge_dim == 6``) and are judged
+    too, one entry per instance in the order of ``constraint_instances`` (``(constraint, sync_index)``): ``constraint_redundancy``,
+    ``constraint_w``, ``constraint_residual_m`` (measured minus nominal distance, scaled for the loss, in world units) and
+    ``constraint_mdb_m`` (``delta0 sigma0 / (weight sqrt(r))``: the smallest error of the nominal distance the adjustment would
+    detect).  Without it these arrays are empty."""
 
     sigma0: float
     dof: int
@@ -128,6 +180,12 @@ class ReliabilityReport:
     point_redundancy: np.ndarray
     n_uncontrolled: int
     delta0: float = DELTA0
+    gauge_dim: int = 7
+    constraint_redundancy: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    constraint_w: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    constraint_residual_m: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    constraint_mdb_m: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    constraint_instances: tuple = ()
 
     @property
     def max_abs_w(self) -> np.ndarray:
@@ -148,9 +206,25 @@ class ReliabilityReport:
         rows = rows[np.argsort(-m[rows], kind="stable")][: max(int(n), 0)]
         return [(int(i), float(m[i]), float(self.redundancy[i].min())) for i in rows]
 
+    def flagged_constraints(self, alpha: float = 0.001) -> np.ndarray:
+        """The constraint instances (positions in ``constraint_instances``) whose ``|w|`` exceeds the two-sided critical value at ``alpha``,
+        ascending."""
+        with np.errstate(invalid="ignore"):
+            return np.flatnonzero(np.abs(self.constraint_w) > critical_value(alpha))
 
-def build_report(result: ReliabilityResult, rows, n_rows, fx, cam_ids, obs_cam, obs_world, n_world, delta0=DELTA0) -> ReliabilityReport:
-    """The report of one call.  ``rows``: the image-point row of every observation of the call, ``n_rows`` the number of image-point
+    def worst_constraints(self, n: int = 10) -> list:
+        """The ``n`` constraint instances with the largest ``|w|``, worst first: ``(position, |w|, r, residual_m)``."""
+        m = np.abs(self.constraint_w)
+        rows = np.flatnonzero(np.isfinite(m))
+        rows = rows[np.argsort(-m[rows], kind="stable")][: max(int(n), 0)]
+        return [(int(i), float(m[i]), float(self.constraint_redundancy[i]), float(self.constraint_residual_m[i])) for i in rows]
+
+
+def build_report(result: ReliabilityResult, rows, n_rows, fx, cam_ids, obs_cam, obs_world, n_world, delta0=DELTA0, constraint_weights=None,
+                 constraint_instances=()) -> ReliabilityReport:
+    """The report of one call.  ``constraint_weights`` (with a result of ``observation_reliability_constrained``): the weight of every
+    constraint row of the call, which turns its scaled residual and its smallest detectable error into world units; ``constraint_instances``
+    names the rows.  ``rows``: the image-point row of every observation of the call, ``n_rows`` the number of image-point
     rows; ``fx`` (n_obs,) the focal length that turns residual units into pixels (``fx0`` of the observation's camera);
     ``cam_ids[obs_cam]`` and ``obs_world`` name the camera and the world-point row of every observation."""
     rows = np.asarray(rows, dtype=np.int64)
@@ -175,7 +249,20 @@ def build_report(result: ReliabilityResult, rows, n_rows, fx, cam_ids, obs_cam, 
     return ReliabilityReport(sigma0=sigma0, dof=result.dof, redundancy=spread(r, 2), redundancy_uv=spread(result.redundancy[:, 0, 1], 0),
                              w=spread(result.w, 2), residual_px=spread(result.residual * fx, 2), mdb_px=spread(mdb, 2),
                              camera_redundancy=camera_redundancy, point_redundancy=point_redundancy, n_uncontrolled=result.n_uncontrolled,
-                             delta0=float(delta0))
+                             delta0=float(delta0), gauge_dim=result.gauge_dim, **_constraint_columns(result, constraint_weights, sigma0, delta0),
+                             constraint_instances=tuple(constraint_instances))
+
+
+def _constraint_columns(result: ReliabilityResult, weights, sigma0, delta0) -> dict:
+    if weights is None or result.constraint_redundancy is None:
+        return {}
+    weights = np.asarray(weights, dtype=np.float64)
+    r = result.constraint_redundancy
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mdb = np.where(r > REL_R_TINY, delta0 * sigma0 / (weights * np.sqrt(np.clip(r, REL_R_TINY, 1.0))), np.inf)
+        mdb = np.where(np.isnan(r), np.nan, mdb)
+        residual_m = result.constraint_residual / weights
+    return dict(constraint_redundancy=r, constraint_w=result.constraint_w, constraint_residual_m=residual_m, constraint_mdb_m=mdb)
 
 
 def snooping_mask(max_abs_w, obs_world, views, critical) -> np.ndarray:
@@ -194,5 +281,6 @@ def snooping_mask(max_abs_w, obs_world, views, critical) -> np.ndarray:
     return keep
 
 
-__all__ = ["DeviceReliability", "ReliabilityResult", "ReliabilityReport", "RelOut", "RELIABILITY_SIGNATURES", "run_reliability_call", "critical_value",
+__all__ = ["DeviceReliability", "ReliabilityResult", "ReliabilityReport", "RelOut", "RelConOut", "RELIABILITY_SIGNATURES",
+           "RELIABILITY_CONSTRAINED_SIGNATURES", "run_reliability_call", "run_reliability_constrained_call", "critical_value",
            "build_report", "snooping_mask", "REL_R_TINY", "DELTA0"]

@@ -12,7 +12,7 @@ its orientation (degrees), per world point its covariance.  The reference comput
 Scope: reprojection rows, and with ``parameter_covariance_constrained`` (``include/caliscope/uncertainty_constrained.h``) the
 rigid-distance rows of a ``ConstraintSet`` too: the rows couple the points of a board (one connected component per board in a frame,
 at most 54 points each) and fix the scale, so the gauge then has six columns (``gauge_dim == 6``) and the rows count in ``dof``.
-``CaptureVolume.parameter_uncertainty(include_constraints=True)`` takes that path; observation reliability does not have it yet.
+``CaptureVolume.parameter_uncertainty(include_constraints=True)`` takes that path, and so does ``observation_reliability(include_constraints=True)`` (``caliscope_amd/reliability.py``).
 
 There is no CPU fallback: without the library or a GPU the call raises ``BackendError``.  ``_solver`` of the method replaces the
 device call (an object with ``parameter_covariance``, as :class:`DeviceUncertainty`) — the CPU test-suite passes a g++ build of the
