@@ -4,6 +4,8 @@ package stays as cheap)."""
 
 _EXPORTS = {"reconstruct_trajectories": "caliscope_amd.reconstruction", "reconstruct_xyz": "caliscope_amd.reconstruction",
             "RefineOptions": "caliscope_amd.trajectory_refinement", "CovarianceOptions": "caliscope_amd.trajectory_uncertainty",
+            "SmootherOptions": "caliscope_amd.trajectory_smoother", "smooth_trajectories": "caliscope_amd.trajectory_smoother",
+            "smoothed_frame": "caliscope_amd.trajectory_smoother", "DeviceTrajectorySmoother": "caliscope_amd.trajectory_smoother",
             "UncertaintyReport": "caliscope_amd.uncertainty", "DeviceUncertainty": "caliscope_amd.uncertainty",
             "ReliabilityReport": "caliscope_amd.reliability", "DeviceReliability": "caliscope_amd.reliability"}
 

@@ -113,23 +113,27 @@ CBA_HD void traj_cov_pair(const double (*Mc)[MAX_NC], const double (*A2)[MAX_NC]
   }
 }
 
-CBA_HD void traj_cov_store(int64_t s, const double* total, const double* calib, int status, double* cov, double* cov_calib, uint8_t* cov_status) {
+CBA_HD void traj_cov_store(int64_t s, const double* total, const double* calib, const double* noise, int status, double* cov, double* cov_calib,
+                           uint8_t* cov_status, double* meas_cov) {
 #if defined(__HIPCC__)
 #pragma unroll
 #endif
   for (int i = 0; i < 6; ++i) {
     cov[6 * s + i] = total[i];
     if (cov_calib) cov_calib[6 * s + i] = calib[i];
+    if (meas_cov) meas_cov[6 * s + i] = noise[i];
   }
   cov_status[s] = (uint8_t)status;
 }
 
 // k_traj_cov, slot s.  tabs: the CamTab of every camera (LDS or global); cam_np[c]: 6 or 9, 0 for a camera that takes no part;
 // cam_off[c]: its first row in cam_cov or -1; cam_cov null: the noise term alone (cam_off is not read, cov_calib gets NaN).
-// valid and xyz are those of the call at this point: the refined (or the DLT) points, before the 3-D fill.
+// valid and xyz are those of the call at this point: the refined (or the DLT) points, before the 3-D fill.  meas_cov (the smoothed
+// call; null: the stores of the uncertain call and no others) takes the noise term alone, before the calibration term is added.
 CBA_HD void traj_cov_slot(int32_t n_cams, int64_t n_slots, int64_t s, const CamTab* tabs, const int32_t* cam_np, const int64_t* cam_off,
                           const double* cam_cov, int64_t ncp, double sigma_px, const uint8_t* cam_posed, const double* xy, const uint8_t* view_state,
-                          const uint8_t* valid, const double* xyz, double* cov, double* cov_calib, uint8_t* cov_status) {
+                          const uint8_t* valid, const double* xyz, double* cov, double* cov_calib, uint8_t* cov_status,
+                          double* meas_cov = nullptr) {
   const double nan = traj_nan();
   const double none[6] = {nan, nan, nan, nan, nan, nan};
   const bool live = valid[s] == 1;
@@ -155,7 +159,7 @@ CBA_HD void traj_cov_slot(int32_t n_cams, int64_t n_slots, int64_t s, const CamT
   }
   double L[6];
   if (!live || !front || !chol3(V, L)) {
-    traj_cov_store(s, none, none, live ? COV_NOT_COMPUTABLE : COV_NO_POINT, cov, cov_calib, cov_status);
+    traj_cov_store(s, none, none, none, live ? COV_NOT_COMPUTABLE : COV_NO_POINT, cov, cov_calib, cov_status, meas_cov);
     return;
   }
   // pass 2: sum over the pairs c' <= c of M_c S[c, c'] M_c'^T, with its transpose for c' < c
@@ -220,10 +224,10 @@ CBA_HD void traj_cov_slot(int32_t n_cams, int64_t n_slots, int64_t s, const CamT
     sum += total[i];
   }
   if (!refine_finite(sum)) {  // (a NaN row never goes out as "ok")
-    traj_cov_store(s, none, none, COV_NOT_COMPUTABLE, cov, cov_calib, cov_status);
+    traj_cov_store(s, none, none, none, COV_NOT_COMPUTABLE, cov, cov_calib, cov_status, meas_cov);
     return;
   }
-  traj_cov_store(s, total, cam_cov ? calib : none, COV_OK, cov, cov_calib, cov_status);
+  traj_cov_store(s, total, cam_cov ? calib : none, noise, COV_OK, cov, cov_calib, cov_status, meas_cov);
 }
 
 // after k_traj_fill3d: a cell the 3-D fill added has no covariance of its own (its row is NaN already: it had no point)

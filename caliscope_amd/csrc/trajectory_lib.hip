@@ -2,9 +2,11 @@
 // to filled, triangulated, filled and smoothed 3-D trajectories on one dense grid; and cba_reconstruct_trajectories_refined
 // (include/caliscope/trajectory_refine.h), the same call with the robust reprojection refinement of every point in between; and
 // cba_reconstruct_trajectories_uncertain (include/caliscope/trajectory_uncertainty.h), either of them with the 3-D covariance of
-// every sample.  What a thread does, and the checks, are trajectory_math.h, trajectory_refine_math.h and trajectory_cov_math.h
-// (shared with tests/native/trajectory_harness.cpp, trajectory_refine_harness.cpp and trajectory_cov_harness.cpp); this file holds
-// the kernels and the entry points.
+// every sample; and cba_reconstruct_trajectories_smoothed and cba_smooth_trajectories (include/caliscope/trajectory_smoother.h), the
+// covariance-weighted fixed-interval smoother behind the uncertain call and on its own.  What a thread does, and the checks, are
+// trajectory_math.h, trajectory_refine_math.h, trajectory_cov_math.h and trajectory_smooth_math.h (shared with
+// tests/native/trajectory_harness.cpp, trajectory_refine_harness.cpp, trajectory_cov_harness.cpp and trajectory_smooth_harness.cpp);
+// this file holds the kernels and the entry points.
 //
 //   k_traj_fill2d       one thread per uploaded row (sorted by camera, trajectory, frame): the row's cell of xy[c][s][2] / ft[c][s],
 //                       and the first min(hole, xy_gap) cells of the hole between it and the next row of its track.  Holes of
@@ -19,11 +21,15 @@
 //                       tables are staged in LDS up to TRAJ_COV_LDS_CAMS cameras (STAGE), read from global memory above.
 //                       No scratch in either form; as compiled for gfx950 the staged form takes 256 VGPRs and 4 AGPRs (one wave
 //                       per SIMD: the table rows it reads from LDS sit in VGPRs), the global form 249 VGPRs (two waves per SIMD:
-//                       its rows are scalar loads).
+//                       its rows are scalar loads).  NOISE (smoothed call only): the noise term also goes to a buffer of its own.
 //   k_traj_fill3d       one thread per slot, in place (see traj_fill3d_cell for why that is safe).
 //   k_traj_cov_filled   (uncertain call with xyz_gap only) one thread per slot: cov_status 2 for the cells the 3-D fill added.
 //   k_traj_filtfilt     one thread per (trajectory, coordinate); thread t reads xyz[f][t] and its scratch column scratch[e][t], so
 //                       a wave's loads and stores are contiguous.
+//   k_traj_smooth       (smoothed calls only) one thread per trajectory: the Kalman filter forward and the modified Bryson-Frazier
+//                       pass backward over the frames of its span, 6-state, everything in registers, what the backward pass needs
+//                       parked component-major in park[45][n_slots].  A serial recurrence like k_traj_filtfilt: latency, not
+//                       throughput; the loads of the next frame are issued before the arithmetic of the current one.
 //
 // Null stream throughout: the launches of a call run in the order they were issued.  Nothing is added with atomics.
 #include <hip/hip_runtime.h>
@@ -34,6 +40,7 @@
 #include "trajectory_math.h"
 #include "trajectory_refine_math.h"
 #include "trajectory_cov_math.h"
+#include "trajectory_smooth_math.h"
 #include "device_call.h"
 
 using namespace cba;
@@ -82,12 +89,12 @@ k_traj_refine(int32_t n_cams, int64_t n_slots, const uint8_t* __restrict__ cam_p
                    xyz, view_state, views, rms_px, max_px, iterations, status);
 }
 
-template <bool STAGE>
+template <bool STAGE, bool NOISE>
 __global__ void __launch_bounds__(TRAJ_BLOCK)
 k_traj_cov(int32_t n_cams, int64_t n_slots, const double* __restrict__ cam_tab, const int32_t* __restrict__ cam_np, const int64_t* __restrict__ cam_off,
            const double* __restrict__ cam_cov, int64_t ncp, double sigma_px, const uint8_t* __restrict__ cam_posed, const double* __restrict__ xy,
            const uint8_t* __restrict__ view_state, const uint8_t* __restrict__ valid, const double* __restrict__ xyz, double* __restrict__ cov,
-           double* __restrict__ cov_calib, uint8_t* __restrict__ cov_status) {
+           double* __restrict__ cov_calib, uint8_t* __restrict__ cov_status, double* __restrict__ meas_cov) {
   extern __shared__ __attribute__((aligned(16))) double s_tab[];
   const CamTab* tabs = (const CamTab*)cam_tab;
   if constexpr (STAGE) {
@@ -97,7 +104,8 @@ k_traj_cov(int32_t n_cams, int64_t n_slots, const double* __restrict__ cam_tab, 
   }
   const int64_t s = (int64_t)blockIdx.x * TRAJ_BLOCK + threadIdx.x;
   if (s >= n_slots) return;
-  traj_cov_slot(n_cams, n_slots, s, tabs, cam_np, cam_off, cam_cov, ncp, sigma_px, cam_posed, xy, view_state, valid, xyz, cov, cov_calib, cov_status);
+  traj_cov_slot(n_cams, n_slots, s, tabs, cam_np, cam_off, cam_cov, ncp, sigma_px, cam_posed, xy, view_state, valid, xyz, cov, cov_calib, cov_status,
+                NOISE ? meas_cov : nullptr);
 }
 
 __global__ void __launch_bounds__(TRAJ_BLOCK)
@@ -122,24 +130,92 @@ k_traj_filtfilt(int64_t n_frames, int64_t n_traj, int order, const double* __res
   traj_filtfilt_thread(n_frames, n_traj, t, order, b, a, zi, valid, xyz, scratch);
 }
 
+__global__ void __launch_bounds__(TRAJ_BLOCK)
+k_traj_smooth(int64_t n_frames, int64_t n_traj, const double* __restrict__ xyz, const double* __restrict__ meas_cov, const uint8_t* __restrict__ measured,
+              SmoothModel model, double* __restrict__ park, double* __restrict__ pos, double* __restrict__ vel, double* __restrict__ pos_cov,
+              double* __restrict__ vel_cov, double* __restrict__ nis, uint8_t* status) {
+  const int64_t j = (int64_t)blockIdx.x * TRAJ_BLOCK + threadIdx.x;
+  if (j >= n_traj) return;
+  traj_smooth_thread(n_frames, n_traj, j, xyz, meas_cov, measured, model, park, pos, vel, pos_cov, vel_cov, nis, status);
+}
+
 unsigned blocks(int64_t n) { return (unsigned)((n + TRAJ_BLOCK - 1) / TRAJ_BLOCK); }
 
 // The checks of a call and its memory check against `memory` (<= 0: not checked)
-int validate(const cba_traj_desc* d, bool refined, const cba_traj_refine* r, const cba_traj_uncertainty* u, const cba_traj_cov_out* co, double memory,
-             std::string& msg) {
+int validate(const cba_traj_desc* d, bool refined, const cba_traj_refine* r, const cba_traj_uncertainty* u, const cba_traj_cov_out* co,
+             const cba_traj_smoother* sm, const cba_traj_smooth_out* so, double memory, std::string& msg) {
+  if (sm) return traj_smoothed_validate(d, refined ? r : nullptr, u, co, sm, so, memory, msg);
   if (u) return traj_uncertain_validate(d, refined ? r : nullptr, u, co, memory, msg);
   return refined ? traj_refined_validate(d, r, memory, msg) : traj_validate(d, memory, msg);
 }
 
-// The three entry points.  refined: r and q belong to the call (r is checked, not assumed); otherwise nothing of the refinement is
+// The device buffers of the smoother's results, NaN / status 0 until k_traj_smooth writes a row, and its scratch.
+struct SmoothBuffers {
+  double *pos = nullptr, *vel = nullptr, *pos_cov = nullptr, *vel_cov = nullptr, *nis = nullptr, *park = nullptr;
+  uint8_t* status = nullptr;
+
+  void make(Buffers& buf, int64_t n_slots) {
+    pos = buf.make<double>(n_slots, 3);
+    vel = buf.make<double>(n_slots, 3);
+    pos_cov = buf.make<double>(n_slots, 6);
+    vel_cov = buf.make<double>(n_slots, 6);
+    nis = buf.make<double>(n_slots);
+    status = buf.make<uint8_t>(n_slots);
+    park = buf.make<double>(SMOOTH_PARK, n_slots);
+  }
+  // (all bits set is a NaN)
+  void clear(Buffers& buf, int64_t n_slots) {
+    const size_t n = (size_t)n_slots;
+    buf.check(hipMemsetAsync(pos, 0xff, n * 3 * sizeof(double), 0));
+    if (!buf.status()) buf.check(hipMemsetAsync(vel, 0xff, n * 3 * sizeof(double), 0));
+    if (!buf.status()) buf.check(hipMemsetAsync(pos_cov, 0xff, n * 6 * sizeof(double), 0));
+    if (!buf.status()) buf.check(hipMemsetAsync(vel_cov, 0xff, n * 6 * sizeof(double), 0));
+    if (!buf.status()) buf.check(hipMemsetAsync(nis, 0xff, n * sizeof(double), 0));
+    if (!buf.status()) buf.check(hipMemsetAsync(status, 0, n, 0));
+  }
+  void launch(int64_t n_frames, int64_t n_traj, const double* xyz, const double* meas_cov, const uint8_t* measured, const SmoothModel& model) {
+    hipLaunchKernelGGL(k_traj_smooth, dim3(blocks(n_traj)), dim3(TRAJ_BLOCK), 0, 0, n_frames, n_traj, xyz, meas_cov, measured, model, park, pos, vel,
+                       pos_cov, vel_cov, nis, status);
+  }
+  void out(Buffers& buf, int64_t n_slots, cba_traj_smooth_out* o) const {
+    buf.out(o->pos, pos, n_slots, 3);
+    buf.out(o->vel, vel, n_slots, 3);
+    buf.out(o->pos_cov, pos_cov, n_slots, 6);
+    buf.out(o->vel_cov, vel_cov, n_slots, 6);
+    buf.out(o->nis, nis, n_slots);
+    buf.out(o->status, status, n_slots);
+  }
+};
+
+// what a call without a launch returns; meas_cov too where the call has one
+void smooth_nothing(int64_t n_slots, cba_traj_smooth_out* o, bool with_meas_cov) {
+  const double nan = traj_nan();
+  for (int64_t s = 0; s < n_slots; ++s) {
+    for (int i = 0; i < 3; ++i) {
+      if (o->pos) o->pos[3 * s + i] = nan;
+      if (o->vel) o->vel[3 * s + i] = nan;
+    }
+    for (int i = 0; i < 6; ++i) {
+      if (o->pos_cov) o->pos_cov[6 * s + i] = nan;
+      if (o->vel_cov) o->vel_cov[6 * s + i] = nan;
+      if (with_meas_cov && o->meas_cov) o->meas_cov[6 * s + i] = nan;
+    }
+    if (o->nis) o->nis[s] = nan;
+    if (o->status) o->status[s] = SMOOTH_NONE;
+  }
+}
+
+// The entry points of the reconstruction.  refined: r and q belong to the call (r is checked, not assumed); otherwise nothing of the refinement is
 // checked, allocated or launched.  u and co: the uncertain call; null, nothing of the covariance is checked, allocated or launched.
+// sm and so: the smoothed call (with u and co); null, nothing of the smoother is checked, allocated or launched.
 int reconstruct(const char* what, const cba_traj_desc* d, bool refined, const cba_traj_refine* r, int32_t device, cba_traj_out* out,
-                cba_traj_quality* q, const cba_traj_uncertainty* u = nullptr, cba_traj_cov_out* co = nullptr) {
+                cba_traj_quality* q, const cba_traj_uncertainty* u = nullptr, cba_traj_cov_out* co = nullptr, const cba_traj_smoother* sm = nullptr,
+                cba_traj_smooth_out* so = nullptr) {
   if (!d || !out || (refined && !q)) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
   // everything that does not need the device first: the sizes, the filter, every index the kernels use
   std::string msg;
   // (memory_limit 0: the free memory is asked for below)
-  int rc = validate(d, refined, r, u, co, (double)d->memory_limit, msg);
+  int rc = validate(d, refined, r, u, co, sm, so, (double)d->memory_limit, msg);
   if (rc) return err(rc, msg);
   const int32_t n_cams = d->n_cams;
   const int64_t n_frames = d->n_frames, n_traj = d->n_traj, n_rows = d->n_rows, n_slots = n_frames * n_traj;
@@ -171,6 +247,7 @@ int reconstruct(const char* what, const cba_traj_desc* d, bool refined, const cb
       }
       if (co->cov_status) co->cov_status[s] = COV_NO_POINT;
     }
+    if (sm) smooth_nothing(n_slots, so, true);
     return CBA_OK;
   }
   rc = select_device(device, what);
@@ -181,8 +258,9 @@ int reconstruct(const char* what, const cba_traj_desc* d, bool refined, const cb
     if (hipMemGetInfo(&free_bytes, &total_bytes) != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": hipMemGetInfo failed");
     memory = (double)free_bytes;
   }
-  if (traj_device_bytes(d) + (refined ? traj_refine_device_bytes(d) : 0.0) + (u ? traj_cov_device_bytes(d, u, co) : 0.0) > memory) {
-    rc = validate(d, refined, r, u, co, memory, msg);  // (puts the message together)
+  if (traj_device_bytes(d) + (refined ? traj_refine_device_bytes(d) : 0.0) + (u ? traj_cov_device_bytes(d, u, co) : 0.0) +
+          (sm ? traj_smooth_device_bytes((double)n_frames, (double)n_traj, false) : 0.0) > memory) {
+    rc = validate(d, refined, r, u, co, sm, so, memory, msg);  // (puts the message together)
     return err(rc ? rc : CBA_ERR_UNSUPPORTED, msg);
   }
   if (n_slots > (int64_t)0x7fffffff * TRAJ_BLOCK || n_rows > (int64_t)0x7fffffff * TRAJ_BLOCK)
@@ -228,6 +306,10 @@ int reconstruct(const char* what, const cba_traj_desc* d, bool refined, const cb
   double* dcov = u ? buf.make<double>(n_slots, 6) : nullptr;
   double* dcalib = u && co->cov_calib ? buf.make<double>(n_slots, 6) : nullptr;
   uint8_t* dcstat = u ? buf.make<uint8_t>(n_slots) : nullptr;
+  // without the smoother its eight buffers stay null
+  double* dmeas = sm ? buf.make<double>(n_slots, 6) : nullptr;
+  SmoothBuffers smooth;
+  if (sm) smooth.make(buf, n_slots);
   if (buf.status()) return buf.result(what);
 
   // all bits set is a NaN: "no row here"
@@ -245,12 +327,15 @@ int reconstruct(const char* what, const cba_traj_desc* d, bool refined, const cb
                        diter, dstatus);
   if (u) {  // (writes every cell of its buffers)
     const int64_t camcov_rows = u->cam_cov ? u->ncp : 0;
-    if (n_cams <= TRAJ_COV_LDS_CAMS)
-      hipLaunchKernelGGL(k_traj_cov<true>, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), (size_t)n_cams * sizeof(CamTab), 0, n_cams, n_slots, dtab, dnp, doff,
-                         dcamcov, camcov_rows, u->sigma_px, dposed, dxy, dstate, dvalid, dxyz, dcov, dcalib, dcstat);
-    else
-      hipLaunchKernelGGL(k_traj_cov<false>, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), 0, 0, n_cams, n_slots, dtab, dnp, doff, dcamcov, camcov_rows,
-                         u->sigma_px, dposed, dxy, dstate, dvalid, dxyz, dcov, dcalib, dcstat);
+    const bool stage = n_cams <= TRAJ_COV_LDS_CAMS;
+    const auto kernel = stage ? (sm ? k_traj_cov<true, true> : k_traj_cov<true, false>) : (sm ? k_traj_cov<false, true> : k_traj_cov<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), stage ? (size_t)n_cams * sizeof(CamTab) : 0, 0, n_cams, n_slots, dtab, dnp, doff,
+                       dcamcov, camcov_rows, u->sigma_px, dposed, dxy, dstate, dvalid, dxyz, dcov, dcalib, dcstat, dmeas);
+  }
+  if (sm) {  // (xyz_gap and the filter are refused with it: xyz and cov_status are those k_traj_cov saw and wrote)
+    smooth.clear(buf, n_slots);
+    if (buf.status()) return buf.result(what);
+    smooth.launch(n_frames, n_traj, dxyz, dmeas, dcstat, smooth_model(sm->fps, sm->accel_density, sm->velocity_prior_std, sm->max_gap));
   }
   if (d->xyz_gap > 0)
     hipLaunchKernelGGL(k_traj_fill3d, dim3(blocks(n_slots)), dim3(TRAJ_BLOCK), 0, 0, n_frames, n_traj, n_slots, (int)d->xyz_gap, dvalid, dxyz, dtime);
@@ -279,6 +364,10 @@ int reconstruct(const char* what, const cba_traj_desc* d, bool refined, const cb
     buf.out(co->cov_calib, dcalib, n_slots, 6);
     buf.out(co->cov_status, dcstat, n_slots);
   }
+  if (sm) {
+    smooth.out(buf, n_slots, so);
+    buf.out(so->meas_cov, dmeas, n_slots, 6);
+  }
   if (!buf.status()) buf.check(hipDeviceSynchronize());
   return buf.result(what);
 }
@@ -300,4 +389,51 @@ extern "C" int cba_reconstruct_trajectories_uncertain(const cba_traj_desc* d, co
   if (!uncertainty || !cov_out) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
   if ((refine == nullptr) != (quality == nullptr)) return err(CBA_ERR_INVALID, std::string(what) + ": quality goes with refine, and with it alone");
   return reconstruct(what, d, refine != nullptr, refine, device, out, quality, uncertainty, cov_out);
+}
+
+extern "C" int cba_reconstruct_trajectories_smoothed(const cba_traj_desc* d, const cba_traj_refine* refine, const cba_traj_uncertainty* uncertainty,
+                                                     const cba_traj_smoother* smoother, int32_t device, cba_traj_out* out, cba_traj_quality* quality,
+                                                     cba_traj_cov_out* cov_out, cba_traj_smooth_out* smooth_out) {
+  const char* what = "cba_reconstruct_trajectories_smoothed";
+  if (!uncertainty || !cov_out) return err(CBA_ERR_INVALID, std::string(what) + ": uncertainty: null argument (the smoother weights a sample by its covariance)");
+  if (!smoother || !smooth_out) return err(CBA_ERR_INVALID, std::string(what) + ": smoother: null argument");
+  if ((refine == nullptr) != (quality == nullptr)) return err(CBA_ERR_INVALID, std::string(what) + ": quality goes with refine, and with it alone");
+  return reconstruct(what, d, refine != nullptr, refine, device, out, quality, uncertainty, cov_out, smoother, smooth_out);
+}
+
+extern "C" int cba_smooth_trajectories(const cba_smooth_desc* d, int32_t device, cba_traj_smooth_out* out) {
+  const char* what = "cba_smooth_trajectories";
+  if (!d || !out) return err(CBA_ERR_INVALID, std::string(what) + ": null argument");
+  std::string msg;
+  bool any = false;
+  int rc = traj_smooth_validate(d, (double)d->memory_limit, msg, &any);
+  if (rc) return err(rc, msg);
+  const int64_t n_frames = d->n_frames, n_traj = d->n_traj, n_slots = n_frames * n_traj;
+  if (!any) {
+    smooth_nothing(n_slots, out, false);
+    return CBA_OK;
+  }
+  rc = select_device(device, what);
+  if (rc) return rc;
+  if (d->memory_limit <= 0) {
+    size_t free_bytes = 0, total_bytes = 0;
+    if (hipMemGetInfo(&free_bytes, &total_bytes) != hipSuccess) return err(CBA_ERR_HIP, std::string(what) + ": hipMemGetInfo failed");
+    rc = traj_smooth_validate(d, (double)free_bytes, msg, &any);
+    if (rc) return err(rc, msg);
+  }
+  if (n_traj > (int64_t)0x7fffffff * TRAJ_BLOCK) return err(CBA_ERR_UNSUPPORTED, std::string(what) + ": more workgroups than one launch takes");
+  Buffers buf;
+  const double* dxyz = buf.in(d->xyz, n_slots, 3);
+  const double* dmeas = buf.in(d->meas_cov, n_slots, 6);
+  const uint8_t* dflag = buf.in(d->measured, n_slots);
+  SmoothBuffers smooth;
+  smooth.make(buf, n_slots);
+  if (buf.status()) return buf.result(what);
+  smooth.clear(buf, n_slots);
+  if (buf.status()) return buf.result(what);
+  smooth.launch(n_frames, n_traj, dxyz, dmeas, dflag, smooth_model(d->fps, d->accel_density, d->velocity_prior_std, d->max_gap));
+  buf.check(hipGetLastError());
+  smooth.out(buf, n_slots, out);
+  if (!buf.status()) buf.check(hipDeviceSynchronize());
+  return buf.result(what);
 }

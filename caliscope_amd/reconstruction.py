@@ -18,7 +18,9 @@ samples raises ``ValueError`` before anything is launched (scipy raises there in
 ``refine=RefineOptions(...)`` makes ``cba_reconstruct_trajectories_refined`` instead (``caliscope_amd/trajectory_refinement.py``): the
 same launches with the robust reprojection refinement of every point, and the rejection of contradicting views, between the
 triangulation and the 3-D fill.  ``covariance=CovarianceOptions(...)`` makes ``cba_reconstruct_trajectories_uncertain``
-(``caliscope_amd/trajectory_uncertainty.py``): either of the two with the 3-D covariance of every sample.
+(``caliscope_amd/trajectory_uncertainty.py``): either of the two with the 3-D covariance of every sample.  With it,
+``smoother=SmootherOptions(...)`` makes ``cba_reconstruct_trajectories_smoothed`` (``caliscope_amd/trajectory_smoother.py``): the
+covariance-weighted fixed-interval smoother behind the covariance, with positions, velocities and their covariances per frame.
 
 There is no CPU fallback: without the library or a GPU the call raises ``BackendError``.  ``_solver`` replaces the device call (an
 object with ``reconstruct``, as :class:`DeviceTrajectorySolver`, and for ``refine`` with ``reconstruct_refined``, as
@@ -217,7 +219,7 @@ def world_points_of(grid: TrajectoryGrid, result: TrajectoryResult) -> WorldPoin
 
 
 def reconstruct_trajectories(image_points: ImagePoints, camera_array, *, xy_gap_fill: int = 3, xyz_gap_fill: int = 0, smooth=None,
-                             float32_io: bool = True, device_id: int = 0, refine=None, return_quality: bool = False, covariance=None, _solver=None):
+                             float32_io: bool = True, device_id: int = 0, refine=None, return_quality: bool = False, covariance=None, smoother=None, _solver=None):
     """``image_points.fill_gaps(xy_gap_fill).triangulate(camera_array)``, then ``.fill_gaps(xyz_gap_fill)`` and, for
     ``smooth = (fps, cutoff_freq, order)``, ``.smooth(*smooth)`` — in one device call.  A gap of 0 skips that fill, ``smooth=None``
     the filter.  An empty table, or one without a posed camera, gives an empty table with the ``frame_time`` column.
@@ -233,13 +235,26 @@ def reconstruct_trajectories(image_points: ImagePoints, camera_array, *, xy_gap_
     the camera parameters; ``camera_array`` has to be the one that report was computed at.  The result then ends with a DataFrame row
     for row beside the table (after the quality frame when ``return_quality`` is set): the keys, ``cov_xx .. cov_zz``,
     ``std_x, std_y, std_z``, ``std_major``, ``calib_share`` and ``cov_status``.  The covariance is that of the sample before the 3-D
-    fill and the filter (cells the fill adds: NaN, status 2).  ``_solver`` then needs ``reconstruct_uncertain``."""
+    fill and the filter (cells the fill adds: NaN, status 2).  ``_solver`` then needs ``reconstruct_uncertain``.
+
+    ``smoother`` (a :class:`caliscope_amd.trajectory_smoother.SmootherOptions`) needs ``covariance`` and does the jobs of
+    ``xyz_gap_fill`` and ``smooth`` itself, so it refuses both (``ValueError``).  The table and the frames before it are those of the
+    call without it; the result then ends with one more DataFrame, ``smoothed_frame``'s: a row per measured sample and per frame
+    of a hole of at most ``max_gap`` frames, with the smoothed position, the velocity, their covariances (the pixel-noise part; the
+    sample's calibration term is passed through beside it) and ``nis``.  ``_solver`` then needs ``reconstruct_smoothed``."""
     if return_quality and refine is None:
         raise ValueError("reconstruct_trajectories: return_quality needs refine (the plain call computes no quality)")
+    if smoother is not None:
+        if covariance is None:
+            raise ValueError("reconstruct_trajectories: smoother needs covariance (it weights every sample by its own covariance)")
+        if int(xyz_gap_fill) != 0:
+            raise ValueError(f"reconstruct_trajectories: smoother with xyz_gap_fill = {xyz_gap_fill}: the smoother fills the holes itself (max_gap)")
+        if smooth is not None:
+            raise ValueError("reconstruct_trajectories: smoother with smooth: one call smooths once, by the filter or by the smoother")
     filt = filter_coefficients(smooth) if smooth is not None else None
     if covariance is not None:
         return _reconstruct_uncertain(image_points, camera_array, int(xy_gap_fill), int(xyz_gap_fill), filt, float32_io, device_id, refine,
-                                      return_quality, covariance, _solver)
+                                      return_quality, covariance, smoother, _solver)
     if refine is None:
         if len(image_points) == 0:
             return _empty()
@@ -262,33 +277,48 @@ def reconstruct_trajectories(image_points: ImagePoints, camera_array, *, xy_gap_
     return (world, quality) if return_quality else world
 
 
-def _reconstruct_uncertain(image_points, camera_array, xy_gap, xyz_gap, filt, float32_io, device_id, refine, return_quality, covariance, _solver):
-    """``reconstruct_trajectories`` with ``covariance``: ``(world[, quality], covariance frame)``."""
+def _reconstruct_uncertain(image_points, camera_array, xy_gap, xyz_gap, filt, float32_io, device_id, refine, return_quality, covariance, smoother,
+                           _solver):
+    """``reconstruct_trajectories`` with ``covariance``: ``(world[, quality], covariance frame[, smoothed frame])``."""
     from caliscope_amd import trajectory_refinement as TR
+    from caliscope_amd import trajectory_smoother as TS
     from caliscope_amd import trajectory_uncertainty as TU
 
     if refine is not None:
         TR.refine_struct(refine)
+    if smoother is not None:
+        TS._fields(smoother)
     grid = trajectory_grid(image_points, camera_array) if len(image_points) else None
+    smoothed = pd.DataFrame(columns=list(TS.SMOOTHED_COLUMNS))
     if grid is None or not grid.cam_posed.any():
         world, quality, frame = _empty(), pd.DataFrame(columns=list(TR.QUALITY_COLUMNS)), pd.DataFrame(columns=list(TU.COVARIANCE_COLUMNS))
+    elif smoother is not None:
+        solver = _solver if _solver is not None else TS.DeviceTrajectorySmoother(device_id)
+        result, q, cov, sm = solver.reconstruct_smoothed(grid, covariance, smoother, refine, camera_array=camera_array, xy_gap=xy_gap, xyz_gap=xyz_gap,
+                                                         filt=filt, float32_io=float32_io)
+        world, frame, smoothed = world_points_of(grid, result), TU.covariance_frame(grid, result, cov), TS.smoothed_frame(grid, sm, cov.cov_calib)
+        quality = TR.quality_frame(grid, result, q) if refine is not None else None
     else:
         solver = _solver if _solver is not None else TU.DeviceUncertainTrajectorySolver(device_id)
         result, q, cov = solver.reconstruct_uncertain(grid, covariance, refine, camera_array=camera_array, xy_gap=xy_gap, xyz_gap=xyz_gap, filt=filt,
                                                       float32_io=float32_io)
         world, frame = world_points_of(grid, result), TU.covariance_frame(grid, result, cov)
         quality = TR.quality_frame(grid, result, q) if refine is not None else None
-    return (world, quality, frame) if return_quality else (world, frame)
+    head = (world, quality, frame) if return_quality else (world, frame)
+    return head + (smoothed,) if smoother is not None else head
 
 
 def reconstruct_xyz(image_points: ImagePoints, camera_array, name: str, output_dir, xy_gap_fill: int = 3, **kw):
     """The reference's ``reconstruct_xyz`` use case: the trajectories of a recording written to ``output_dir / xyz_{name}.csv``
     (``WorldPoints.to_csv``).  Returns the path, or None when there are no 2-D points or nothing triangulates (no file then).
-    With ``covariance=CovarianceOptions(...)`` the covariance frame goes to ``xyz_{name}_covariance.csv`` beside it."""
+    With ``covariance=CovarianceOptions(...)`` the covariance frame goes to ``xyz_{name}_covariance.csv`` beside it, and with
+    ``smoother=SmootherOptions(...)`` the smoothed frame to ``xyz_{name}_smoothed.csv``."""
     if len(image_points) == 0:
         return None
     world = reconstruct_trajectories(image_points, camera_array, xy_gap_fill=xy_gap_fill, **kw)
-    frame = None
+    frame, smoothed = None, None
+    if kw.get("smoother") is not None:
+        world, smoothed = world[:-1], world[-1]
     if kw.get("covariance") is not None:
         world, frame = world[0], world[-1]
     if len(world) == 0:
@@ -297,6 +327,8 @@ def reconstruct_xyz(image_points: ImagePoints, camera_array, name: str, output_d
     world.to_csv(path)
     if frame is not None:
         frame.to_csv(Path(output_dir) / f"xyz_{name}_covariance.csv", index=False)
+    if smoothed is not None:
+        smoothed.to_csv(Path(output_dir) / f"xyz_{name}_smoothed.csv", index=False)
     return path
 
 
