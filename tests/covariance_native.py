@@ -250,13 +250,14 @@ def _reference(key, loss, f_scale):
 
 
 _SCENES = {}
+SCENE_BUILDERS = {"small": scene, "wide": wide_scene, "ragged": ragged_scene}  # (tests/covariance_edge_scenes.py adds its own)
 
 
 def key_scene(key):
     """Scenes by hashable key, built once and never written to: ("small", n_cams, n_points, k, refine, loss, outliers),
-    ("wide", widths, fisheye_six), ("ragged",)."""
+    ("wide", widths, fisheye_six[, n_points]), ("ragged",), and the keys of the builders other modules put into SCENE_BUILDERS."""
     if key not in _SCENES:
-        _SCENES[key] = scene(*key[1:]) if key[0] == "small" else wide_scene(*key[1:]) if key[0] == "wide" else ragged_scene()
+        _SCENES[key] = SCENE_BUILDERS[key[0]](*key[1:])
     return _SCENES[key]
 
 
