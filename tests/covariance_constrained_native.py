@@ -198,12 +198,14 @@ def free_intrinsics():
 
 
 _SCENES = {}
+SCENE_BUILDERS = {"board": board, "mixed": mixed, "free intrinsics": free_intrinsics}  # (tests/covariance_constrained_edge_scenes.py adds its own)
 
 
 def key_scene(key):
-    """Scenes by hashable key, built once and never written to: ("board", n_cams, n_frames, rows, cols, sigma_m), ("mixed",) or ("free intrinsics",)."""
+    """Scenes by hashable key, built once and never written to: ("board", n_cams, n_frames, rows, cols, sigma_m), ("mixed",), ("free intrinsics",),
+    and the keys of the builders other modules put into SCENE_BUILDERS."""
     if key not in _SCENES:
-        _SCENES[key] = mixed() if key[0] == "mixed" else free_intrinsics() if key[0] == "free intrinsics" else board(*key[1:])
+        _SCENES[key] = SCENE_BUILDERS[key[0]](*key[1:])
     return _SCENES[key]
 
 
