@@ -221,7 +221,7 @@ CBA_HD void project_full(const CamTab& c, double X, double Y, double Z, double u
 // is exactly 1.0 there): the same arithmetic for G, Yr, Aint and B in the same order, no u, v, e, and c.cx / c.cy are not read.
 template <bool RES>
 CBA_HD void project_factors_impl(const CamTab& c, double X, double Y, double Z, double u, double v,
-                                 double* e, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3]) {
+                                 double* e, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3], double* nrm = nullptr) {
   const double Y0 = c.R[0] * X + c.R[1] * Y + c.R[2] * Z;
   const double Y1 = c.R[3] * X + c.R[4] * Y + c.R[5] * Z;
   const double Y2 = c.R[6] * X + c.R[7] * Y + c.R[8] * Z;
@@ -229,6 +229,7 @@ CBA_HD void project_factors_impl(const CamTab& c, double X, double Y, double Z, 
   const double Zc = Y2 + c.t[2];
   const double iz = 1.0 / Zc;
   const double x = (Y0 + c.t[0]) * iz, y = (Y1 + c.t[1]) * iz;
+  if (nrm) { nrm[0] = x; nrm[1] = y; nrm[2] = iz; }  // the normalised point and the reciprocal depth: what a six-parameter record is packed from (rec6_pack)
   Lens L;
   if (c.model != 0.0) lens_fisheye(c.d, x, y, &L); else lens_pinhole(c.d, x, y, &L);
   const double s = c.inv_fx0;
@@ -252,12 +253,52 @@ CBA_HD void project_factors_impl(const CamTab& c, double X, double Y, double Z, 
   Aint[0][2] = free_intr ? fxs * L.xr4 : 0.0;      Aint[1][2] = free_intr ? fys * L.yr4 : 0.0;
 }
 CBA_HD void project_factors(const CamTab& c, double X, double Y, double Z, double u, double v,
-                            double* e, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3]) {
-  project_factors_impl<true>(c, X, Y, Z, u, v, e, G, Yr, Aint, B);
+                            double* e, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3], double* nrm = nullptr) {
+  project_factors_impl<true>(c, X, Y, Z, u, v, e, G, Yr, Aint, B, nrm);
 }
 // the factors alone (no residual)
-CBA_HD void project_factors(const CamTab& c, double X, double Y, double Z, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3]) {
-  project_factors_impl<false>(c, X, Y, Z, 0.0, 0.0, nullptr, G, Yr, Aint, B);
+CBA_HD void project_factors(const CamTab& c, double X, double Y, double Z, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3],
+                            double* nrm = nullptr) {
+  project_factors_impl<false>(c, X, Y, Z, 0.0, 0.0, nullptr, G, Yr, Aint, B, nrm);
+}
+
+// Compact Schur record of a six-parameter camera (cba_kernels.h, SchurRec<6>).  G = K2 (1/Zc) [[1, 0, -x], [0, 1, -y]], so the third row of
+// Q = G^T Z is -(x Q_row0 + y Q_row1) with the normalised point x = (Y0 + t0) / Zc, y = (Y1 + t1) / Zc.  The record is
+// (Y0, Y1, Y2, 1/Zc, Q_row0, Q_row1): ten doubles.  Y = R X is kept as it is (a record that carried Yc = Y + t and had the translation taken off the
+// sums per camera lost |Yc| / |Y| — squared in the rotation blocks — of their precision to cancellation); a reader rebuilds x and y from Y, 1/Zc
+// and its camera's t with project_factors' own expression, so they come out bit for bit as the G of the record saw them.
+constexpr int REC6_VALUES = 10;
+// x, y and 1/Zc from the rotated point and the translation (project_factors' own expressions: the same bits as its nrm)
+CBA_HD void rec6_head(const double* Yr, const double* t, double* nrm) {
+  const double Zc = Yr[2] + t[2];
+  const double iz = 1.0 / Zc;
+  nrm[0] = (Yr[0] + t[0]) * iz; nrm[1] = (Yr[1] + t[1]) * iz; nrm[2] = iz;
+}
+// the record: Y, 1/Zc, rows 0 and 1 of Q = G^T Z (Z = B L^-T, 2 x 3)
+CBA_HD void rec6_pack(const double (*G)[3], const double* Yr, const double (*Z)[3], double iz, double* rec) {
+  rec[0] = Yr[0]; rec[1] = Yr[1]; rec[2] = Yr[2]; rec[3] = iz;
+  for (int r = 0; r < 2; ++r)
+    for (int k = 0; k < 3; ++k) rec[4 + 3 * r + k] = G[0][r] * Z[0][k] + G[1][r] * Z[1][k];
+}
+CBA_HD void rec6_pack(const double (*G)[3], const double* Yr, const double* t, const double (*Z)[3], double* rec) {
+  double nrm[3];
+  rec6_head(Yr, t, nrm);
+  rec6_pack(G, Yr, Z, nrm[2], rec);
+}
+// the normalised point of a record, given its camera's translation (only t[0], t[1] are read)
+CBA_HD void rec6_xy(const double* rec, const double* t, double* x, double* y) {
+  *x = (rec[0] + t[0]) * rec[3];
+  *y = (rec[1] + t[1]) * rec[3];
+}
+// the twelve values of the full record, Y = R X (3) and Q (3 x 3, row-major), given the camera's translation
+CBA_HD void rec6_expand(const double* rec, const double* t, double* full) {
+  double x, y;
+  rec6_xy(rec, t, &x, &y);
+  full[0] = rec[0]; full[1] = rec[1]; full[2] = rec[2];
+  for (int k = 0; k < 3; ++k) {
+    full[3 + k] = rec[4 + k]; full[6 + k] = rec[7 + k];
+    full[9 + k] = -(x * rec[4 + k] + y * rec[7 + k]);
+  }
 }
 
 // scipy's robust-loss treatment of ONE scalar residual r (least_squares.py:169-237, common.py:720-731).

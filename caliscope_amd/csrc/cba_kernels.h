@@ -397,7 +397,7 @@ __device__ __forceinline__ double obs_linearize(const CamTab& c_lds, double X, d
 // rows; the camera row is copied from LDS WITHOUT its J_l (27 of 36 doubles: the table reads of the per-observation kernels are random gathers into the
 // LDS banks, ~2.5 cycles per access group, and were 19 of k_jv's and 38 of k_tprep's microseconds of LDS time on cfg4 — r05 SQ counters).
 __device__ __forceinline__ double obs_factors(const CamTab& c_lds, double X, double Y, double Z, double u, double v, int loss, double f_scale, double* e,
-                                              double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3]) {
+                                              double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3], double* nrm = nullptr) {
   CamTab c;
   {
     const double* src = reinterpret_cast<const double*>(&c_lds);
@@ -408,7 +408,11 @@ __device__ __forceinline__ double obs_factors(const CamTab& c_lds, double X, dou
     for (int i = 21; i < 35; ++i) dst[i] = src[i];         // fx .. nparams (J_l, entries 12..20, is not read)
   }
   __builtin_amdgcn_sched_barrier(0);
-  project_factors(c, X, Y, Z, u, v, e, G, Yr, Aint, B);
+  project_factors(c, X, Y, Z, u, v, e, G, Yr, Aint, B, nrm);
+  if (nrm) {  // (nrm: the head of a compact record, ba_math.h rec6_pack; fenced as in the linear form below)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) asm("" : "+v"(nrm[k]));
+  }
   double rho = 0.0;
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
@@ -424,7 +428,8 @@ __device__ __forceinline__ double obs_factors(const CamTab& c_lds, double X, dou
 }
 // The factors alone, for a LINEAR loss (k_tprep<.., LIN>, k_jv<.., LIN>): the row scale is exactly 1.0 there and the second linearisations use nothing
 // else of the residual, so no pixel is loaded, cx and cy stay in the table (25 of 36 doubles) and G, Yr, Aint, B come out bit for bit as above.
-__device__ __forceinline__ void obs_factors(const CamTab& c_lds, double X, double Y, double Z, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3]) {
+__device__ __forceinline__ void obs_factors(const CamTab& c_lds, double X, double Y, double Z, double (*G)[3], double* Yr, double (*Aint)[3], double (*B)[3],
+                                            double* nrm = nullptr) {
   CamTab c;
   {
     const double* src = reinterpret_cast<const double*>(&c_lds);
@@ -436,7 +441,7 @@ __device__ __forceinline__ void obs_factors(const CamTab& c_lds, double X, doubl
     for (int i = 25; i < 35; ++i) dst[i] = src[i];         // d .. nparams
   }
   __builtin_amdgcn_sched_barrier(0);
-  project_factors(c, X, Y, Z, G, Yr, Aint, B);
+  project_factors(c, X, Y, Z, G, Yr, Aint, B, nrm);
   // The generic form's robust-loss branches end the basic block here.  Without them the compiler contracts and re-associates ACROSS this point (the
   // sums B and Yr end in are folded into the multiply-adds of chol3_fwd and of the right-hand side: other roundings, other bits in the records): the
   // factors pass through an empty asm, which costs no instruction and which the compiler cannot see through.
@@ -447,6 +452,10 @@ __device__ __forceinline__ void obs_factors(const CamTab& c_lds, double X, doubl
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) asm("" : "+v"(Yr[k]));
+  if (nrm) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) asm("" : "+v"(nrm[k]));
+  }
 }
 
 template <int NC> struct UPack {
@@ -1178,27 +1187,37 @@ struct TilePlan {
 // are the four 3 x 3 quarters of the PRIMED block T'_i T'_j^T, T' = [[Y]x Q ; Q ; T_intr] (99 FP64 operations per pair
 // instead of 108 on 18 + 18 doubles).  The per-camera factor J_l^T is applied once per block in the pair kernel's epilogue.
 // The rhs needs the true rows 0..2, which k_tprep has in registers anyway.
+//
+// NC = 6: two of those twelve doubles are saved (ba_math.h, rec6_pack).  G = K2 (1/Zc) [[1, 0, -x], [0, 1, -y]], so Q's third row is
+// -(x Q_row0 + y Q_row1) with x = (Y0 + t0) / Zc, y = (Y1 + t1) / Zc.  The record is (Y, 1/Zc, Q_row0, Q_row1): 10 doubles = 80 B, five pieces in
+// HBM and in LDS; a reader rebuilds x and y from its camera's t (a constant of a pair-kernel thread; staged per camera by the back-substitution).
+// (First form, measured and dropped: (x, y, Zc, Q_row0, Q_row1) with the sums formed on Yc = Y + t and the translation taken off per camera —
+// two instructions per record cheaper, but the rotation blocks lost |Yc|^2 / |Y|^2 of their precision to the cancellation.)
 template <int NC> struct SchurRec {
-  static constexpr int NVAL = (NC == 9) ? 21 : 12;        // doubles that carry data
-  static constexpr int NPH = (NVAL + 1) / 2;              // 16-byte pieces that carry data: 6 / 11
-  static constexpr int LST = (NPH & 1) ? NPH : NPH + 1;   // record stride in LDS, 16-byte pieces, odd: 7 / 11 (bank spread)
-  static constexpr int REC = 2 * LST;                     // record stride in LDS, doubles: 14 / 22
-  // record stride in HBM, doubles: the pieces that carry data, 12 / 22 (96 / 176 bytes).  NC = 6: the seventh piece of the LDS stride is padding
-  // for the bank spread only; the pair kernel's load lanes that land on it fetch the sixth piece again.  (128-byte records, one line each, were
-  // measured: the pair kernel's issue phase shrank by 7 %, k_tprep grew by as much, and the pass moved 1.15 GB instead of 0.93 GB through HBM.)
+  static constexpr int NVAL = (NC == 9) ? 21 : 10;        // doubles that carry data
+  static constexpr int NPH = (NVAL + 1) / 2;              // 16-byte pieces that carry data: 5 / 11
+  static constexpr int LST = (NPH & 1) ? NPH : NPH + 1;   // record stride in LDS, 16-byte pieces, odd: 5 / 11 (bank spread)
+  static constexpr int REC = 2 * LST;                     // record stride in LDS, doubles: 10 / 22
+  // record stride in HBM, doubles: the pieces that carry data, 10 / 22 (80 / 176 bytes).  (128-byte records, one line each, were measured on the
+  // twelve-double form: the pair kernel's issue phase shrank by 7 %, k_tprep grew by as much, and the pass moved 1.15 GB instead of 0.93 GB through HBM.)
   static constexpr int HREC = 2 * NPH;
   static constexpr int STAGE = (HREC / 2) | 1;            // k_tprep's transposing LDS stage: record stride in pieces, odd (bank spread)
   // waves of a k_tprep workgroup that stage at the same time.  NC = 9: two, in two turns — with a stage for all four (45 KB) next to the camera
   // table the kernel had 92 KB of LDS and ran one workgroup per CU
   static constexpr int STAGE_WAVES = (NC == 9) ? 2 : 4;
 };
-static_assert(SchurRec<6>::REC == 14 && SchurRec<6>::LST == 7 && SchurRec<9>::REC == 22 && SchurRec<9>::LST == 11, "record sizes");
+static_assert(SchurRec<6>::REC == 10 && SchurRec<6>::LST == 5 && SchurRec<6>::HREC == 10 && SchurRec<6>::STAGE == 5 && SchurRec<9>::REC == 22 &&
+                  SchurRec<9>::LST == 11,
+              "record sizes");
 
-// true T (NC x 3, row-major) from a compact record and the camera's J_l (row-major): k_heavy_schur, k_con_schur
+// true T (NC x 3, row-major) from a compact record and the camera's table row (t and J_l, row-major): k_heavy_schur, k_con_schur
 template <int NC>
-__device__ __forceinline__ void expand_record(const double* __restrict__ rec, const double* __restrict__ Jl, double* __restrict__ T) {
-  const double Y0 = rec[0], Y1 = rec[1], Y2 = rec[2];
-  const double* Q = rec + 3;
+__device__ __forceinline__ void expand_record(const double* __restrict__ rec, const double* __restrict__ cam_row, double* __restrict__ T) {
+  const double* Jl = cam_row + 12;  // CamTab::Jl
+  double full[12];
+  if constexpr (NC == 6) rec6_expand(rec, cam_row + 9 /* CamTab::t */, full);
+  const double Y0 = (NC == 6) ? full[0] : rec[0], Y1 = (NC == 6) ? full[1] : rec[1], Y2 = (NC == 6) ? full[2] : rec[2];
+  const double* Q = (NC == 6) ? full + 3 : rec + 3;
 #pragma unroll
   for (int m = 0; m < 3; ++m) {
     const double q0 = Q[m], q1 = Q[3 + m], q2 = Q[6 + m];
@@ -1406,9 +1425,9 @@ k_tprep(const double* __restrict__ obs_u, const double* __restrict__ obs_v, cons
       const double X = ops.X, Yw = ops.Y, Zw = ops.Z;
       // factored linearisation (round 6): T = A^T Z = [J_l^T [Y]x Q ; Q ; T_intr] with Q = G^T Z — the record never held the top rows, and their share
       // of the right-hand side, J_l^T (Y x (Q y)), is accumulated WITHOUT its J_l^T (applied once per camera when the workgroup writes its row out)
-      double e[2], G[2][3], Yr[3], Aint[2][3], B[2][3], Z[2][3];
-      if constexpr (LIN) obs_factors(ct, X, Yw, Zw, G, Yr, Aint, B);
-      else obs_factors(ct, X, Yw, Zw, cur.u, cur.v, loss, f_scale, e, G, Yr, Aint, B);
+      double e[2], G[2][3], Yr[3], Aint[2][3], B[2][3], Z[2][3], nrm[3];
+      if constexpr (LIN) obs_factors(ct, X, Yw, Zw, G, Yr, Aint, B, NC == 6 ? nrm : nullptr);
+      else obs_factors(ct, X, Yw, Zw, cur.u, cur.v, loss, f_scale, e, G, Yr, Aint, B, NC == 6 ? nrm : nullptr);
       const int np = (int)ct.nparams;
       double Vd[6], L[6];
 #pragma unroll
@@ -1428,18 +1447,39 @@ k_tprep(const double* __restrict__ obs_u, const double* __restrict__ obs_v, cons
       // rotated point Y = R X (the record's first three entries)
       rec[0] = Yr[0]; rec[1] = Yr[1]; rec[2] = Yr[2];
       double qy[3];  // Q y
+      if constexpr (NC == 6) {
+        // compact record (SchurRec<6>; the layout of ba_math.h rec6_pack, packed here beside the rhs terms that share its products): 1 / Zc, then
+        // rows 0 and 1 of Q = G^T Z; the third row, -(x Q_row0 + y Q_row1), is never formed
+        rec[3] = nrm[2];
 #pragma unroll
-      for (int r = 3; r < NC; ++r) {  // rows 3..5: Q = G^T Z; rows 6..8: T_intr = A_intr^T Z
-        const bool live = r < np;
-        const double a0 = (r < 6) ? G[0][r - 3] : Aint[0][(r - 6) % 3], a1 = (r < 6) ? G[1][r - 3] : Aint[1][(r - 6) % 3];
-        double t[3];
+        for (int r = 3; r < 5; ++r) {
+          const double a0 = G[0][r - 3], a1 = G[1][r - 3];
+          double t[3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) t[k] = live ? a0 * Z[0][k] + a1 * Z[1][k] : 0.0;
-        const double ty = t[0] * y[0] + t[1] * y[1] + t[2] * y[2];
-        if (r < 6) qy[r - 3] = ty;
-        if (DET) bval[r] = live ? ty : 0.0;
-        else if (live) lds_add(&bc[r], ty);
-        rec[3 * r - 6] = t[0]; rec[3 * r - 5] = t[1]; rec[3 * r - 4] = t[2];
+          for (int k = 0; k < 3; ++k) t[k] = a0 * Z[0][k] + a1 * Z[1][k];
+          qy[r - 3] = t[0] * y[0] + t[1] * y[1] + t[2] * y[2];
+          rec[3 * r - 5] = t[0]; rec[3 * r - 4] = t[1]; rec[3 * r - 3] = t[2];
+        }
+        qy[2] = -fma(nrm[0], qy[0], nrm[1] * qy[1]);
+#pragma unroll
+        for (int r = 3; r < 6; ++r) {
+          if (DET) bval[r] = qy[r - 3];
+          else lds_add(&bc[r], qy[r - 3]);
+        }
+      } else {
+#pragma unroll
+        for (int r = 3; r < NC; ++r) {  // rows 3..5: Q = G^T Z; rows 6..8: T_intr = A_intr^T Z
+          const bool live = r < np;
+          const double a0 = (r < 6) ? G[0][r - 3] : Aint[0][(r - 6) % 3], a1 = (r < 6) ? G[1][r - 3] : Aint[1][(r - 6) % 3];
+          double t[3];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) t[k] = live ? a0 * Z[0][k] + a1 * Z[1][k] : 0.0;
+          const double ty = t[0] * y[0] + t[1] * y[1] + t[2] * y[2];
+          if (r < 6) qy[r - 3] = ty;
+          if (DET) bval[r] = live ? ty : 0.0;
+          else if (live) lds_add(&bc[r], ty);
+          rec[3 * r - 6] = t[0]; rec[3 * r - 5] = t[1]; rec[3 * r - 4] = t[2];
+        }
       }
       {  // rows 0..2 of the right-hand side: J_l^T c, c = Y x (Q y)
         const double c0 = Yr[1] * qy[2] - Yr[2] * qy[1], c1 = Yr[2] * qy[0] - Yr[0] * qy[2], c2 = Yr[0] * qy[1] - Yr[1] * qy[0];
@@ -1616,7 +1656,7 @@ template <int NC> struct Reg3Cfg {
   static constexpr int PAIR_CAP = 0;
   static constexpr int SCHUNK = (NC == 9) ? 384 : 320;                              // slots per chunk (per LDS buffer)
   static constexpr int EPW = SCHUNK / NWAVES;                                       // slots loaded by one wave (80 / 32)
-  static constexpr int NLD = (EPW * LST + WAVE - 1) / WAVE;                         // load instructions per wave and chunk (9 / 6)
+  static constexpr int NLD = (EPW * LST + WAVE - 1) / WAVE;                         // load instructions per wave and chunk (7 / 6)
   static constexpr int WAVE_PIECES = NLD * WAVE;                                    // LDS pieces of one wave's run, padded to whole loads
   static constexpr int ZERO_PIECE = NWAVES * WAVE_PIECES;                           // all-zero record behind the chunk, in each buffer
   static constexpr int BUF_PIECES = ZERO_PIECE + LST + 1;                           // (+1: keeps the second buffer 32-byte aligned)
@@ -1635,19 +1675,41 @@ template <int NC> struct Reg3Cfg {
   static_assert(CODE_WAVES % 4 == 0, "iteration counts: four waves per word");
 };
 
-// primed pair product of six-parameter cameras, T'_i T'_j^T added to the thread's 6 x 6 accumulators: 99 FP64 instructions on 12 + 12 doubles
-__device__ __forceinline__ void pair6(double (&acc)[6][6], const double2* __restrict__ Ri, const double2* __restrict__ Rj) {
-  const double2 i0 = Ri[0], i1 = Ri[1], i2 = Ri[2], i3 = Ri[3], i4 = Ri[4], i5 = Ri[5];
-  const double2 j0 = Rj[0], j1 = Rj[1], j2 = Rj[2], j3 = Rj[3], j4 = Rj[4], j5 = Rj[5];
+// the layout numbers tests/test_compact_records.py replays the plan with (EPW, LST, WAVE_PIECES, SCHUNK): a change here has to change them there
+static_assert(Reg3Cfg<6>::EPW == 80 && Reg3Cfg<6>::LST == 5 && Reg3Cfg<6>::NLD == 7 && Reg3Cfg<6>::WAVE_PIECES == 448 && Reg3Cfg<6>::SCHUNK == 320 &&
+                  Reg3Cfg<6>::ZERO_PIECE == 1792,
+              "six-parameter pair kernel layout");
+
+// primed pair product of six-parameter cameras, T'_i T'_j^T with T' = [[Y]x Q ; Q], added to the thread's 6 x 6 accumulators: 102 FP64 instructions on
+// the 10 + 10 doubles of two compact records (Y, 1/Zc, Q_row0, Q_row1).  Q's third row is -(x Q_row0 + y Q_row1), so D = Q_i Q_j^T is its 2 x 2 corner
+// (12 instructions), bordered by a third column -(x_j D[a][0] + y_j D[a][1]) (4) and a third row -(x_i D[0][b] + y_i D[1][b]) (6); x = (Y0 + t0) / Zc and
+// y = (Y1 + t1) / Zc (8 for the two records) take the translations of the thread's two cameras, constants of the thread.
+__device__ __forceinline__ void pair6(double (&acc)[6][6], const double2* __restrict__ Ri, const double2* __restrict__ Rj, double ti0, double ti1, double tj0,
+                                      double tj1) {
+  // Five whole 16-byte reads per record, as vector loads.  Read as double2 members the compiler may split a record into doubles and pair them anew
+  // (with nine doubles in use it made ds_read2_b64 of doubles (1, 2), (3, 4), ...: eight-byte accesses at half the rate of ds_read_b128, straddling
+  // the pieces whose bank groups the plan colours — the pair phase went from 97k to 133k clocks per wave).
+  typedef double piece_t __attribute__((ext_vector_type(2)));
+  const piece_t* Pi = reinterpret_cast<const piece_t*>(Ri);
+  const piece_t* Pj = reinterpret_cast<const piece_t*>(Rj);
+  const piece_t i0 = Pi[0], i1 = Pi[1], i2 = Pi[2], i3 = Pi[3], i4 = Pi[4];
+  const piece_t j0 = Pj[0], j1 = Pj[1], j2 = Pj[2], j3 = Pj[3], j4 = Pj[4];
   const double Yi[3] = {i0.x, i0.y, i1.x}, Yj[3] = {j0.x, j0.y, j1.x};
-  const double Qi[9] = {i1.y, i2.x, i2.y, i3.x, i3.y, i4.x, i4.y, i5.x, i5.y};
-  const double Qj[9] = {j1.y, j2.x, j2.y, j3.x, j3.y, j4.x, j4.y, j5.x, j5.y};
+  const double xi = (Yi[0] + ti0) * i1.y, yi = (Yi[1] + ti1) * i1.y, xj = (Yj[0] + tj0) * j1.y, yj = (Yj[1] + tj1) * j1.y;  // (rec6_xy)
+  const double Qi[6] = {i2.x, i2.y, i3.x, i3.y, i4.x, i4.y};
+  const double Qj[6] = {j2.x, j2.y, j3.x, j3.y, j4.x, j4.y};
   double M[3][6];
 #pragma unroll
-  for (int a = 0; a < 3; ++a) {
+  for (int a = 0; a < 2; ++a) {
 #pragma unroll
-    for (int b2 = 0; b2 < 3; ++b2)
+    for (int b2 = 0; b2 < 2; ++b2)
       M[a][3 + b2] = fma(Qi[3 * a + 2], Qj[3 * b2 + 2], fma(Qi[3 * a + 1], Qj[3 * b2 + 1], Qi[3 * a] * Qj[3 * b2]));
+    M[a][5] = -fma(xj, M[a][3], yj * M[a][4]);
+  }
+#pragma unroll
+  for (int b2 = 0; b2 < 3; ++b2) M[2][3 + b2] = -fma(xi, M[0][3 + b2], yi * M[1][3 + b2]);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
     M[a][0] = fma(Yj[1], M[a][5], -(Yj[2] * M[a][4]));
     M[a][1] = fma(Yj[2], M[a][3], -(Yj[0] * M[a][5]));
     M[a][2] = fma(Yj[0], M[a][4], -(Yj[1] * M[a][3]));
@@ -1735,6 +1797,33 @@ __device__ __forceinline__ void schur_reg3_body(const TilePlan& tp, const unsign
     }
     __syncthreads();
   }
+  // the cameras of this thread's block (the epilogue's J_l factors; NC = 6: their translations, which pair6 rebuilds the normalised points with)
+  int ci = -1, cj = -1;
+  auto block_cameras = [&]() {
+    if (blk >= nblk) return;
+    const int tile = tp.wg_tile[wg];
+    const int ga = tp.tile_a[tile], gb = tp.tile_b[tile];
+    const int ca0 = tp.group_cam_begin[ga], na = tp.group_cam_begin[ga + 1] - ca0;
+    const int cb0 = tp.group_cam_begin[gb], nb = tp.group_cam_begin[gb + 1] - cb0;
+    const int li = blk / tp.g, lj = blk % tp.g;
+    if (ga == gb && lj <= li) {  // helper thread of a diagonal tile: the (i, i) items of one camera (schur_plan.h)
+      const int hk = li * (li + 1) / 2 + lj;
+      ci = cj = ca0 + hk % max(na, 1);
+    } else if (li < na && lj < nb) {  // (else a ragged group: no such camera, nothing is accumulated)
+      ci = ca0 + li; cj = cb0 + lj;
+    }
+  };
+  double ti0 = 0.0, ti1 = 0.0, tj0 = 0.0, tj1 = 0.0;
+  if constexpr (NC == 6) {
+    block_cameras();
+    if (ci >= 0) {
+      ti0 = tab[(long)ci * CAMTAB_DOUBLES + 9]; ti1 = tab[(long)ci * CAMTAB_DOUBLES + 10];  // CamTab::t
+      tj0 = tab[(long)cj * CAMTAB_DOUBLES + 9]; tj1 = tab[(long)cj * CAMTAB_DOUBLES + 10];
+    }
+    // (landed and laundered here: left pending into the loop, the compiler would wait for them at their first use in every trip, behind the gather)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("" : "+v"(ti0), "+v"(ti1), "+v"(tj0), "+v"(tj1));
+  }
   const int last = first + (own_trips ? (own_trips - 1) * stride : 0);  // last chunk of this workgroup
   // Per trip every wave issues, in this order and WITHOUT waiting in between: the codes of the next chunk and the record indices
   // of the chunk after next (their addresses come from the iteration counts / offsets loaded a trip earlier), the counts and
@@ -1808,7 +1897,7 @@ __device__ __forceinline__ void schur_reg3_body(const TilePlan& tp, const unsign
     const double2* Ri = bufp + (code & 0xffffu);
     const double2* Rj = bufp + (code >> 16);
     if constexpr (NC == 6) {
-      pair6(acc, Ri, Rj);
+      pair6(acc, Ri, Rj, ti0, ti1, tj0, tj1);
     } else {
       if (half == 0) pair9_corner(acc, Ri, Rj);
       else if (half == 1) pair9_cols(accf, Ri, Rj);
@@ -1896,19 +1985,8 @@ __device__ __forceinline__ void schur_reg3_body(const TilePlan& tp, const unsign
   // The accumulators hold PRIMED blocks T'_i T'_j^T (T' = [[Y]x Q ; Q ; T_intr]); the true block is P_i^T (.) P_j with P = blockdiag(J_l, I).  That
   // map is linear, so every thread applies it to its own partial block here — ~100 FMAs once per kernel — and no separate pass over the reduced
   // matrix is needed.
-  if (blk < nblk) {
-    const int tile = tp.wg_tile[wg];
-    const int ga = tp.tile_a[tile], gb = tp.tile_b[tile];
-    const int ca0 = tp.group_cam_begin[ga], na = tp.group_cam_begin[ga + 1] - ca0;
-    const int cb0 = tp.group_cam_begin[gb], nb = tp.group_cam_begin[gb + 1] - cb0;
-    const int li = blk / tp.g, lj = blk % tp.g;
-    int ci = -1, cj = -1;
-    if (ga == gb && lj <= li) {  // helper thread of a diagonal tile: the (i, i) items of one camera (schur_plan.h)
-      const int hk = li * (li + 1) / 2 + lj;
-      ci = cj = ca0 + hk % max(na, 1);
-    } else if (li < na && lj < nb) {  // (else a ragged group: no such camera, nothing was accumulated)
-      ci = ca0 + li; cj = cb0 + lj;
-    }
+  {
+    if constexpr (NC != 6) block_cameras();  // (nine parameters: looked up here, the pair loop has no registers to carry them)
     if (ci >= 0) {
       const double* Ji = tab + (long)ci * CAMTAB_DOUBLES + 12;  // CamTab::Jl, row-major
       const double* Jj = tab + (long)cj * CAMTAB_DOUBLES + 12;
@@ -3238,8 +3316,8 @@ k_backsub(const double* __restrict__ obs_u, const double* __restrict__ obs_v, co
 // The body is a function with Trec as a __restrict__ PARAMETER for the reason given at schur_reg3_body (LDS reads may pass the pending DMA).
 constexpr int BSR_PT = 3 * CHUNK;  // doubles of one buffer of per-observation terms
 template <int NC> struct BsrCfg {
-  static constexpr int NP = SchurRec<NC>::NPH;       // 16-byte pieces of a record in HBM (6 / 11)
-  static constexpr int CS = (NC == 9) ? 9 : 6;       // doubles of a camera's step entry
+  static constexpr int NP = SchurRec<NC>::NPH;       // 16-byte pieces of a record in HBM (5 / 11)
+  static constexpr int CS = (NC == 9) ? 9 : 8;       // doubles of a camera's entry: its step (w, dt [, di]); six parameters: and t0, t1
   static constexpr int CSS = CS;                     // its stride in LDS (an odd stride would spread the banks; 40 000 bytes per workgroup let four share a CU)
   static constexpr size_t lds_bytes(int n_cams) { return ((size_t)BLOCK * NP * 2 + 2 * BSR_PT + (size_t)n_cams * CSS + 8) * sizeof(double); }
 };
@@ -3263,6 +3341,7 @@ __device__ __forceinline__ void backsub_rec_body(const double* __restrict__ Trec
     sh_step[c * CSS + a] = fma(Jl[3 * a + 2], s_cam[off + 2], fma(Jl[3 * a + 1], s_cam[off + 1], Jl[3 * a] * s_cam[off]));
     sh_step[c * CSS + 3 + a] = s_cam[off + 3 + a];
     if (NC == 9) sh_step[c * CSS + 6 + a] = (cam_np[c] == 9) ? s_cam[off + 6 + a] : 0.0;
+    if (NC == 6 && a < 2) sh_step[c * CSS + 6 + a] = tab[(long)c * CAMTAB_DOUBLES + 9 + a];  // t0, t1: the compact record's x and y are rebuilt with them (rec6_xy)
   }
   const int n_obs = chunk_start[n_chunks];
   const int last_obs = max(n_obs - 1, 0);
@@ -3390,10 +3469,20 @@ __device__ __forceinline__ void backsub_rec_body(const double* __restrict__ Trec
       const double m0 = fma(w1, Y2, fma(-w2, Y1, cs[3]));
       const double m1 = fma(w2, Y0, fma(-w0, Y2, cs[4]));
       const double m2 = fma(w0, Y1, fma(-w1, Y0, cs[5]));
-      // Q row-major behind Y: entries 3..11 of the record
-      t0 = fma(rec[4].y, m2, fma(rec[3].x, m1, rec[1].y * m0));
-      t1 = fma(rec[5].x, m2, fma(rec[3].y, m1, rec[2].x * m0));
-      t2 = fma(rec[5].y, m2, fma(rec[4].x, m1, rec[2].y * m0));
+      if constexpr (NC == 6) {
+        // compact record (Y, 1/Zc, Q_row0, Q_row1): Q^T m = Q_row0^T (m0 - x m2) + Q_row1^T (m1 - y m2) because Q_row2 = -(x Q_row0 + y Q_row1),
+        // x = (Y0 + t0) / Zc, y = (Y1 + t1) / Zc with the camera's t0, t1 in cs[6], cs[7]
+        const double x = (Y0 + cs[6]) * rec[1].y, y = (Y1 + cs[7]) * rec[1].y;
+        const double v0 = fma(-x, m2, m0), v1 = fma(-y, m2, m1);
+        t0 = fma(rec[3].y, v1, rec[2].x * v0);
+        t1 = fma(rec[4].x, v1, rec[2].y * v0);
+        t2 = fma(rec[4].y, v1, rec[3].x * v0);
+      } else {
+        // Q row-major behind Y: entries 3..11 of the record
+        t0 = fma(rec[4].y, m2, fma(rec[3].x, m1, rec[1].y * m0));
+        t1 = fma(rec[5].x, m2, fma(rec[3].y, m1, rec[2].x * m0));
+        t2 = fma(rec[5].y, m2, fma(rec[4].x, m1, rec[2].y * m0));
+      }
       if constexpr (NC == 9) {  // T_intr row-major: entries 12..20
         const double i0 = cs[6], i1 = cs[7], i2 = cs[8];
         t0 = fma(rec[9].x, i2, fma(rec[7].y, i1, fma(rec[6].x, i0, t0)));
@@ -4142,7 +4231,7 @@ k_heavy_schur(const int* __restrict__ heavy_pts, const int* __restrict__ pt_star
   for (int i = o0 + threadIdx.x; i < o1; i += BLOCK) {
     const int cam = obs_cam[i], off = cam_off[cam], np = cam_np[cam];
     double T[3 * NC];
-    expand_record<NC>(Trec + (long)i * REC, tab + (long)cam * CAMTAB_DOUBLES + 12, T);  // compact record -> true T (J_l of the camera)
+    expand_record<NC>(Trec + (long)i * REC, tab + (long)cam * CAMTAB_DOUBLES, T);  // compact record -> true T (J_l of the camera)
 #pragma unroll
     for (int r = 0; r < NC; ++r) {  // (constant trip count: T stays in registers; `r < np` as a loop bound indexed it dynamically: 160 / 224 bytes of scratch)
       if (r < np) {
@@ -4428,7 +4517,7 @@ k_con_schur(ConPlan cp, VecLayout lay, double lam, const double* __restrict__ Vb
       for (int i = pt_start[p]; i < pt_start[p + 1]; ++i) {
         const int cam = obs_cam[i];
         double T[3 * NC];
-        expand_record<NC>(Trec + (long)i * REC, tab + (long)cam * CAMTAB_DOUBLES + 12, T);
+        expand_record<NC>(Trec + (long)i * REC, tab + (long)cam * CAMTAB_DOUBLES, T);
         const int off = cam_off[cam], npar = cam_np[cam];
 #pragma unroll
         for (int r = 0; r < NC; ++r)  // (constant trip count: T stays in registers)
@@ -4545,7 +4634,7 @@ k_con_schur_small(ConPlan cp, VecLayout lay, double lam, const double* __restric
     for (int i = pt_start[p] + (tid % 16); i < pt_start[p + 1]; i += 16) {
       const int cam = obs_cam[i];
       double T[3 * NC];
-      expand_record<NC>(Trec + (long)i * REC, tab + (long)cam * CAMTAB_DOUBLES + 12, T);
+      expand_record<NC>(Trec + (long)i * REC, tab + (long)cam * CAMTAB_DOUBLES, T);
       const int off = cam_off[cam], npar = cam_np[cam];
 #pragma unroll
       for (int r = 0; r < NC; ++r)  // (constant trip count: T stays in registers)
