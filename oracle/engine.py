@@ -219,6 +219,7 @@ class OracleEngine:
             red = self._allreduce(np.concatenate([S_loc.reshape(-1), b_loc]))
             S = self.U + lam * np.diag(D2[:ncp]) + red[: ncp * ncp].reshape(ncp, ncp)
             rhs = -g_c + red[ncp * ncp :]
+            self.S, self.rhs = S, rhs  # (kept for the tests that compare the reduced system itself)
             try:
                 L = np.linalg.cholesky(0.5 * (S + S.T))
             except np.linalg.LinAlgError:
@@ -247,6 +248,7 @@ class OracleEngine:
         red = self._allreduce(np.concatenate([S_loc.reshape(-1), b_loc]))
         S = self.U + lam * np.diag(D2[:ncp]) + red[: ncp * ncp].reshape(ncp, ncp)
         rhs = -g_c + red[ncp * ncp :]
+        self.S, self.rhs = S, rhs
         try:
             L = np.linalg.cholesky(S)
         except np.linalg.LinAlgError:
