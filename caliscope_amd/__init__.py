@@ -6,6 +6,8 @@ _EXPORTS = {"reconstruct_trajectories": "caliscope_amd.reconstruction", "reconst
             "RefineOptions": "caliscope_amd.trajectory_refinement", "CovarianceOptions": "caliscope_amd.trajectory_uncertainty",
             "SmootherOptions": "caliscope_amd.trajectory_smoother", "smooth_trajectories": "caliscope_amd.trajectory_smoother",
             "smoothed_frame": "caliscope_amd.trajectory_smoother", "DeviceTrajectorySmoother": "caliscope_amd.trajectory_smoother",
+            "Skeleton": "caliscope_amd.trajectory_skeleton", "SkeletonOptions": "caliscope_amd.trajectory_skeleton",
+            "adjust_skeleton": "caliscope_amd.trajectory_skeleton", "DeviceSkeletonAdjuster": "caliscope_amd.trajectory_skeleton",
             "UncertaintyReport": "caliscope_amd.uncertainty", "DeviceUncertainty": "caliscope_amd.uncertainty",
             "ReliabilityReport": "caliscope_amd.reliability", "DeviceReliability": "caliscope_amd.reliability"}
 
