@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ba_math.h"
+#include "kernel_plan.h"
 #include "trf_math.h"
 #include "wg_binding.h"
 #include "chol_schedule.h"
@@ -21,7 +22,7 @@ namespace cba {
 
 constexpr int BLOCK = 256;
 constexpr int CHUNK = 256;
-constexpr int WAVE = 64;
+static_assert(BLOCK == dims::BLOCK && CHUNK == dims::CHUNK, "kernel_plan.h lays out the LDS for these sizes");
 
 struct VecLayout {
   int ncp;      // number of camera parameters
@@ -95,11 +96,7 @@ __device__ __forceinline__ double block_max(double v, double* sh) {
 
 __device__ __forceinline__ void lds_add(double* addr, double v) { unsafeAtomicAdd(addr, v); }
 
-// LDS copy of the camera table.  Rows are padded to 49 doubles: with the natural stride of 48 doubles
-// (96 dwords == 32 mod 64 banks) the lanes of a wave, each reading the same field of a different camera,
-// would land on two bank pairs (32-way conflict); an odd stride spreads 32 cameras over all bank pairs.
-constexpr int CAMTAB_LIVE = 36;               // doubles of a CamTab row in use (everything up to and including pad[0], the camera's parameter offset)
-constexpr int CAMTAB_LDS = CAMTAB_LIVE + 1;    // 37 (odd): the padding stays in HBM (49 doubles per camera cost k_build / k_tprep their third workgroup per CU)
+// (the LDS copy of the camera table, CAMTAB_LIVE doubles of a row at the odd stride CAMTAB_LDS: kernel_plan.h)
 // The per-observation kernels walk their chunks with the NEXT chunk's observation record already in flight:
 // registers for (u, v, camera, point) of chunk n + 1 are loaded (unconditionally, index clamped) before chunk n is
 // processed, so each workgroup sees the streaming-load latency once instead of once per chunk.
@@ -180,8 +177,9 @@ k_cost(const double* __restrict__ obs_u, const double* __restrict__ obs_v, const
        const double* __restrict__ tab, int n_cams, int loss, double f_scale, double* __restrict__ partial,
        int* __restrict__ flags, double* __restrict__ r_out, const int* __restrict__ order) {
   extern __shared__ __attribute__((aligned(16))) double sh[];
-  double* sh_tab = sh;
-  double* sh_red = sh + (CAMG ? 0 : n_cams * CAMTAB_LDS);
+  const CostLds L(n_cams, CAMG);
+  double* sh_tab = sh + L.tab;
+  double* sh_red = sh + L.red;
   if (!CAMG) stage_camtab(sh_tab, tab, n_cams);
   __syncthreads();
   const double* px = xvec + lay.ncp_pad;
@@ -458,12 +456,6 @@ __device__ __forceinline__ void obs_factors(const CamTab& c_lds, double X, doubl
   }
 }
 
-template <int NC> struct UPack {
-  static constexpr int TRI = NC * (NC + 1) / 2;
-  static constexpr int STRIDE = TRI + NC;  // upper triangle + gradient
-  __host__ __device__ static constexpr int idx(int r, int c) { return r * NC - r * (r - 1) / 2 + (c - r); }
-};
-
 // ------------------------------------------------------------------------------------------------
 // Deterministic per-camera sums (cba_options.deterministic).  The default kernels add an observation's share of U_c, g_c
 // (k_build) and of the rhs (k_tprep) with FP64 LDS atomics, whose order — and with it the last bits of the sums, and now
@@ -472,8 +464,8 @@ template <int NC> struct UPack {
 // camera in the chunk's FIXED camera-sorted order (cba_create lays out, per chunk, the observation order by camera and the
 // camera offsets); every thread owns the running sums of its (camera, value) tasks for the whole kernel, so the
 // per-workgroup partials and everything downstream (k_reduce_rows, fixed order) are reproducible bit for bit.
-constexpr int DET_ROUND = 9;              // values per observation and round
-constexpr int DET_LD = CHUNK + 1;         // row stride of the parking area (odd: the nine rows of a task group hit nine banks)
+constexpr int DET_ROUND = 9;              // values per observation and round (parked at the row stride DET_LD: kernel_plan.h)
+static_assert(DET_ROUND == dims::DET_ROUND, "kernel_plan.h lays out the parking area for this many");
 struct DetPlan {
   const unsigned char* perm;    // [n_chunks][CHUNK] chunk-local observation indices, sorted by camera
   const unsigned short* cstart; // [n_chunks][C + 1] offsets into perm
@@ -532,15 +524,16 @@ k_build(const double* __restrict__ obs_u, const double* __restrict__ obs_v, cons
   constexpr bool DET = DETM > 0;
   if (skip && *skip != 0.0) return;  // fused step without a trial (k_fused_subspace handed the iteration to the host)
   extern __shared__ __attribute__((aligned(16))) double sh[];
-  double* sh_tab = sh;
-  double* sh_U = sh_tab + (CAMG ? 0 : n_cams * CAMTAB_LDS);            // DET: the parking area of det_round instead
+  const BuildLds<NC> L(n_cams, DET, CAMG);
+  double* sh_tab = sh + L.tab;
+  double* sh_U = sh + L.U;                                             // DET: the parking area of det_round instead
   auto cam_of = [&](int cam) -> const CamTab& {
     return CAMG ? *reinterpret_cast<const CamTab*>(tab + (long)cam * CAMTAB_DOUBLES) : cam_at(sh_tab, cam);
   };
-  double* sh_pt = sh_U + (DET ? DET_ROUND * DET_LD : n_cams * UP::STRIDE);
-  double* sh_red = sh_pt + 9 * CHUNK;
-  int* sh_perm = reinterpret_cast<int*>(sh_red + 8);                   // DET: [CHUNK] + [n_cams + 1]
-  int* sh_cs = sh_perm + CHUNK;
+  double* sh_pt = sh + L.pt;
+  double* sh_red = sh + L.red;
+  int* sh_perm = reinterpret_cast<int*>(reinterpret_cast<char*>(sh) + L.perm);  // DET: [CHUNK] + [n_cams + 1]
+  int* sh_cs = reinterpret_cast<int*>(reinterpret_cast<char*>(sh) + L.cs);
   constexpr int DROUNDS = (UP::STRIDE + DET_ROUND - 1) / DET_ROUND;    // 3 / 6
   constexpr int DM = DET ? DETM : 1;                                   // tasks per thread and round: ceil(C * 9 / 256)
   double dacc[DROUNDS][DM];
@@ -720,12 +713,13 @@ k_build_cs(CsPlan cs, const double* __restrict__ xvec, VecLayout lay, const doub
   static_assert(!UGLOB || CAMG, "a camera count beyond the LDS copy of the blocks is beyond the LDS copy of the table as well");
   if (skip && *skip != 0.0) return;  // fused step without a trial (k_fused_subspace handed the iteration to the host)
   extern __shared__ __attribute__((aligned(16))) double sh[];
-  double* sh_tab = sh;
-  double* sh_U = sh_tab + (CAMG ? 0 : n_cams * CAMTAB_LDS);
   const int PM = cs.pmax;
-  double* sh_vg = sh_U + (UGLOB ? 0 : n_cams * UP::STRIDE);        // [9][PM]
-  double* sh_x = sh_vg + 9 * PM;                     // [3][PM]
-  double* sh_red = sh_x + 3 * PM;
+  const BuildCsLds<NC> L(n_cams, PM, CAMG, UGLOB);
+  double* sh_tab = sh + L.tab;
+  double* sh_U = sh + L.U;
+  double* sh_vg = sh + L.vg;                         // [9][PM]
+  double* sh_x = sh + L.x;                           // [3][PM]
+  double* sh_red = sh + L.red;
   if (!CAMG) stage_camtab(sh_tab, tab, n_cams);
   if (!UGLOB)
     for (int i = threadIdx.x; i < n_cams * UP::STRIDE; i += BLOCK) sh_U[i] = 0.0;
@@ -1028,9 +1022,10 @@ k_jv(const double* __restrict__ obs_u, const double* __restrict__ obs_v, const i
     return;
   }
   extern __shared__ __attribute__((aligned(16))) double sh[];
-  double* sh_tab = sh;
-  double* sh_v = sh_tab + (CAMG ? 0 : n_cams * CAMTAB_LDS);  // NV * ncp_pad
-  double* sh_red = sh_v + NV * lay.ncp_pad;
+  const JvLds L(n_cams, lay.ncp_pad, NV, CAMG);
+  double* sh_tab = sh + L.tab;
+  double* sh_v = sh + L.v;  // NV * ncp_pad
+  double* sh_red = sh + L.red;
   if (!CAMG) stage_camtab(sh_tab, tab, n_cams);
   for (int i = threadIdx.x; i < lay.ncp_pad; i += BLOCK) {
     sh_v[i] = v1[i];
@@ -1193,22 +1188,7 @@ struct TilePlan {
 // HBM and in LDS; a reader rebuilds x and y from its camera's t (a constant of a pair-kernel thread; staged per camera by the back-substitution).
 // (First form, measured and dropped: (x, y, Zc, Q_row0, Q_row1) with the sums formed on Yc = Y + t and the translation taken off per camera —
 // two instructions per record cheaper, but the rotation blocks lost |Yc|^2 / |Y|^2 of their precision to the cancellation.)
-template <int NC> struct SchurRec {
-  static constexpr int NVAL = (NC == 9) ? 21 : 10;        // doubles that carry data
-  static constexpr int NPH = (NVAL + 1) / 2;              // 16-byte pieces that carry data: 5 / 11
-  static constexpr int LST = (NPH & 1) ? NPH : NPH + 1;   // record stride in LDS, 16-byte pieces, odd: 5 / 11 (bank spread)
-  static constexpr int REC = 2 * LST;                     // record stride in LDS, doubles: 10 / 22
-  // record stride in HBM, doubles: the pieces that carry data, 10 / 22 (80 / 176 bytes).  (128-byte records, one line each, were measured on the
-  // twelve-double form: the pair kernel's issue phase shrank by 7 %, k_tprep grew by as much, and the pass moved 1.15 GB instead of 0.93 GB through HBM.)
-  static constexpr int HREC = 2 * NPH;
-  static constexpr int STAGE = (HREC / 2) | 1;            // k_tprep's transposing LDS stage: record stride in pieces, odd (bank spread)
-  // waves of a k_tprep workgroup that stage at the same time.  NC = 9: two, in two turns — with a stage for all four (45 KB) next to the camera
-  // table the kernel had 92 KB of LDS and ran one workgroup per CU
-  static constexpr int STAGE_WAVES = (NC == 9) ? 2 : 4;
-};
-static_assert(SchurRec<6>::REC == 10 && SchurRec<6>::LST == 5 && SchurRec<6>::HREC == 10 && SchurRec<6>::STAGE == 5 && SchurRec<9>::REC == 22 &&
-                  SchurRec<9>::LST == 11,
-              "record sizes");
+// (SchurRec<NC>, the sizes: kernel_plan.h)
 
 // true T (NC x 3, row-major) from a compact record and the camera's table row (t and J_l, row-major): k_heavy_schur, k_con_schur
 template <int NC>
@@ -1310,16 +1290,17 @@ k_tprep(const double* __restrict__ obs_u, const double* __restrict__ obs_v, cons
     lam = lin_finish_block(lf, sh_lf_red, sh_lf_out);
   } else if (lam_dev) lam = *lam_dev;  // fused step: the damping was computed on the device (k_fused_lam / k_lin_finish)
   extern __shared__ __attribute__((aligned(16))) double sh[];
-  double2* sh_stage = reinterpret_cast<double2*>(sh);        // [SW][WAVE * SP]  record transpose, per wave (of a turn)
-  double* sh_tab = sh + (size_t)SW * WAVE * SP * 2;
-  double* sh_b = sh_tab + (CAMG ? 0 : n_cams * CAMTAB_LDS);  // ncp_pad (DET: the parking area of det_round, then the chunk's camera order)
-  int* sh_perm = reinterpret_cast<int*>(sh_b + DET_ROUND * DET_LD);
-  int* sh_cs = sh_perm + CHUNK;
+  const TprepLds<NC> L(n_cams, lay.ncp_pad, DET, CAMG);
+  double2* sh_stage = reinterpret_cast<double2*>(sh + L.stage);  // [SW][WAVE * SP]  record transpose, per wave (of a turn)
+  double* sh_tab = sh + L.tab;
+  double* sh_b = sh + L.b;  // ncp_pad (DET: the parking area of det_round, then the chunk's camera order)
+  int* sh_perm = reinterpret_cast<int*>(reinterpret_cast<char*>(sh) + L.perm);
+  int* sh_cs = reinterpret_cast<int*>(reinterpret_cast<char*>(sh) + L.cs);
   constexpr int DM = DET ? DETM : 1;
   double dacc[DM];
 #pragma unroll
   for (int m = 0; m < DM; ++m) dacc[m] = 0.0;
-  stage_camtab(sh_tab, tab, n_cams);
+  if (!CAMG) stage_camtab(sh_tab, tab, n_cams);
   if (!DET)
     for (int i = threadIdx.x; i < lay.ncp_pad; i += BLOCK) sh_b[i] = 0.0;
   __syncthreads();
@@ -2872,9 +2853,7 @@ k_chol_step(double* __restrict__ W, int n, int ldw, int k, int* __restrict__ fla
 // blocked Cholesky (the 32-pivot wave factorisation of chol_factor_block per diagonal block, panel solves with its inverse, trailing updates; the
 // rhs rides along as row n), backward substitution with the blocks' inverses, x to `out`.  Replaces k_schur_finalize + ncp / 32 + 1 k_chol_step +
 // k_chol_apply: five launches of 4-9 us each on cfg2, where every launch — however small — occupies the device for ~4.5 us.
-constexpr int SMALL_N = 96;
-constexpr int SMALL_THREADS = 512;
-constexpr int SMALL_LD = SMALL_N + 1;  // odd row stride
+constexpr int SMALL_THREADS = 512;  // (SMALL_N, SMALL_LD and the LDS layout, SmallSolveLds: kernel_plan.h)
 template <int NC>
 __global__ void __launch_bounds__(SMALL_THREADS)
 k_small_solve(const double* __restrict__ Sacc, const double* __restrict__ bacc, const double* __restrict__ Upacked, const double* __restrict__ gvec,
@@ -2885,18 +2864,19 @@ k_small_solve(const double* __restrict__ Sacc, const double* __restrict__ bacc, 
   CBA_STAMP(ST_SMALL_SOLVE);
   using UP = UPack<NC>;
   extern __shared__ __attribute__((aligned(16))) double sh[];
-  double (*W)[SMALL_LD] = reinterpret_cast<double (*)[SMALL_LD]>(sh);                       // [n + 1][SMALL_LD]: S, then rhs^T
-  double (*D)[NB + 1] = reinterpret_cast<double (*)[NB + 1]>(sh + (SMALL_N + 1) * SMALL_LD);  // [2 NB][NB + 1]: chol_factor_block's block
-  double (*X)[NB][NB + 1] = reinterpret_cast<double (*)[NB][NB + 1]>(&D[2 * NB][0]);          // [nbk][NB][NB + 1]: inverses of the diagonal blocks
-  double* y = &X[(SMALL_N + NB - 1) / NB][0][0];                                              // [SMALL_N]
+  using L = SmallSolveLds;
+  double (*W)[SMALL_LD] = reinterpret_cast<double (*)[SMALL_LD]>(sh + L::W);             // [n + 1][SMALL_LD]: S, then rhs^T
+  double (*D)[NB + 1] = reinterpret_cast<double (*)[NB + 1]>(sh + L::D);                 // [2 NB][NB + 1]: chol_factor_block's block
+  double (*X)[NB][NB + 1] = reinterpret_cast<double (*)[NB][NB + 1]>(sh + L::X);         // [nbk][NB][NB + 1]: inverses of the diagonal blocks
+  double* y = sh + L::y;                                                                 // [SMALL_N]
   if (lam_dev) lam = *lam_dev;
   const int tid = threadIdx.x, nbk = (n + NB - 1) / NB;
   // 1. the reduced system (k_schur_finalize's arithmetic).  A thread handles several entries one after the other, so nothing a load's address
   // depends on may come from global memory inside the loops (a chain of three dependent loads per entry was 25 of this kernel's first 42 us): the
   // per-parameter tables go to LDS first, the off-block entries are four independent loads per trip, the few entries inside a camera's own block
   // (they carry U_c, the damping and the folded helper sums) have a loop of their own.
-  int* pc = reinterpret_cast<int*>(y + SMALL_N);  // [n] camera of a parameter
-  int* pl = pc + SMALL_N;                         // [n] its index inside the camera's block
+  int* pc = reinterpret_cast<int*>(reinterpret_cast<char*>(sh) + L::pc);  // [n] camera of a parameter
+  int* pl = reinterpret_cast<int*>(reinterpret_cast<char*>(sh) + L::pl);  // [n] its index inside the camera's block
   for (int i = tid; i < n; i += SMALL_THREADS) {
     pc[i] = param_cam[i]; pl[i] = param_loc[i];
     const double rv = -gvec[i] + b_entry(bacc, b_width, i);
@@ -3162,9 +3142,10 @@ k_backsub(const double* __restrict__ obs_u, const double* __restrict__ obs_v, co
   CBA_STAMP(ST_BACKSUB);
   extern __shared__ __attribute__((aligned(16))) double sh[];
   if (lam_dev) lam = *lam_dev;
-  double* sh_tab = sh;
-  double* sh_dc = sh_tab + (CAMG ? 0 : n_cams * CAMTAB_LDS);  // ncp_pad
-  double* sh_pt = sh_dc + lay.ncp_pad;               // [3][CHUNK]
+  const BacksubLds L(n_cams, lay.ncp_pad, CAMG);
+  double* sh_tab = sh + L.tab;
+  double* sh_dc = sh + L.dc;  // ncp_pad
+  double* sh_pt = sh + L.pt;  // [3][CHUNK]
   if (!CAMG) stage_camtab(sh_tab, tab, n_cams);
   for (int i = threadIdx.x; i < lay.ncp_pad; i += BLOCK) sh_dc[i] = svec[i];
   __syncthreads();
@@ -3314,13 +3295,7 @@ k_backsub(const double* __restrict__ obs_u, const double* __restrict__ obs_v, co
 //     from the other — by threads spread over all four waves — in the same barrier interval, so one barrier per chunk and no wave waits for
 //     a serial point phase (k_backsub: one wave solved the points of a chunk while three were parked: SQ_WAIT_ANY 68 %).
 // The body is a function with Trec as a __restrict__ PARAMETER for the reason given at schur_reg3_body (LDS reads may pass the pending DMA).
-constexpr int BSR_PT = 3 * CHUNK;  // doubles of one buffer of per-observation terms
-template <int NC> struct BsrCfg {
-  static constexpr int NP = SchurRec<NC>::NPH;       // 16-byte pieces of a record in HBM (5 / 11)
-  static constexpr int CS = (NC == 9) ? 9 : 8;       // doubles of a camera's entry: its step (w, dt [, di]); six parameters: and t0, t1
-  static constexpr int CSS = CS;                     // its stride in LDS (an odd stride would spread the banks; 40 000 bytes per workgroup let four share a CU)
-  static constexpr size_t lds_bytes(int n_cams) { return ((size_t)BLOCK * NP * 2 + 2 * BSR_PT + (size_t)n_cams * CSS + 8) * sizeof(double); }
-};
+// (BsrCfg<NC>, the sizes and the LDS layout: kernel_plan.h)
 template <int NC, bool SCAL>
 __device__ __forceinline__ void backsub_rec_body(const double* __restrict__ Trec, const int* __restrict__ obs_cam, const int* __restrict__ pt_start,
                                                  const int* __restrict__ chunk_start, const int* __restrict__ chunk_pts, int n_chunks, VecLayout lay,
@@ -3330,9 +3305,9 @@ __device__ __forceinline__ void backsub_rec_body(const double* __restrict__ Trec
                                                  double* __restrict__ step_partial, double* sh) {
   using Cfg = BsrCfg<NC>;
   constexpr int NP = Cfg::NP, CSS = Cfg::CSS;
-  double2* sh_rec = reinterpret_cast<double2*>(sh);          // [BLOCK][NP] pieces, wave w owns [w * 64 * NP, (w + 1) * 64 * NP)
-  double* sh_pt = sh + (size_t)BLOCK * NP * 2;               // [2][3][CHUNK]
-  double* sh_step = sh_pt + 2 * BSR_PT;                      // [n_cams][CSS]
+  double2* sh_rec = reinterpret_cast<double2*>(sh + Cfg::REC);  // [BLOCK][NP] pieces, wave w owns [w * 64 * NP, (w + 1) * 64 * NP)
+  double* sh_pt = sh + Cfg::PT;                                 // [2][3][CHUNK]
+  double* sh_step = sh + Cfg::STEP;                             // [n_cams][CSS]
   const int tid = (int)threadIdx.x, lane = tid % WAVE;
   const int wv = __builtin_amdgcn_readfirstlane(tid / WAVE);
   for (int idx = tid; idx < n_cams * 3; idx += BLOCK) {

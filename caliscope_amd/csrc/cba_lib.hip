@@ -115,7 +115,7 @@ struct cba_problem {
   int ldw = 0;             // row stride of the Cholesky work matrix Lbuf (multiple of 4 doubles)
   double *Sacc = nullptr, *S = nullptr, *Lbuf = nullptr, *rhs = nullptr, *red = nullptr, *Trec = nullptr, *partial_b = nullptr;
   CsPlan cs{};              // camera-sorted super-chunks of the build pass (k_build_cs); cs.n_sc == 0: k_build (CBA_BUILD_CS=0, deterministic sums, fragments)
-  bool tab_global = false;  // the per-observation kernels read the camera table from global memory (CAMG variants): its LDS copy would not fit
+  KernelRoutes routes;      // which variant of every kernel family the handle runs (kernel_plan.h), chosen once by cba_create
   int det_m = 0;  // cba_options.deterministic: tasks per thread of the fixed-order camera sums (3, 5, 8 or 16; 0: atomics)
   DetPlan det{nullptr, nullptr};
   double* tri = nullptr;   // packed upper triangle of Sacc + b for the exchange of a sharded solve
@@ -142,7 +142,6 @@ struct cba_problem {
   int grid_backsub = 1;  // k_backsub keeps 34 KB of LDS (cfg4): more resident workgroups than the 57-65 KB kernels sharing p->grid
   int jv_grid = 0;       // workgroups of k_jv: what the device holds at once (its 150 registers per thread admit three 256-thread workgroups per CU)
   bool has_fragments = false;  // some chunk is a fragment of a point with more than CHUNK observations (k_backsub adds its sums by atomics)
-  bool backsub_rec = false;    // the back-substitution streams the T records (k_backsub_rec) instead of linearising every observation again
   int n_heavy = 0; int* heavy_pts = nullptr; int* heavy_frag = nullptr; double* heavy_W = nullptr;  // heavy points (k_heavy_schur)
   std::vector<int> h_heavy_pts;
   ConPlan con{};           // rigid-distance constraint rows (cba_set_constraints); con.n_con == 0: none
@@ -772,13 +771,13 @@ static int raise_lds_ceiling(const void* fn, size_t bytes) {
 
 // k_tprep and k_jv run in their LIN form: asked at every launch, because cba_set_loss changes the loss of a live handle.  Six-parameter kernels only
 // (LIN_FORM<NC>): the nine-parameter k_tprep measured SLOWER without the pixels (cfg5: 535 - 541 us against 495 - 507), and where
-// LIN_FORM is false the launch sites below name the generic instantiation twice.
+// LIN_FORM is false the pickers below name the generic instantiation twice.
 template <int NC> constexpr bool LIN_FORM = NC == 6;
 template <int NC> static bool linear_pass_now(const cba_problem* p) { return LIN_FORM<NC> && p->linear_pass && p->loss == LOSS_LINEAR; }
 
 template <typename K>
 static int allow_lds(K kernel, size_t bytes) {
-  if (bytes > 160 * 1024) return fail(CBA_ERR_UNSUPPORTED, "kernel needs %zu bytes of LDS (> 160 KiB)", bytes);
+  if (bytes > LDS_MAX) return fail(CBA_ERR_UNSUPPORTED, LDS_REFUSAL, bytes);
   return raise_lds_ceiling(reinterpret_cast<const void*>(kernel), bytes);
 }
 
@@ -793,44 +792,76 @@ static int resident_per_cu(K kernel, size_t lds, int fallback) {
   return std::min(n, 8);
 }
 
-static size_t lds_tab(const cba_problem* p) { return p->tab_global ? 0 : (size_t)p->C * CAMTAB_LDS; }  // doubles of the LDS copy of the camera table
-static size_t lds_cost(const cba_problem* p) { return (lds_tab(p) + 8) * 8; }
-// k_build<NC, 0, true> reads the camera table from global memory: chosen when the table is what keeps a second workgroup off the CU
-template <int NC> static size_t lds_build_camg(const cba_problem* p) { return ((size_t)p->C * UPack<NC>::STRIDE + 9 * CHUNK + 8) * 8; }
-template <int NC> static bool build_camg(const cba_problem* p) {
-  if (p->tab_global) return true;
-  const size_t with_tab = ((size_t)p->C * CAMTAB_LDS + (size_t)p->C * UPack<NC>::STRIDE + 9 * CHUNK + 8) * 8;
-  if (const char* e = std::getenv("CBA_BUILD_CAMG")) return std::atoi(e) != 0 && !p->det_m;
-  // (a second workgroup per CU when the table is what keeps it off; no choice at all when table + accumulators exceed the LDS)
-  return !p->det_m && ((with_tab > 80 * 1024 && lds_build_camg<NC>(p) <= 80 * 1024) || with_tab > 160 * 1024);
-}
-template <int NC> static size_t lds_build_cs(const cba_problem* p, bool camg, bool uglob = false) {
-  return ((camg ? 0 : (size_t)p->C * CAMTAB_LDS) + (uglob ? 0 : (size_t)p->C * UPack<NC>::STRIDE) + 12 * (size_t)p->cs.pmax + 8) * 8;
-}
-// beyond ~650 six- / ~320 nine-parameter cameras the packed camera blocks do not fit the LDS: one global copy, FP64 global atomics (k_build_cs<.., UGLOB>)
-template <int NC> static bool build_cs_uglob(const cba_problem* p) { return lds_build_cs<NC>(p, true) > 160 * 1024; }
-// k_build_cs keeps the camera table in LDS while that leaves room for two workgroups per CU
-template <int NC> static bool build_cs_camg(const cba_problem* p) { return p->tab_global || lds_build_cs<NC>(p, false) > 80 * 1024; }
-template <int NC> static size_t lds_build(const cba_problem* p) {
-  if (build_camg<NC>(p)) return lds_build_camg<NC>(p);
-  if (p->det_m)  // parking area of the fixed-order sums instead of the packed blocks, + the chunk's camera order (ints)
-    return ((size_t)p->C * CAMTAB_LDS + (size_t)DET_ROUND * DET_LD + 9 * CHUNK + 8) * 8 + ((size_t)CHUNK + p->C + 1) * 4;
-  return ((size_t)p->C * CAMTAB_LDS + (size_t)p->C * UPack<NC>::STRIDE + 9 * CHUNK + 8) * 8;
-}
-static size_t lds_jv(const cba_problem* p, int nv) { return (lds_tab(p) + (size_t)nv * p->lay.ncp_pad + 8) * 8; }
 // Register-accumulating Schur kernel per camera width: rows of a camera-pair block per thread = NC / SPLIT, minimum waves
 // per SIMD the kernel is compiled for, resident workgroups per CU the plan sizes its grid for (see k_schur_reg3).
 template <int NC> struct RegCfg;
 template <> struct RegCfg<6> { static constexpr int SPLIT = 1, MINW = 2, PER_CU = 2; };
 template <> struct RegCfg<9> { static constexpr int SPLIT = 3, MINW = 3, PER_CU = 1; };
-template <int NC> static size_t lds_tprep(const cba_problem* p) {
-  if (p->det_m) return ((size_t)SchurRec<NC>::STAGE_WAVES * WAVE * SchurRec<NC>::STAGE * 2 + (size_t)p->C * CAMTAB_LDS + (size_t)DET_ROUND * DET_LD) * 8 + ((size_t)CHUNK + p->C + 1) * 4;
-  return ((size_t)SchurRec<NC>::STAGE_WAVES * WAVE * SchurRec<NC>::STAGE * 2 + lds_tab(p) + p->lay.ncp_pad) * 8;
-}
 constexpr int kSchurRegMaxGroup = 16;  // g*g blocks <= 256 threads
-constexpr size_t kSmallSolveLds = ((size_t)(SMALL_N + 1) * SMALL_LD + (size_t)2 * NB * (NB + 1) + (size_t)((SMALL_N + NB - 1) / NB) * NB * (NB + 1) + 2 * SMALL_N) * 8;  // k_small_solve
-static size_t lds_backsub(const cba_problem* p) { return (lds_tab(p) + p->lay.ncp_pad + 3 * CHUNK) * 8; }
-template <int NC> static size_t lds_backsub_rec(const cba_problem* p) { return BsrCfg<NC>::lds_bytes(p->C); }
+
+// ---- one picker per kernel family: the runtime flags of a launch -> the instantiation.  configure_kernels raises the LDS ceilings over the same
+// functions, so a variant a launch can reach is a variant that was made ready; nullptr: the combination has no instantiation. --------------------
+static auto cost_kernel(bool write_r, bool camg) {
+  static constexpr decltype(&k_cost<false, false>) k[2][2] = {{k_cost<false, false>, k_cost<false, true>}, {k_cost<true, false>, k_cost<true, true>}};
+  return k[write_r][camg];
+}
+constexpr int kDetM[] = {3, 5, 8, 16};  // tasks per thread of the fixed-order sums that have kernels (16: six-parameter cameras only)
+template <int NC> static auto build_kernel(int det_m, bool camg) -> decltype(&k_build<NC>) {
+  if (det_m && camg) return nullptr;  // (the fixed-order sums keep the camera table in LDS)
+  switch (det_m) {
+    case 0: return camg ? k_build<NC, 0, true> : k_build<NC, 0>;
+    case 3: return k_build<NC, 3>;
+    case 5: return k_build<NC, 5>;
+    case 8: return k_build<NC, 8>;
+    case 16: if constexpr (NC == 6) return k_build<NC, 16>;
+  }
+  return nullptr;
+}
+template <int NC> static auto build_cs_kernel(bool camg, bool uglob, bool trial) -> decltype(&k_build_cs<NC>) {
+  if (uglob) return !camg ? nullptr : trial ? k_build_cs<NC, true, true, true> : k_build_cs<NC, true, true>;
+  if (camg) return trial ? k_build_cs<NC, true, false, true> : k_build_cs<NC, true>;
+  return trial ? k_build_cs<NC, false, false, true> : k_build_cs<NC, false>;
+}
+// lin: the LIN form of a linear loss, where LIN_FORM<NC> has one (linear_pass_now)
+template <int NC> static auto jv_kernel(int nv, bool camg, bool lin) -> decltype(&k_jv<NC, 1>) {
+  constexpr bool L = LIN_FORM<NC>;
+  static constexpr decltype(&k_jv<NC, 1>) k[2][2][2] = {{{k_jv<NC, 1, false>, k_jv<NC, 1, false, L>}, {k_jv<NC, 1, true>, k_jv<NC, 1, true, L>}},
+                                                         {{k_jv<NC, 2, false>, k_jv<NC, 2, false, L>}, {k_jv<NC, 2, true>, k_jv<NC, 2, true, L>}}};
+  return (nv == 1 || nv == 2) ? k[nv - 1][camg][lin] : nullptr;
+}
+// linf: the launch finishes the linearisation's reductions itself (LinFin); lin as for jv_kernel
+template <int NC> static auto tprep_kernel(int det_m, bool camg, bool linf, bool lin) -> decltype(&k_tprep<NC>) {
+  constexpr bool L = LIN_FORM<NC>;
+  if (det_m && (camg || linf)) return nullptr;
+  switch (det_m) {
+    case 0: {
+      static constexpr decltype(&k_tprep<NC>) k[2][2][2] = {{{k_tprep<NC, 0, false, false>, k_tprep<NC, 0, false, false, L>}, {k_tprep<NC, 0, false, true>, k_tprep<NC, 0, false, true, L>}},
+                                                            {{k_tprep<NC, 0, true, false>, k_tprep<NC, 0, true, false, L>}, {k_tprep<NC, 0, true, true>, k_tprep<NC, 0, true, true, L>}}};
+      return k[camg][linf][lin];
+    }
+    case 3: return lin ? k_tprep<NC, 3, false, false, L> : k_tprep<NC, 3>;
+    case 5: return lin ? k_tprep<NC, 5, false, false, L> : k_tprep<NC, 5>;
+    case 8: return lin ? k_tprep<NC, 8, false, false, L> : k_tprep<NC, 8>;
+    case 16: if constexpr (NC == 6) return lin ? k_tprep<NC, 16, false, false, L> : k_tprep<NC, 16>;
+  }
+  return nullptr;
+}
+template <int NC> static auto backsub_kernel(bool camg, bool scal) {
+  static constexpr decltype(&k_backsub<NC>) k[2][2] = {{k_backsub<NC, false, false>, k_backsub<NC, false, true>}, {k_backsub<NC, true, false>, k_backsub<NC, true, true>}};
+  return k[camg][scal];
+}
+template <int NC> static auto backsub_rec_kernel(bool scal) { return scal ? k_backsub_rec<NC, true> : k_backsub_rec<NC, false>; }
+static int no_kernel(const char* family, int nct, int det_m) {
+  return fail(CBA_ERR_UNSUPPORTED, "%s: no kernel for %d-parameter cameras with %d fixed-order tasks per thread", family, nct, det_m);
+}
+
+// the LDS layouts of a handle's launches (kernel_plan.h: what the kernels carve up), on the handle's routes
+static CostLds cost_lds(const cba_problem* p) { return CostLds(p->C, p->routes.tab_global); }
+template <int NC> static BuildLds<NC> build_lds(const cba_problem* p) { return BuildLds<NC>(p->C, p->det_m != 0, p->routes.build_pt_camg); }
+template <int NC> static BuildCsLds<NC> build_cs_lds(const cba_problem* p) { return BuildCsLds<NC>(p->C, p->cs.pmax, p->routes.build_cs_camg, p->routes.build_uglob); }
+static JvLds jv_lds(const cba_problem* p, int nv) { return JvLds(p->C, p->lay.ncp_pad, nv, p->routes.tab_global); }
+template <int NC> static TprepLds<NC> tprep_lds(const cba_problem* p) { return TprepLds<NC>(p->C, p->lay.ncp_pad, p->det_m != 0, p->routes.tab_global); }
+static BacksubLds backsub_lds(const cba_problem* p) { return BacksubLds(p->C, p->lay.ncp_pad, p->routes.tab_global); }
 
 
 // Plan of the pair kernel (schur_plan.h builds it on the host).  The dealing is ~1 us of host work per observation and needs nothing but the
@@ -1057,99 +1088,74 @@ static void choose_schur_groups(cba_problem* p) {
   p->n_tiles = p->G * (p->G + 1) / 2;
 }
 
+// -1: not set; CBA_CAMTAB_GLOBAL and CBA_BUILD_CAMG are numbers (0: off), CBA_BACKSUB_REC is '0' or '1' (anything else: not set)
+static int env_switch(const char* name, bool digit_only) {
+  const char* e = std::getenv(name);
+  if (!e) return -1;
+  if (digit_only) return e[0] == '1' ? 1 : e[0] == '0' ? 0 : -1;
+  return std::atoi(e) != 0;
+}
+// the routes of the handle, once (kernel_plan.h); the three switches are read here and nowhere else
+static int choose_routes(cba_problem* p) {
+  p->routes = kernel_routes(p->C, p->nct, p->lay.ncp_pad, p->det_m, p->n_heavy, p->cs.n_sc, p->cs.pmax, p->eval_only, p->has_fragments,
+                            env_switch("CBA_CAMTAB_GLOBAL", false), env_switch("CBA_BUILD_CAMG", false), env_switch("CBA_BACKSUB_REC", true));
+  if (p->routes.refused_bytes) return fail(CBA_ERR_UNSUPPORTED, LDS_REFUSAL, p->routes.refused_bytes);
+  return CBA_OK;
+}
+
+// Raises the LDS ceilings of every kernel the handle can launch: each family's picker over its flag domain, with the bytes of the handle's routes.
 template <int NC>
 static int configure_kernels(cba_problem* p) {
   int rc;
-  // The camera table in LDS (296 B per camera) next to the largest other LDS user: beyond the budget every per-observation kernel switches to
-  // its CAMG variant (table through the vector cache).  What then bounds the camera count is the per-camera accumulators of the linearisation
-  // (nc (nc + 3) / 2 doubles per camera in LDS: ~650 six-parameter or ~320 nine-parameter cameras).  CBA_CAMTAB_GLOBAL=0/1 forces the choice (tests).
-  {
-    p->tab_global = false;
-    const size_t worst = std::max(std::max(lds_jv(p, 2), lds_backsub(p)), lds_tprep<NC>(p));  // (the linearisation has its own switch: build_camg)
-    p->tab_global = !p->det_m && worst > 150 * 1024;
-    if (const char* e = std::getenv("CBA_CAMTAB_GLOBAL")) p->tab_global = std::atoi(e) != 0 && !p->det_m;
-  }
-  if ((rc = allow_lds(k_cost<false>, lds_cost(p)))) return rc;
-  if ((rc = allow_lds(k_cost<true>, lds_cost(p)))) return rc;
-  if ((rc = allow_lds(k_cost<false, true>, lds_cost(p)))) return rc;
-  if ((rc = allow_lds(k_cost<true, true>, lds_cost(p)))) return rc;
-  const bool use_cs = p->cs.n_sc && !p->det_m && !p->n_heavy;  // (run_build_into's condition)
-  if (use_cs) {
-    if (build_cs_uglob<NC>(p)) { rc = allow_lds(k_build_cs<NC, true, true>, lds_build_cs<NC>(p, true, true)); if (!rc) rc = allow_lds(k_build_cs<NC, true, true, true>, lds_build_cs<NC>(p, true, true)); }
-    else if (build_cs_camg<NC>(p)) { rc = allow_lds(k_build_cs<NC, true>, lds_build_cs<NC>(p, true)); if (!rc) rc = allow_lds(k_build_cs<NC, true, false, true>, lds_build_cs<NC>(p, true)); }
-    else { rc = allow_lds(k_build_cs<NC, false>, lds_build_cs<NC>(p, false)); if (!rc) rc = allow_lds(k_build_cs<NC, false, false, true>, lds_build_cs<NC>(p, false)); }
-    if (rc) return rc;
-  }
-  if (!use_cs || !build_cs_uglob<NC>(p)) {  // the point-ordered kernel keeps the packed blocks in LDS: not with that many cameras
-    if ((rc = allow_lds(k_build<NC>, lds_build<NC>(p)))) return rc;
-    if ((rc = allow_lds(k_build<NC, 0, true>, lds_build<NC>(p)))) return rc;
-  } else if (p->eval_only) {
-    // (nothing: an evaluation-only handle runs k_cost only)
-  }
-  if (p->det_m) {
-    if ((rc = allow_lds(k_build<NC, 3>, lds_build<NC>(p)))) return rc;
-    if ((rc = allow_lds(k_build<NC, 5>, lds_build<NC>(p)))) return rc;
-    if ((rc = allow_lds(k_build<NC, 8>, lds_build<NC>(p)))) return rc;
-    if ((rc = allow_lds(k_tprep<NC, 3>, lds_tprep<NC>(p)))) return rc;
-    if ((rc = allow_lds(k_tprep<NC, 5>, lds_tprep<NC>(p)))) return rc;
-    if ((rc = allow_lds(k_tprep<NC, 8>, lds_tprep<NC>(p)))) return rc;
-    if ((rc = allow_lds(k_tprep<NC, 3, false, false, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
-    if ((rc = allow_lds(k_tprep<NC, 5, false, false, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
-    if ((rc = allow_lds(k_tprep<NC, 8, false, false, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
-    if constexpr (NC == 6) {
-      if ((rc = allow_lds(k_build<NC, 16>, lds_build<NC>(p)))) return rc;
-      if ((rc = allow_lds(k_tprep<NC, 16>, lds_tprep<NC>(p)))) return rc;
-      if ((rc = allow_lds(k_tprep<NC, 16, false, false, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
-    }
-  }
-  if ((rc = allow_lds(k_jv<NC, 1>, lds_jv(p, 1)))) return rc;
-  if ((rc = allow_lds(k_jv<NC, 2>, lds_jv(p, 2)))) return rc;
-  if ((rc = allow_lds(k_jv<NC, 1, true>, lds_jv(p, 1)))) return rc;
-  if ((rc = allow_lds(k_jv<NC, 2, true>, lds_jv(p, 2)))) return rc;
+  const KernelRoutes& r = p->routes;
+  auto allow = [&](auto kernel, size_t bytes) { return kernel ? allow_lds(kernel, bytes) : CBA_OK; };  // (nullptr: no such instantiation, nothing to launch)
+  for (int wr = 0; wr < 2; ++wr)
+    for (int camg = 0; camg < 2; ++camg)
+      if ((rc = allow(cost_kernel(wr, camg), cost_lds(p).bytes()))) return rc;
+  if (r.build_cs)
+    for (int trial = 0; trial < 2; ++trial)
+      if ((rc = allow(build_cs_kernel<NC>(r.build_cs_camg, r.build_uglob, trial), build_cs_lds<NC>(p).bytes()))) return rc;
+  if (!r.build_uglob)  // the point-ordered kernel keeps the packed blocks in LDS: not with that many cameras
+    for (int camg = 0; camg < 2; ++camg)
+      if ((rc = allow(build_kernel<NC>(0, camg), build_lds<NC>(p).bytes()))) return rc;
   // (the LIN forms of a linear loss: the loss of a handle can change, cba_set_loss, so both are made ready)
-  if ((rc = allow_lds(k_jv<NC, 1, false, LIN_FORM<NC>>, lds_jv(p, 1)))) return rc;
-  if ((rc = allow_lds(k_jv<NC, 2, false, LIN_FORM<NC>>, lds_jv(p, 2)))) return rc;
-  if ((rc = allow_lds(k_jv<NC, 1, true, LIN_FORM<NC>>, lds_jv(p, 1)))) return rc;
-  if ((rc = allow_lds(k_jv<NC, 2, true, LIN_FORM<NC>>, lds_jv(p, 2)))) return rc;
-  if ((rc = allow_lds(k_schur_reg3<NC, RegCfg<NC>::SPLIT, RegCfg<NC>::MINW>, Reg3Cfg<NC>::LDS_BYTES))) return rc;
-  if ((rc = allow_lds(k_tprep<NC>, lds_tprep<NC>(p)))) return rc;
-  if ((rc = allow_lds(k_tprep<NC, 0, true>, lds_tprep<NC>(p)))) return rc;
-  if ((rc = allow_lds(k_tprep<NC, 0, false, true>, lds_tprep<NC>(p)))) return rc;
-  if ((rc = allow_lds(k_tprep<NC, 0, true, true>, lds_tprep<NC>(p)))) return rc;
-  if ((rc = allow_lds(k_tprep<NC, 0, false, false, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
-  if ((rc = allow_lds(k_tprep<NC, 0, true, false, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
-  if ((rc = allow_lds(k_tprep<NC, 0, false, true, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
-  if ((rc = allow_lds(k_tprep<NC, 0, true, true, LIN_FORM<NC>>, lds_tprep<NC>(p)))) return rc;
-  if ((rc = allow_lds(k_backsub<NC>, lds_backsub(p)))) return rc;
-  if ((rc = allow_lds(k_backsub<NC, true>, lds_backsub(p)))) return rc;
-  if ((rc = allow_lds(k_backsub<NC, false, true>, lds_backsub(p)))) return rc;
-  if ((rc = allow_lds(k_backsub<NC, true, true>, lds_backsub(p)))) return rc;
-  // back-substitution from the T records: whenever no chunk is a fragment of a very large point (those add their sums by atomics in k_backsub) and the
-  // per-camera step entries fit the LDS next to the record buffer (~2400 six- / ~1000 nine-parameter cameras); CBA_BACKSUB_REC=0: the old kernel (A/B)
-  {
-    const char* e = std::getenv("CBA_BACKSUB_REC");
-    // nine-parameter cameras keep k_backsub: their records are 176 bytes, and streaming them costs more than linearising again (cfg5, round 6: 394 us
-    // against 326; six-parameter cameras, cfg4: 48 against 64)
-    p->backsub_rec = (NC == 6 || (e && e[0] == '1')) && !p->eval_only && !p->has_fragments && lds_backsub_rec<NC>(p) <= 150 * 1024 && !(e && e[0] == '0');
-    if (p->backsub_rec) {
-      if ((rc = allow_lds(k_backsub_rec<NC, false>, lds_backsub_rec<NC>(p)))) return rc;
-      if ((rc = allow_lds(k_backsub_rec<NC, true>, lds_backsub_rec<NC>(p)))) return rc;
-      if (!std::getenv("CBA_BACKSUB_WGS"))  // as many workgroups as are resident at once (cfg4: four per CU, 40 000 bytes of LDS each: 48 us against 53 at two)
-        p->grid_backsub = std::max(1, std::min(p->n_chunks, p->cus * resident_per_cu(k_backsub_rec<NC, true>, lds_backsub_rec<NC>(p), 2)));
+  if (p->det_m)
+    for (int m : kDetM) {
+      if ((rc = allow(build_kernel<NC>(m, false), build_lds<NC>(p).bytes()))) return rc;
+      for (int lin = 0; lin < 2; ++lin)
+        if ((rc = allow(tprep_kernel<NC>(m, false, false, lin), tprep_lds<NC>(p).bytes()))) return rc;
     }
+  for (int nv = 1; nv <= 2; ++nv)
+    for (int camg = 0; camg < 2; ++camg)
+      for (int lin = 0; lin < 2; ++lin)
+        if ((rc = allow(jv_kernel<NC>(nv, camg, lin), jv_lds(p, nv).bytes()))) return rc;
+  if ((rc = allow_lds(k_schur_reg3<NC, RegCfg<NC>::SPLIT, RegCfg<NC>::MINW>, Reg3Cfg<NC>::LDS_BYTES))) return rc;
+  for (int camg = 0; camg < 2; ++camg)
+    for (int linf = 0; linf < 2; ++linf)
+      for (int lin = 0; lin < 2; ++lin)
+        if ((rc = allow(tprep_kernel<NC>(0, camg, linf, lin), tprep_lds<NC>(p).bytes()))) return rc;
+  for (int camg = 0; camg < 2; ++camg)
+    for (int scal = 0; scal < 2; ++scal)
+      if ((rc = allow(backsub_kernel<NC>(camg, scal), backsub_lds(p).bytes()))) return rc;
+  if (r.backsub_rec) {
+    const size_t lds = BsrCfg<NC>::lds_bytes(p->C);
+    for (int scal = 0; scal < 2; ++scal)
+      if ((rc = allow(backsub_rec_kernel<NC>(scal), lds))) return rc;
+    if (!std::getenv("CBA_BACKSUB_WGS"))  // as many workgroups as are resident at once (cfg4: four per CU, 40 000 bytes of LDS each: 48 us against 53 at two)
+      p->grid_backsub = std::max(1, std::min(p->n_chunks, p->cus * resident_per_cu(backsub_rec_kernel<NC>(true), lds, 2)));
   }
   {
     // (asked of the generic kernel for every loss: the grid decides how ||J v||^2 is cut into partial sums, and a linear loss's LIN form, which needs
     // no more registers, has to leave the same bits)
-    int per_cu = p->tab_global ? resident_per_cu(k_jv<NC, 1, true>, lds_jv(p, 1), 2) : resident_per_cu(k_jv<NC, 1>, lds_jv(p, 1), 2);
+    int per_cu = resident_per_cu(jv_kernel<NC>(1, r.tab_global, false), jv_lds(p, 1).bytes(), 2);
     if (const char* e = std::getenv("CBA_JV_WGS")) per_cu = std::max(1, std::min(std::atoi(e), 8));
     p->jv_grid = (int)std::max<long>(1, std::min<long>((p->N + BLOCK - 1) / BLOCK, (long)p->cus * per_cu));
     p->jv_grid = std::min(p->jv_grid, JV_ROWS);  // (rows of partial4 before the constraint rows' CON_ROWS)
   }
-  if (p->n_heavy && (rc = allow_lds(k_heavy_schur<NC>, (size_t)p->ncp * 3 * sizeof(double) + (size_t)p->ncp * sizeof(int)))) return rc;
-  if ((rc = allow_lds(k_chol_apply, (size_t)p->ncp * 8))) return rc;
-  if ((rc = allow_lds(k_step_cam, (size_t)p->lay.ncp_pad * 8))) return rc;
-  if (p->one_workgroup_solve() && (rc = allow_lds(k_small_solve<NC>, kSmallSolveLds))) return rc;
+  if (p->n_heavy && (rc = allow_lds(k_heavy_schur<NC>, heavy_schur_lds_bytes(p->ncp)))) return rc;
+  if ((rc = allow_lds(k_chol_apply, chol_apply_lds_bytes(p->ncp)))) return rc;
+  if ((rc = allow_lds(k_step_cam, step_cam_lds_bytes(p->lay.ncp_pad)))) return rc;
+  if (p->one_workgroup_solve() && (rc = allow_lds(k_small_solve<NC>, SmallSolveLds::bytes()))) return rc;
   return CBA_OK;
 }
 
@@ -1447,6 +1453,7 @@ int cba_create(const cba_problem_desc* d, const cba_options* opt, cba_problem** 
   lap("upload observations");
   TRY(alloc_vectors(p));
   lap("allocate vectors");
+  TRY(choose_routes(p));
   if (nct == 9) TRY(configure_kernels<9>(p)); else TRY(configure_kernels<6>(p));
   lap("reorder, upload, allocate");
   if (!p->eval_only) TRY(install_first_plan(p, plan_timing));
@@ -1497,10 +1504,8 @@ int cba_get_info(cba_problem* p, cba_info* o) {
   o->schur_groups = p->G; o->schur_tiles = p->n_tiles; o->schur_grid = p->tile_grid; o->schur_stream_len = p->tile_stream_len; o->schur_pairs = p->n_pairs;
   o->max_obs_per_point = p->max_obs_per_point; o->device_bytes = p->device_bytes; o->n_heavy_points = p->n_heavy;
   {
-    const bool cs = p->cs.n_sc && !p->det_m && !p->n_heavy;
-    const bool camg = cs ? (p->nct == 6 ? build_cs_camg<6>(p) : build_cs_camg<9>(p)) : (p->nct == 6 ? build_camg<6>(p) : build_camg<9>(p));
-    const bool uglob = cs && (p->nct == 6 ? build_cs_uglob<6>(p) : build_cs_uglob<9>(p));
-    o->build_camg = (camg ? 1 : 0) | (p->tab_global ? 2 : 0) | (cs ? 4 : 0) | (uglob ? 8 : 0) | (p->backsub_rec ? 16 : 0) |
+    const KernelRoutes& r = p->routes;
+    o->build_camg = (r.build_camg() ? 1 : 0) | (r.tab_global ? 2 : 0) | (r.build_cs ? 4 : 0) | (r.build_uglob ? 8 : 0) | (r.backsub_rec ? 16 : 0) |
                     (p->con.n_con && p->con.small ? 32 : 0) | (p->one_workgroup_solve() ? 64 : 0);
   }
   o->spec_jv_skipped = p->spec_jv_skipped;
@@ -1559,12 +1564,8 @@ static int launch_cost(cba_problem* p, const double* xvec, const double* tab, in
   const int grid = (int)std::min<long>((p->N + BLOCK - 1) / BLOCK, 1024);
   {
     ScopedTimer t(p, T_COST);
-    auto launch = [&](auto kernel, double* r, const int* ord) {
-      hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds_cost(p), p->stream, p->obs_u, p->obs_v, p->obs_cam,
-                         p->obs_pt, p->N, xvec, p->lay, tab, p->C, p->loss, p->f_scale, p->partial1, p->flags, r, ord);
-    };
-    if (r_out) { if (p->tab_global) launch(k_cost<true, true>, r_out, (const int*)p->order); else launch(k_cost<true>, r_out, (const int*)p->order); }
-    else { if (p->tab_global) launch(k_cost<false, true>, (double*)nullptr, (const int*)nullptr); else launch(k_cost<false>, (double*)nullptr, (const int*)nullptr); }
+    hipLaunchKernelGGL(cost_kernel(r_out != nullptr, p->routes.tab_global), dim3(grid), dim3(BLOCK), cost_lds(p).bytes(), p->stream, p->obs_u, p->obs_v, p->obs_cam,
+                       p->obs_pt, p->N, xvec, p->lay, tab, p->C, p->loss, p->f_scale, p->partial1, p->flags, r_out, r_out ? (const int*)p->order : (const int*)nullptr);
   }
   ScopedTimer t(p, T_VECTOR);
   int rows = grid;
@@ -1581,7 +1582,7 @@ static int launch_cost(cba_problem* p, const double* xvec, const double* tab, in
 // Single-rank fused iteration over camera-sorted super-chunks: the step scalars of the point block come out of k_backsub, one workgroup
 // (k_step_cam) adds the camera block, takes the subspace step and prepares the trial point's cameras, and the trial build forms the point
 // entries of the trial point itself — k_step_scalars, k_step_finish / k_step_small and k_trial_update are not launched.
-static bool fused_trial(const cba_problem* p, bool compact) { return compact && p->cs.n_sc && !p->det_m && !p->n_heavy && !p->con.n_con; }
+static bool fused_trial(const cba_problem* p, bool compact) { return compact && p->routes.build_cs && !p->con.n_con; }
 // The plain scale pass rides in the launch that reduces the camera blocks (k_reduce_scale_pub) on the routes fused_trial names, unbounded.  Fixed-order
 // sums, sharded handles, constraint rows, heavy points and bounded solves (Coleman-Li scaling, k_scale_lin<NC, true>) keep the two launches.
 // (its rows must fit the 2048 of partial4b and partial_gmax: about 2.5 million points; beyond, the two launches)
@@ -1591,7 +1592,7 @@ static bool scale_fusable(const cba_problem* p, bool compact) {
 }
 
 // Build pass at xvec (camera table tab) into the given outputs; the rho sum lands in scal[cost_slot].
-// trial != nullptr (fused_trial): k_build_cs<.., TRIAL> forms the point entries of xvec = x_new from *trial while it stages them.
+// trial != nullptr (fused_trial): the TRIAL form of k_build_cs makes the point entries of xvec = x_new from *trial while it stages them.
 // scale != nullptr (scale_fusable): the plain scale pass at xvec runs inside the launch that reduces the camera blocks (k_reduce_scale_pub), which
 // also writes the camera entries of g whether `compact` or not; its rows: p->scale_rows.
 template <int NC>
@@ -1604,44 +1605,25 @@ static int run_build_into(cba_problem* p, const double* xvec, const double* tab,
     if (p->n_heavy)  // fragments of heavy points add their sums by atomics
       hipLaunchKernelGGL(k_zero_heavy, dim3((p->n_heavy + 63) / 64), dim3(64), 0, p->stream, p->heavy_pts, p->n_heavy, p->lay, V, 6,
                          g + p->lay.ncp_pad, 3);
-    auto launch_build = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(p->grid), dim3(BLOCK), lds_build<NC>(p), p->stream, p->obs_u, p->obs_v, p->obs_cam,
+    if (p->routes.build_cs) {  // camera-sorted super-chunks: the camera blocks accumulate in registers
+      const TrialSrc tsrc = trial ? *trial : TrialSrc{};
+      if (p->routes.build_uglob)
+        (void)hipMemsetAsync(p->partial, 0, (size_t)p->C * UPack<NC>::STRIDE * sizeof(double), p->stream);  // the ONE copy the atomics add to
+      hipLaunchKernelGGL(build_cs_kernel<NC>(p->routes.build_cs_camg, p->routes.build_uglob, trial != nullptr), dim3(p->grid), dim3(BLOCK), build_cs_lds<NC>(p).bytes(),
+                         p->stream, p->cs, xvec, p->lay, tab, p->C, p->loss, p->f_scale, V, g, p->partial, p->partial1, p->flags + flag_slot, skip, tsrc);
+    } else {  // point by point; deterministic: fixed-order camera sums, det_m tasks per thread
+      const auto kernel = build_kernel<NC>(p->det_m, p->routes.build_pt_camg);
+      if (!kernel) return no_kernel("k_build", NC, p->det_m);
+      hipLaunchKernelGGL(kernel, dim3(p->grid), dim3(BLOCK), build_lds<NC>(p).bytes(), p->stream, p->obs_u, p->obs_v, p->obs_cam,
                          p->obs_pt, p->pt_start, p->chunk_start, p->chunk_pts, p->n_chunks, xvec, p->lay, tab, p->C, p->loss, p->f_scale,
                          V, g, p->partial, p->partial1, p->flags + flag_slot, skip, p->det);
-    };
-    if (p->cs.n_sc && !p->det_m && !p->n_heavy) {  // camera-sorted super-chunks: the camera blocks accumulate in registers
-      const TrialSrc tsrc = trial ? *trial : TrialSrc{};
-      auto launch_cs = [&](auto kernel, size_t lds) {
-        hipLaunchKernelGGL(kernel, dim3(p->grid), dim3(BLOCK), lds, p->stream, p->cs, xvec, p->lay, tab, p->C, p->loss, p->f_scale,
-                           V, g, p->partial, p->partial1, p->flags + flag_slot, skip, tsrc);
-      };
-      if (build_cs_uglob<NC>(p)) {
-        (void)hipMemsetAsync(p->partial, 0, (size_t)p->C * UPack<NC>::STRIDE * sizeof(double), p->stream);  // the ONE copy the atomics add to
-        if (trial) launch_cs(k_build_cs<NC, true, true, true>, lds_build_cs<NC>(p, true, true));
-        else launch_cs(k_build_cs<NC, true, true>, lds_build_cs<NC>(p, true, true));
-      } else if (build_cs_camg<NC>(p)) {
-        if (trial) launch_cs(k_build_cs<NC, true, false, true>, lds_build_cs<NC>(p, true));
-        else launch_cs(k_build_cs<NC, true>, lds_build_cs<NC>(p, true));
-      } else {
-        if (trial) launch_cs(k_build_cs<NC, false, false, true>, lds_build_cs<NC>(p, false));
-        else launch_cs(k_build_cs<NC, false>, lds_build_cs<NC>(p, false));
-      }
-    } else
-    switch (p->det_m) {  // deterministic: fixed-order camera sums (k_build<NC, tasks per thread>)
-      case 3: launch_build(k_build<NC, 3>); break;
-      case 5: launch_build(k_build<NC, 5>); break;
-      case 8: launch_build(k_build<NC, 8>); break;
-      case 16: { if constexpr (NC == 6) launch_build(k_build<NC, 16>); } break;
-      default:
-        if (build_camg<NC>(p)) launch_build(k_build<NC, 0, true>); else launch_build(k_build<NC, 0>);
-        break;
     }
   }
   {
     ScopedTimer t(p, T_BUILD_REDUCE);
     const int w = p->C * UPack<NC>::STRIDE;
     // rows of per-workgroup partial blocks to sum; the global-atomics form of k_build_cs leaves ONE row
-    const int u_rows = (p->cs.n_sc && !p->det_m && !p->n_heavy && build_cs_uglob<NC>(p)) ? 1 : p->grid;
+    const int u_rows = p->routes.build_uglob ? 1 : p->grid;
     if (scale) {
       using SF = ScaleFuse<NC>;
       const int rows = SF::cam_wgs(p->C) + (int)SF::pt_wgs(p->lay);
@@ -1697,15 +1679,8 @@ static int run_jv(cba_problem* p, int nv, int* rows_out = nullptr, const double*
   const int con_rows = p->con.n_con ? p->con_grid : 0;
   if (grid + con_rows > PARTIAL4_ROWS)  // (nothing launched: the rows would land beyond the end of partial4)
     return fail(CBA_ERR_UNSUPPORTED, "run_jv: %d rows of k_jv and %d of k_con_jv exceed the %d rows of partial4", grid, con_rows, PARTIAL4_ROWS);
-  auto launch_jv = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds_jv(p, nv), p->stream, p->obs_u, p->obs_v, p->obs_cam, p->obs_pt,
-                       p->N, xvec, p->lay, tab, p->cam_off, p->C, p->loss, p->f_scale, p->v1, p->v2, p->partial4, skip);
-  };
-  if (linear_pass_now<NC>(p)) {
-    if (nv == 1) { if (p->tab_global) launch_jv(k_jv<NC, 1, true, LIN_FORM<NC>>); else launch_jv(k_jv<NC, 1, false, LIN_FORM<NC>>); }
-    else { if (p->tab_global) launch_jv(k_jv<NC, 2, true, LIN_FORM<NC>>); else launch_jv(k_jv<NC, 2, false, LIN_FORM<NC>>); }
-  } else if (nv == 1) { if (p->tab_global) launch_jv(k_jv<NC, 1, true>); else launch_jv(k_jv<NC, 1>); }
-  else { if (p->tab_global) launch_jv(k_jv<NC, 2, true>); else launch_jv(k_jv<NC, 2>); }
+  hipLaunchKernelGGL(jv_kernel<NC>(nv == 1 ? 1 : 2, p->routes.tab_global, linear_pass_now<NC>(p)), dim3(grid), dim3(BLOCK), jv_lds(p, nv).bytes(), p->stream, p->obs_u,
+                     p->obs_v, p->obs_cam, p->obs_pt, p->N, xvec, p->lay, tab, p->cam_off, p->C, p->loss, p->f_scale, p->v1, p->v2, p->partial4, skip);
   int rows = grid;
   if (con_rows) {
     if (nv == 1) hipLaunchKernelGGL(k_con_jv<1>, dim3(p->con_grid), dim3(BLOCK), 0, p->stream, p->con, p->lay, p->v1, p->v2, p->partial4 + 4 * grid);
@@ -1870,7 +1845,7 @@ static int enqueue_cholesky(cba_problem* p) {
     else hipLaunchKernelGGL(k_chol_last_apply<false>, grid, dim3(CHOL_THREADS), 0, p->stream, (const double*)p->Lbuf, n, p->ldw, (const double*)p->Xinv, (const double*)p->Tinv, p->s);
     return CBA_OK;
   }
-  hipLaunchKernelGGL(k_chol_apply, dim3(nbk), dim3(APPLY_THREADS), (size_t)n * 8, p->stream, (const double*)p->Tinv, (const double*)p->Lbuf, n, p->ldw, p->s);
+  hipLaunchKernelGGL(k_chol_apply, dim3(nbk), dim3(APPLY_THREADS), chol_apply_lds_bytes(n), p->stream, (const double*)p->Tinv, (const double*)p->Lbuf, n, p->ldw, p->s);
   return CBA_OK;
 }
 
@@ -2014,30 +1989,11 @@ static int run_newton_chain(cba_problem* p, double lam, const double* lam_dev, b
     {
       const bool linf = p->lf_pending;  // (set by run_lin_chain(defer_finish) of the same cba_step: never in fixed-order mode)
       p->lf_pending = false;
-      auto launch_tprep = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(p->grid), dim3(BLOCK), lds_tprep<NC>(p), p->stream, p->obs_u, p->obs_v, p->obs_cam, p->obs_pt,
-                           p->chunk_start, p->n_chunks, p->x, p->lay, p->tab, p->cam_off, p->C, p->loss, p->f_scale, lam, lam_dev, p->V, p->g,
-                           p->sinv, p->Trec, p->partial_b, p->flags, p->det, linf ? p->lf : LinFin{});
-      };
-      if (linear_pass_now<NC>(p)) switch (p->det_m) {  // the LIN forms: no pixel loads
-        case 3: launch_tprep(k_tprep<NC, 3, false, false, LIN_FORM<NC>>); break;
-        case 5: launch_tprep(k_tprep<NC, 5, false, false, LIN_FORM<NC>>); break;
-        case 8: launch_tprep(k_tprep<NC, 8, false, false, LIN_FORM<NC>>); break;
-        case 16: { if constexpr (NC == 6) launch_tprep(k_tprep<NC, 16, false, false, LIN_FORM<NC>>); } break;
-        default:
-          if (linf) { if (p->tab_global) launch_tprep(k_tprep<NC, 0, true, true, LIN_FORM<NC>>); else launch_tprep(k_tprep<NC, 0, false, true, LIN_FORM<NC>>); }
-          else if (p->tab_global) launch_tprep(k_tprep<NC, 0, true, false, LIN_FORM<NC>>); else launch_tprep(k_tprep<NC, 0, false, false, LIN_FORM<NC>>);
-          break;
-      } else switch (p->det_m) {
-        case 3: launch_tprep(k_tprep<NC, 3>); break;
-        case 5: launch_tprep(k_tprep<NC, 5>); break;
-        case 8: launch_tprep(k_tprep<NC, 8>); break;
-        case 16: { if constexpr (NC == 6) launch_tprep(k_tprep<NC, 16>); } break;
-        default:
-          if (linf) { if (p->tab_global) launch_tprep(k_tprep<NC, 0, true, true>); else launch_tprep(k_tprep<NC, 0, false, true>); }
-          else if (p->tab_global) launch_tprep(k_tprep<NC, 0, true>); else launch_tprep(k_tprep<NC, 0>);
-          break;
-      }
+      const auto tprep = tprep_kernel<NC>(p->det_m, p->routes.tab_global, linf, linear_pass_now<NC>(p));  // (its LIN form: no pixel loads)
+      if (!tprep) return no_kernel("k_tprep", NC, p->det_m);
+      hipLaunchKernelGGL(tprep, dim3(p->grid), dim3(BLOCK), tprep_lds<NC>(p).bytes(), p->stream, p->obs_u, p->obs_v, p->obs_cam, p->obs_pt,
+                         p->chunk_start, p->n_chunks, p->x, p->lay, p->tab, p->cam_off, p->C, p->loss, p->f_scale, lam, lam_dev, p->V, p->g,
+                         p->sinv, p->Trec, p->partial_b, p->flags, p->det, linf ? p->lf : LinFin{});
       // (the per-workgroup rhs rows k_tprep leaves in partial_b are summed by an extra grid row of k_reg_reduce, behind the pair kernel)
       ScopedTimer tpairs(p, T_SCHUR_PAIRS);  // nested in "schur": the pair kernel alone
       constexpr int SP = RegCfg<NC>::SPLIT, MW = RegCfg<NC>::MINW;
@@ -2074,7 +2030,7 @@ static int run_newton_chain(cba_problem* p, double lam, const double* lam_dev, b
         hipLaunchKernelGGL(k_reg_fold, dim3((p->gsz * NC * NC + 63) / 64, p->G), dim3(64), 0, p->stream, p->tp, p->red,
                            p->cam_off, p->cam_np, NC, ncp, p->Sacc);
       if (p->n_heavy)  // per-camera sums of the heavy points, one workgroup each (the pair plan skips them)
-        hipLaunchKernelGGL((k_heavy_schur<NC>), dim3(p->n_heavy), dim3(BLOCK), (size_t)ncp * 3 * sizeof(double) + (size_t)ncp * sizeof(int), p->stream,
+        hipLaunchKernelGGL((k_heavy_schur<NC>), dim3(p->n_heavy), dim3(BLOCK), heavy_schur_lds_bytes(ncp), p->stream,
                            p->heavy_pts, p->pt_start, p->obs_cam, p->cam_off, p->cam_np, ncp, p->Trec, p->tab, p->heavy_W, p->Sacc);
       if (p->con.n_con) {  // Woodbury correction of S and b for the constraint rows, one workgroup per component
         if (p->con.small)
@@ -2106,7 +2062,7 @@ static int run_newton_chain(cba_problem* p, double lam, const double* lam_dev, b
   if (small_solve) {  // small rigs: reduced system, factorisation and both substitutions in one workgroup (k_small_solve)
     RoctxRange r2("cba:cholesky");
     ScopedTimer t(p, T_CHOLESKY);
-    hipLaunchKernelGGL((k_small_solve<NC>), dim3(1), dim3(SMALL_THREADS), kSmallSolveLds, p->stream, p->Sacc, p->Sacc + (size_t)ncp * ncp, p->Upacked, p->g, p->sinv,
+    hipLaunchKernelGGL((k_small_solve<NC>), dim3(1), dim3(SMALL_THREADS), SmallSolveLds::bytes(), p->stream, p->Sacc, p->Sacc + (size_t)ncp * ncp, p->Upacked, p->g, p->sinv,
                        p->param_cam, p->param_loc, ncp, lam, lam_dev, p->cam_diag, p->S, p->rhs, fold_in_finalize ? (const double*)p->red : (const double*)nullptr,
                        p->tp.g, (long)p->tp.tile_elems, (const int*)p->tp.group_cam_begin, p->flags, p->s, p->lay.ncp_pad);
   } else {
@@ -2120,20 +2076,16 @@ static int run_newton_chain(cba_problem* p, double lam, const double* lam_dev, b
     if (p->n_heavy)  // fragments add sum_i W_i^T dc of a heavy point into s by atomics; k_heavy_finish solves for dp
       hipLaunchKernelGGL(k_zero_heavy, dim3((p->n_heavy + 63) / 64), dim3(64), 0, p->stream, p->heavy_pts, p->n_heavy, p->lay,
                          p->s + p->lay.ncp_pad, 3, p->s + p->lay.ncp_pad, 0);
-    auto launch_backsub = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(p->grid_backsub), dim3(BLOCK), lds_backsub(p), p->stream, p->obs_u, p->obs_v, p->obs_cam,
-                         p->obs_pt, p->pt_start, p->chunk_start, p->chunk_pts, p->n_chunks, p->x, p->lay, p->tab, p->cam_off, p->C, p->loss,
-                         p->f_scale, lam, lam_dev, p->V, p->g, p->sinv, p->s, p->partial4);
-    };
-    auto launch_backsub_rec = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(p->grid_backsub), dim3(BLOCK), lds_backsub_rec<NC>(p), p->stream, (const double*)p->Trec, (const int*)p->obs_cam,
+    const bool scal = fused_trial(p, compact);
+    if (p->routes.backsub_rec)
+      hipLaunchKernelGGL(backsub_rec_kernel<NC>(scal), dim3(p->grid_backsub), dim3(BLOCK), BsrCfg<NC>::lds_bytes(p->C), p->stream, (const double*)p->Trec, (const int*)p->obs_cam,
                          (const int*)p->pt_start, (const int*)p->chunk_start, (const int*)p->chunk_pts, p->n_chunks, p->lay, (const double*)p->tab,
                          (const int*)p->cam_off, (const int*)p->cam_np, p->C, lam, lam_dev, (const double*)p->V, (const double*)p->g,
                          (const double*)p->sinv, p->s, p->partial4);
-    };
-    if (p->backsub_rec) { if (fused_trial(p, compact)) launch_backsub_rec(k_backsub_rec<NC, true>); else launch_backsub_rec(k_backsub_rec<NC, false>); }
-    else if (fused_trial(p, compact)) { if (p->tab_global) launch_backsub(k_backsub<NC, true, true>); else launch_backsub(k_backsub<NC, false, true>); }
-    else if (p->tab_global) launch_backsub(k_backsub<NC, true>); else launch_backsub(k_backsub<NC>);
+    else
+      hipLaunchKernelGGL(backsub_kernel<NC>(p->routes.tab_global, scal), dim3(p->grid_backsub), dim3(BLOCK), backsub_lds(p).bytes(), p->stream, p->obs_u, p->obs_v, p->obs_cam,
+                         p->obs_pt, p->pt_start, p->chunk_start, p->chunk_pts, p->n_chunks, p->x, p->lay, p->tab, p->cam_off, p->C, p->loss,
+                         p->f_scale, lam, lam_dev, p->V, p->g, p->sinv, p->s, p->partial4);
     if (p->n_heavy)
       hipLaunchKernelGGL(k_heavy_finish, dim3((p->n_heavy + 63) / 64), dim3(64), 0, p->stream, p->heavy_pts, p->heavy_frag, p->n_heavy, p->lay, lam,
                          p->V, p->g, p->sinv, p->s);
@@ -2142,7 +2094,7 @@ static int run_newton_chain(cba_problem* p, double lam, const double* lam_dev, b
         hipLaunchKernelGGL(k_con_orphan_start, dim3((p->n_con_orphan + 63) / 64), dim3(64), 0, p->stream, (const int*)p->con_orphan, p->n_con_orphan, p->lay,
                            lam, (const double*)p->V, (const double*)p->g, (const double*)p->sinv, p->s);
       if (p->con.small)
-        hipLaunchKernelGGL(k_con_backsub_small, dim3(p->con.n_comp), dim3(BLOCK), (size_t)(9 * p->con.max_np + 2 * p->con.max_m) * sizeof(double), p->stream,
+        hipLaunchKernelGGL(k_con_backsub_small, dim3(p->con.n_comp), dim3(BLOCK), con_backsub_small_lds_bytes(p->con.max_np, p->con.max_m), p->stream,
                            p->con, p->lay, lam, p->V, p->sinv, p->s);
       else
         hipLaunchKernelGGL(k_con_backsub, dim3(p->con.n_comp), dim3(BLOCK), 0, p->stream, p->con, p->lay, lam, p->V, p->sinv, p->s);
@@ -2151,7 +2103,7 @@ static int run_newton_chain(cba_problem* p, double lam, const double* lam_dev, b
   if (fused_trial(p, compact)) {
     // step scalars (the point block's share came out of k_backsub), subspace step, camera entries and camera table of the trial point: one workgroup
     ScopedTimer t(p, T_VECTOR);
-    hipLaunchKernelGGL(k_step_cam, dim3(1), dim3(BLOCK), (size_t)p->lay.ncp_pad * sizeof(double), p->stream, (const double*)p->partial4, p->grid_backsub,
+    hipLaunchKernelGGL(k_step_cam, dim3(1), dim3(BLOCK), step_cam_lds_bytes(p->lay.ncp_pad), p->stream, (const double*)p->partial4, p->grid_backsub,
                        (const double*)p->x, (const double*)p->g, (const double*)p->sinv, (const double*)p->s, p->lay.ncp_pad, p->scal, (const int*)p->flags, p->fz,
                        p->x_new, p->partial4 + p->grid, p->tab_new, (const double*)p->cam_const, (const int*)p->cam_model, (const int*)p->cam_np,
                        (const int*)p->cam_off, p->C, p->bounds_on ? (const double*)p->lb_dev : (const double*)nullptr,
@@ -2423,7 +2375,7 @@ int cba_set_constraints(cba_problem* p, int32_t n_con, const int32_t* groups_a, 
     cp.small = (max_m <= CON_SMALL_M && !p->n_heavy && cp.small_lds <= 120 * 1024 && !(e && e[0] == '0')) ? 1 : 0;
     if (cp.small) {
       int rcl = (p->nct == 9) ? allow_lds(k_con_schur_small<9>, (size_t)cp.small_lds) : allow_lds(k_con_schur_small<6>, (size_t)cp.small_lds);
-      if (!rcl) rcl = allow_lds(k_con_backsub_small, (size_t)(9 * max_pts + 2 * max_m) * sizeof(double));
+      if (!rcl) rcl = allow_lds(k_con_backsub_small, con_backsub_small_lds_bytes(max_pts, max_m));
       if (rcl) return rcl;
     }
   }
