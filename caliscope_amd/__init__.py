@@ -8,6 +8,9 @@ _EXPORTS = {"reconstruct_trajectories": "caliscope_amd.reconstruction", "reconst
             "smoothed_frame": "caliscope_amd.trajectory_smoother", "DeviceTrajectorySmoother": "caliscope_amd.trajectory_smoother",
             "Skeleton": "caliscope_amd.trajectory_skeleton", "SkeletonOptions": "caliscope_amd.trajectory_skeleton",
             "adjust_skeleton": "caliscope_amd.trajectory_skeleton", "DeviceSkeletonAdjuster": "caliscope_amd.trajectory_skeleton",
+            "TimeOffsetOptions": "caliscope_amd.time_offsets", "TimeOffsets": "caliscope_amd.time_offsets",
+            "estimate_time_offsets": "caliscope_amd.time_offsets", "apply_time_offsets": "caliscope_amd.time_offsets",
+            "DeviceTimeOffsetSolver": "caliscope_amd.time_offsets",
             "UncertaintyReport": "caliscope_amd.uncertainty", "DeviceUncertainty": "caliscope_amd.uncertainty",
             "ReliabilityReport": "caliscope_amd.reliability", "DeviceReliability": "caliscope_amd.reliability"}
 

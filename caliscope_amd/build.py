@@ -14,9 +14,9 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 OUT = HERE / "libcaliscope_ba.so"
-SOURCES = [CSRC / "cba_lib.hip", CSRC / "cba_solve.cpp", CSRC / "pose_lib.hip", CSRC / "scale_lib.hip", CSRC / "coverage_lib.hip", CSRC / "vertical_lib.hip", CSRC / "report_lib.hip", CSRC / "trajectory_lib.hip", CSRC / "covariance_lib.hip", CSRC / "reliability_lib.hip", CSRC / "skeleton_lib.hip"]
-DEPENDS = [CSRC / "cba_kernels.h", CSRC / "schur_plan.h", CSRC / "chol_schedule.h", CSRC / "chol_factor.h", CSRC / "host_plan.h", CSRC / "kernel_plan.h", CSRC / "wg_binding.h", CSRC / "ba_math.h", CSRC / "trf_math.h", CSRC / "pnp_math.h", CSRC / "epipolar_math.h", CSRC / "intrinsic_math.h", CSRC / "frame_select_math.h", CSRC / "scale_math.h", CSRC / "coverage_math.h", CSRC / "vertical_math.h", CSRC / "report_math.h", CSRC / "trajectory_math.h", CSRC / "trajectory_refine_math.h", CSRC / "trajectory_cov_math.h", CSRC / "trajectory_smooth_math.h", CSRC / "trajectory_skeleton_math.h", CSRC / "covariance_math.h", CSRC / "covariance_constraint_math.h", CSRC / "covariance_constraint_plan.h", CSRC / "covariance_pipeline.h", CSRC / "reliability_math.h", CSRC / "reliability_constraint_math.h", CSRC / "device_call.h",
-           HERE.parent / "include" / "caliscope_ba.h", HERE.parent / "include" / "caliscope_pose.h", HERE.parent / "include" / "caliscope_coverage.h", HERE.parent / "include" / "caliscope_vertical.h", HERE.parent / "include" / "caliscope_report.h", HERE.parent / "include" / "caliscope_trajectory.h", HERE.parent / "include" / "caliscope" / "uncertainty.h", HERE.parent / "include" / "caliscope" / "uncertainty_constrained.h",HERE.parent / "include" / "caliscope" / "reliability.h", HERE.parent / "include" / "caliscope" / "reliability_constrained.h",HERE.parent / "include" / "caliscope" / "trajectory_refine.h", HERE.parent / "include" / "caliscope" / "trajectory_uncertainty.h", HERE.parent / "include" / "caliscope" / "trajectory_smoother.h", HERE.parent / "include" / "caliscope" / "trajectory_skeleton.h"]
+SOURCES = [CSRC / "cba_lib.hip", CSRC / "cba_solve.cpp", CSRC / "pose_lib.hip", CSRC / "scale_lib.hip", CSRC / "coverage_lib.hip", CSRC / "vertical_lib.hip", CSRC / "report_lib.hip", CSRC / "trajectory_lib.hip", CSRC / "covariance_lib.hip", CSRC / "reliability_lib.hip", CSRC / "skeleton_lib.hip", CSRC / "time_offset_lib.hip"]
+DEPENDS = [CSRC / "cba_kernels.h", CSRC / "schur_plan.h", CSRC / "chol_schedule.h", CSRC / "chol_factor.h", CSRC / "host_plan.h", CSRC / "kernel_plan.h", CSRC / "wg_binding.h", CSRC / "ba_math.h", CSRC / "trf_math.h", CSRC / "pnp_math.h", CSRC / "epipolar_math.h", CSRC / "intrinsic_math.h", CSRC / "frame_select_math.h", CSRC / "scale_math.h", CSRC / "coverage_math.h", CSRC / "vertical_math.h", CSRC / "report_math.h", CSRC / "trajectory_math.h", CSRC / "trajectory_refine_math.h", CSRC / "trajectory_cov_math.h", CSRC / "trajectory_smooth_math.h", CSRC / "trajectory_skeleton_math.h", CSRC / "time_offset_math.h", CSRC / "covariance_math.h", CSRC / "covariance_constraint_math.h", CSRC / "covariance_constraint_plan.h", CSRC / "covariance_pipeline.h", CSRC / "reliability_math.h", CSRC / "reliability_constraint_math.h", CSRC / "device_call.h",
+           HERE.parent / "include" / "caliscope_ba.h", HERE.parent / "include" / "caliscope_pose.h", HERE.parent / "include" / "caliscope_coverage.h", HERE.parent / "include" / "caliscope_vertical.h", HERE.parent / "include" / "caliscope_report.h", HERE.parent / "include" / "caliscope_trajectory.h", HERE.parent / "include" / "caliscope" / "uncertainty.h", HERE.parent / "include" / "caliscope" / "uncertainty_constrained.h",HERE.parent / "include" / "caliscope" / "reliability.h", HERE.parent / "include" / "caliscope" / "reliability_constrained.h",HERE.parent / "include" / "caliscope" / "trajectory_refine.h", HERE.parent / "include" / "caliscope" / "trajectory_uncertainty.h", HERE.parent / "include" / "caliscope" / "trajectory_smoother.h", HERE.parent / "include" / "caliscope" / "trajectory_skeleton.h", HERE.parent / "include" / "caliscope" / "time_offsets.h"]
 ARCH = "gfx950"
 
 
